@@ -7,13 +7,19 @@ gather (main.py:118).  Weak scaling: 64 images per GPU.  200 classes (CUB-200, B
 configs[1]) except at N = 8, where the workload is configs[3] (CARS: 196 classes, 512 images
 over 8 GPUs).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline] [--no-extra]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py --full [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline] [--no-extra]
+
+A plain run sets up, runs W warm-up steps, times K steps, writes the last timed step's outputs
+when ``--dump-outputs DIR`` is given, and prints the result line (``value``, ``ms_per_step``).
+Everything else -- the instrumented roofline pass, the other GEMM precision, the other GPU
+configs and the CPU baseline -- runs only with ``--full``.
 
 With ``--gpus N > 1`` and no torchrun environment, bench.py launches its own N ranks (a
 ``torch.distributed.run`` child, started before anything touches the GPU) and exits with
 its status; under torchrun, ``WORLD_SIZE`` must equal N.
 
-The same run also times the other GPU configs of BASELINE.json (``extra``), each with its own
+A ``--full`` run also times the other GPU configs of BASELINE.json (``extra``), each with its own
 dominant-kernel roofline; ``value`` / ``config`` stay C2.  C3 (PIP-Net ResNet-50, 128 images
 of 224x224, bf16) is a 1-GPU config: at N > 1 every rank runs its own configs[2] batch.  C5
 (CountPIPNet bilinear, 2048 prototypes, 128x128) is configs[4] = 256 images over 4 GPUs: at
@@ -55,12 +61,19 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--classes", type=int, default=None,
                     help="classifier width (default: 196 = CARS at N = 8, BASELINE configs[3]; else 200 = CUB)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the C3 / C5 timings")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the roofline pass, the other precision (--alt-precision), the C3 / C5 "
+                         "configs and the CPU baseline; a plain run only times the headline steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to DIR/<name>.npy "
+                         "(float32; proto_features as a fixed seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the C3 / C5 timings")
     ap.add_argument("--precision", choices=["fp32", "bf16x3"], default="fp32",
                     help="fp32: exact fp32 MFMA GEMMs; bf16x3: split-bf16 GEMMs (fp32 in/out, ~1e-5 per product)")
     ap.add_argument("--alt-precision", choices=["none", "fp32", "bf16x3"], default="bf16x3",
-                    help="also time this precision on the same network (reported under alt_precision)")
+                    help="with --full: also time this precision on the same network (reported under "
+                         "alt_precision)")
     ap.add_argument("--stream-split", type=int, default=None,
                     help="override the models' default stream split for the throughput pass, C3 / C5 included "
                          "(profiling runs use 1 so every launch of a kernel is a full-batch launch, as in the "
@@ -313,6 +326,37 @@ def cpu_baseline(batch=64, repeats=3):
                       f"CPU: {_cpu_model()}"}
 
 
+DUMP_SAMPLE = 1 << 22           # elements kept of an output too large to write whole (16 MB as float32)
+DUMP_WHOLE_BYTES = 16 << 20      # outputs up to this size are written whole
+DUMP_SEED = 20240613
+
+
+def dump_outputs(outdir, outputs):
+    """Write ``outputs`` (name -> tensor, what one step of the timed path returned) as
+    ``outdir/<name>.npy`` in float32.  An output above DUMP_WHOLE_BYTES is written as a fixed
+    sample: DUMP_SAMPLE elements of its flattened (logical, row-major) form at sorted indices
+    drawn once from a generator seeded with DUMP_SEED, so two runs -- or two builds -- sample
+    the same elements.  Returns {name: {"shape", "written", "sampled"}}."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    info = {}
+    for name, t in outputs.items():
+        t = t.detach()
+        n = t.numel()
+        sampled = n * 4 > DUMP_WHOLE_BYTES
+        if sampled:
+            g = torch.Generator(device="cpu")
+            g.manual_seed(DUMP_SEED)
+            idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=g, dtype=torch.int64).sort().values
+            arr = t.reshape(-1)[idx.to(t.device)]
+        else:
+            arr = t
+        arr = arr.to(torch.float32).cpu().contiguous().numpy()
+        np.save(os.path.join(outdir, name + ".npy"), arr)
+        info[name] = {"shape": list(t.shape), "written": list(arr.shape), "sampled": sampled}
+    return info
+
+
 def main():
     a = parse_args()
     launch_ranks_if_needed(a)
@@ -338,15 +382,17 @@ def main():
         if world > 1:
             dist.barrier()
 
-    def timed(model, inp, batch, steps, warmup, instrument=False, gw=None):
+    def timed(model, inp, batch, steps, warmup, instrument=False, gw=None, keep=None):
         """W warm-up steps, then K steps bracketed by barrier + synchronize, max over ranks.
+        ``keep``: a list that receives what the last timed step returned (only that step's
+        outputs are held, so the other steps allocate and free exactly as without it).
         ``instrument``: every MFMA GEMM / conv launch in the timed region is bracketed by HIP
         events on the stream it is launched on (torch's current stream) for the
         dominant-kernel roofline -- a separate pass, so the events' own cost never enters
         ``value``."""
         def step():
             with torch.no_grad():
-                model(inp, inference=True, global_batch=False, sizes=[batch] * (gw or world))
+                return model(inp, inference=True, global_batch=False, sizes=[batch] * (gw or world))
         for _ in range(warmup):
             step()
         timer = GemmTimer()
@@ -359,14 +405,19 @@ def main():
         torch.cuda.synchronize()
         timer.enabled = instrument
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             step()
+        if steps > 0:
+            last = step()
         torch.cuda.synchronize()
         barrier()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         timer.enabled = False
         kernels.set_launch_hook(None)
+        if keep is not None and steps > 0:
+            keep.append(last)
+        last = None
         agg = timer.summary()
         ev = getattr(model, "exchange_events", None)
         if ev:
@@ -401,14 +452,20 @@ def main():
 
     from count_pipnet_amd.pipnet import set_stream_split, stream_split
 
-    def measure(model, inner, inp, batch, steps, peak_of, gw=None):
-        """Throughput with the model's default stream split (clean pass), then the roofline
-        pass: one stream (per-kernel events must not overlap another stream's kernels),
-        instrumented.  ``gw``: ranks in the model's process group (default: the world); the
-        barriers and the max-over-ranks time always span the whole world.  Returns (elapsed,
-        roofline dict, agg, extra fields)."""
+    def measure(model, inner, inp, batch, steps, peak_of, gw=None, keep=None, after_timed=None):
+        """Throughput with the model's default stream split (clean pass), then -- with --full --
+        the roofline pass: one stream (per-kernel events must not overlap another stream's
+        kernels), instrumented.  ``gw``: ranks in the model's process group (default: the world);
+        the barriers and the max-over-ranks time always span the whole world.  ``keep`` as in
+        ``timed`` (clean pass); ``after_timed`` is called right after the clean pass.  Returns
+        (elapsed, roofline dict, agg, extra fields); without --full the roofline dict is None
+        and agg is empty."""
         nsplit = stream_split(inner, inp)
-        el, _ = timed(model, inp, batch, steps, a.warmup, gw=gw)
+        el, _ = timed(model, inp, batch, steps, a.warmup, gw=gw, keep=keep)
+        if after_timed is not None:
+            after_timed()
+        if not a.full:
+            return el, None, {}, {"stream_split": nsplit}
         set_stream_split(inner, 1)
         el1, agg = timed(model, inp, batch, steps, max(1, a.warmup // 2), instrument=True, gw=gw)
         set_stream_split(inner, nsplit)
@@ -421,10 +478,18 @@ def main():
         return el, roof, agg, info
 
     split = a.precision == "bf16x3"
-    elapsed, roof, agg, info = measure(sharded, net, xs, a.batch, a.steps, peak_for(split))
-    dom = roof["kernel"]
-    gemm_flops = sum(v[1] for v in agg.values())
-    gemm_time = sum(v[2] for v in agg.values())
+    kept, dumped = [], {}
+
+    def write_outputs():
+        # what a caller of the timed path received from the last timed step: proto_features (this
+        # rank's shard), pooled and logits (global batch order); rank 0 writes
+        if a.dump_outputs and rank == 0 and kept:
+            proto, pooled, out = kept[0]
+            dumped.update(dump_outputs(a.dump_outputs, {"proto_features": proto, "pooled": pooled, "logits": out}))
+        kept.clear()
+
+    elapsed, roof, agg, info = measure(sharded, net, xs, a.batch, a.steps, peak_for(split),
+                                       keep=kept if a.dump_outputs else None, after_timed=write_outputs)
     imgs = a.batch * world * a.steps
     ms = elapsed / a.steps * 1e3
     cfg_name = "configs[3]: CARS, 196 classes, 512 images over 8 GPUs" if (world == 8 and classes == 196) \
@@ -442,6 +507,7 @@ def main():
         "vs_baseline": None,
         "dtype": "f32 (bf16x3 split-product GEMMs)" if split else "f32",
         "data": "synthetic",
+        "full": a.full,
         "config": {"workload": f"PIP-Net ConvNeXt-tiny-26 forward(inference=True), 224x224, fp32, "
                                f"BASELINE {cfg_name}" + (", split-bf16 GEMMs" if split else ""),
                    "num_classes": classes, "global_batch": a.batch * world, "per_gpu_batch": a.batch,
@@ -450,16 +516,21 @@ def main():
                                 + " all_gather_into_tensor([pooled | logits])", "collectives_per_step": 1,
                                 "ms_per_step": info.get("exchange_ms_per_step"),
                                 "timing": "HIP events around the packed all-gather on the current stream, "
-                                          "roofline pass, mean over the timed steps, max over ranks"}
+                                          "roofline pass (--full only), mean over the timed steps, max over ranks"}
                                if world > 1 else None},
-        "roofline": roof,
         "model_tflops": GFLOP_C2 * a.batch / (ms * 1e-3) / 1e3,
         "model_frac_of_f32_peak": GFLOP_C2 * a.batch / (ms * 1e-3) / 1e3 / PEAK_F32_TFLOPS,
-        "gemm_all": {"tflops": gemm_flops / gemm_time / 1e12,
-                     "ms_per_step": gemm_time / a.steps * 1e3, "pass": "roofline pass (one stream)"},
     }
     result.update(info)
-    if a.alt_precision != "none" and a.alt_precision != a.precision:
+    if a.dump_outputs:
+        result["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
+    if a.full:
+        gemm_flops = sum(v[1] for v in agg.values())
+        gemm_time = sum(v[2] for v in agg.values())
+        result["roofline"] = roof
+        result["gemm_all"] = {"tflops": gemm_flops / gemm_time / 1e12,
+                              "ms_per_step": gemm_time / a.steps * 1e3, "pass": "roofline pass (one stream)"}
+    if a.full and a.alt_precision != "none" and a.alt_precision != a.precision:
         # the same network and inputs with the other GEMM precision, timed the same way
         from count_pipnet_amd.pipnet import set_hip_dtype
         set_hip_dtype(net, a.alt_precision)
@@ -477,7 +548,7 @@ def main():
     del sharded, net, xs
     torch.cuda.empty_cache()
 
-    if not a.no_extra:
+    if a.full and not a.no_extra:
         extra = {}
         for name, cfg in EXTRA.items():
             enet = make_extra(cfg, dev)
@@ -510,7 +581,7 @@ def main():
             del ewrap, enet, exs
             torch.cuda.empty_cache()
         result["extra"] = extra
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline()
     if rank == 0:
         print(json.dumps(result), flush=True)

@@ -69,9 +69,10 @@ def test_launcher_command_line(monkeypatch):
 def test_bench_self_launches_two_ranks(gpu):
     """The driver's command shape: `bench.py --gpus 2` with no torchrun wrapper starts two
     ranks (rehearsed over gloo with both on cuda:0 -- RCCL refuses two ranks on one device)
-    and rank 0 prints one JSON line with n_gpus 2 and the all-gather exchange."""
-    r = _bench(["--gpus", "2", "--dist-backend", "gloo", "--device-index", "0", "--steps", "2", "--warmup", "1",
-                "--no-cpu-baseline", "--alt-precision", "none", "--no-extra"], timeout=400)
+    and rank 0 prints one JSON line with n_gpus 2 and the all-gather exchange (event-timed in
+    the roofline pass, hence --full)."""
+    r = _bench(["--full", "--gpus", "2", "--dist-backend", "gloo", "--device-index", "0", "--steps", "2",
+                "--warmup", "1", "--no-cpu-baseline", "--alt-precision", "none", "--no-extra"], timeout=400)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -81,6 +82,63 @@ def test_bench_self_launches_two_ranks(gpu):
     assert ex["collective"] == "gloo all_gather_into_tensor([pooled | logits])" and ex["collectives_per_step"] == 1
     assert ex["ms_per_step"] is not None and ex["ms_per_step"] > 0
     assert res["config"]["num_classes"] == 200 and res["value"] > 0
+
+
+def test_plain_and_full_options():
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse_args(["--full", "--dump-outputs", "somewhere"])
+    assert a.full is True and a.dump_outputs == "somewhere"
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """Small outputs are written whole, a large one as the same seeded sample every time; all
+    float32 and far below 64 MB in total."""
+    import numpy as np
+    import torch
+
+    import bench
+    big = torch.arange(bench.DUMP_WHOLE_BYTES // 4 + 1000, dtype=torch.float64).reshape(-1, 8).t()   # strided view
+    outs = {"proto_features": big, "pooled": torch.rand(5, 7), "logits": torch.rand(5, 3, dtype=torch.float64)}
+    info = bench.dump_outputs(str(tmp_path / "a"), outs)
+    bench.dump_outputs(str(tmp_path / "b"), outs)
+    total = 0
+    for name, t in outs.items():
+        x, y = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert x.dtype == np.float32 and np.array_equal(x, y)
+        total += x.nbytes
+        if name == "proto_features":
+            assert info[name]["sampled"] and x.shape == (bench.DUMP_SAMPLE,)
+            flat = t.reshape(-1).to(torch.float32).numpy()
+            assert np.isin(x, flat).all() and len(np.unique(x)) > bench.DUMP_SAMPLE // 2
+        else:
+            assert not info[name]["sampled"] and np.array_equal(x, t.to(torch.float32).numpy())
+    assert total <= 64 << 20
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_only_and_dumps_outputs(gpu, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` prints one result line without the --full
+    sections; --dump-outputs writes the last timed step's three outputs as float32 arrays."""
+    import numpy as np
+    out = tmp_path / "dump"
+    r = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4", "--dump-outputs", str(out)],
+               timeout=300)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res["steps"] == 2 and res["warmup"] == 1 and res["full"] is False
+    assert res["unit"] == "images/sec" and res["higher_is_better"] is True and res["dtype"] == "f32"
+    assert res["ms_per_step"] > 0 and res["value"] == pytest.approx(4 / (res["ms_per_step"] * 1e-3), rel=1e-6)
+    for moved in ("roofline", "gemm_all", "roofline_pass", "alt_precision", "extra", "cpu_baseline"):
+        assert moved not in res
+    shapes = {"proto_features": (4, 768, 26, 26), "pooled": (4, 768), "logits": (4, 200)}
+    for name, shape in shapes.items():
+        x = np.load(out / f"{name}.npy")
+        assert x.dtype == np.float32 and x.shape == shape and np.isfinite(x).all()
+    assert sorted(p.name for p in out.iterdir()) == sorted(f"{n}.npy" for n in shapes)
 
 
 @pytest.mark.parametrize("world", [1, 2, 4, 8])

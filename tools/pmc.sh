@@ -7,7 +7,7 @@ R=$PWD
 O=gpurun_out/${PMC_OUT:-pmc}
 mkdir -p $O
 export TMPDIR=/tmp
-CMD="python3 $R/${PMC_TARGET:-bench.py} ${PMC_ARGS:---steps 3 --warmup 1 --no-cpu-baseline}"
+CMD="python3 $R/${PMC_TARGET:-bench.py} ${PMC_ARGS:---full --steps 3 --warmup 1 --no-cpu-baseline}"
 i=0
 for ctr in "GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVES" "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))
