@@ -6,7 +6,9 @@ streams, events and graph capture.  Nothing here computes on the host.
 """
 from __future__ import annotations
 
+import contextlib
 import functools
+import threading
 
 from typing import Optional, Tuple
 
@@ -77,6 +79,7 @@ def _num_cus() -> int:
 
 SPLITK_WG_PER_CU = int(os.environ.get("PIPNET_SPLITK_WG_PER_CU", "2"))   # env: A/B runs (tools)
 SPLITK_MIN_K = int(os.environ.get("PIPNET_SPLITK_MIN_K", "256"))          # env: A/B runs (tools)
+SPLITK_MAX_M = 512               # longer products never split K
 
 
 def splitk_factor(m: int, n: int, k: int, cus: int = 256) -> int:
@@ -84,12 +87,36 @@ def splitk_factor(m: int, n: int, k: int, cus: int = 256) -> int:
     at M = batch: 48 tiles of 64 x 128 over 151 MB of W / V): enough workgroups for
     SPLITK_WG_PER_CU per CU -- about 100 KB of LDS-DMA in flight per CU, what HBM latency
     needs -- each slab >= 8 K-tiles of 32."""
-    if n % 4 or k % 32 or m > 512:     # backbone GEMMs (M = pixels) stay batch-invariant
+    if n % 4 or k % 32 or m > SPLITK_MAX_M:     # backbone GEMMs (M = pixels) stay batch-invariant
         return 1
     tiles = -(-m // 64) * -(-n // 128)
     if tiles >= cus:
         return 1
     return max(1, min(-(-SPLITK_WG_PER_CU * cus // tiles), k // SPLITK_MIN_K, 64))
+
+
+# On small feature maps (batch * pixels <= SPLITK_MAX_M) the split-K rule above does see the batch
+# size, so a forward's last bits there depend on how many images share the call.  A caller whose
+# results must not depend on its batching (topk.prototype_topk) plans each product for ONE image's
+# rows: the slab count is then the one a single-image forward takes, and a row's arithmetic in the
+# split-K kernels depends on (K, slabs) only -- every image gets its batch-1 bits at any batch size.
+_PLAN = threading.local()
+
+
+@contextlib.contextmanager
+def per_image_gemm_plan(images: int):
+    """Inside, ``linear`` plans split-K as for m / images rows (pixel GEMMs of an ``images``-image batch)."""
+    prev = getattr(_PLAN, "images", 1)
+    _PLAN.images = max(int(images), 1)
+    try:
+        yield
+    finally:
+        _PLAN.images = prev
+
+
+def _plan_rows(m: int) -> int:
+    images = getattr(_PLAN, "images", 1)
+    return m // images if images > 1 and m % images == 0 else m
 
 
 def _ptr(t: Optional[Tensor]) -> Optional[int]:
@@ -128,7 +155,7 @@ def linear(a: Tensor, w: Tensor, bias: Optional[Tensor] = None, epilogue: int = 
     if out is None:
         out = torch.empty((m, n), device=a.device, dtype=torch.float32)
     ldr = r.stride(0) if r is not None else 0
-    splits = splitk_factor(m, n, k)
+    splits = splitk_factor(_plan_rows(m), n, k)
     if splits > 1:
         ws = torch.empty((splits, m, n), device=a.device, dtype=torch.float32)
         _launch(f"pipnet_gemm::gemm_f32_tn_kernel<32, 1, 0, 0, 3, 2, 0, false>", 2.0 * m * n * k,
@@ -633,6 +660,90 @@ def softmax_pool(feat_nhwc: Tensor, pool_mode: int, out=None) -> Tuple[Tensor, T
     _lib.call("pipnet_softmax_pool_f32", feat_nhwc.data_ptr(), b, h * w, p, pool_mode, proto.data_ptr(),
               pooled.data_ptr(), _stream(feat_nhwc))
     return proto, pooled
+
+
+def softmax_pool_argmax(feat_nhwc: Tensor, write_proto: bool = False, out=None):
+    """softmax_pool(feat, 0) that also says where each prototype's maximum sits: feat [B,h,w,P] ->
+    (proto [B,h,w,P] or None, pooled [B,P], loc [B,P] int32 = h_idx * w + w_idx by the reference's
+    two-step torch.max, util/vis_pipnet.py:235-238).  pooled (and proto, written only when
+    ``write_proto``) equal softmax_pool's bit for bit.  ``out`` = (pooled, loc) to write into."""
+    _chk(feat_nhwc, "prototype logits")
+    b, h, w, p = feat_nhwc.shape
+    dev = feat_nhwc.device
+    pooled, loc = _argmax_out(out, b, p, dev, "softmax_pool_argmax")
+    proto =torch.empty((b, h, w, p), device=dev, dtype=torch.float32) if write_proto else None
+    ws = torch.empty((max(b * p, 1),), device=dev, dtype=torch.int64)       # the packed (value, rank) keys
+    _lib.call("pipnet_softmax_pool_argmax_f32", feat_nhwc.data_ptr(), b, h, w, p, _ptr(proto), pooled.data_ptr(),
+              loc.data_ptr(), ws.data_ptr(), _stream(feat_nhwc))
+    return proto, pooled, loc
+
+
+def _argmax_out(out, b: int, p: int, dev, what: str) -> Tuple[Tensor, Tensor]:
+    """Caller-provided (value [B,P] float32, loc [B,P] int32) contiguous outputs, or new ones."""
+    if out is None:
+        return (torch.empty((b, p), device=dev, dtype=torch.float32),
+                torch.empty((b, p), device=dev, dtype=torch.int32))
+    val, loc = out
+    if tuple(val.shape) != (b, p) or tuple(loc.shape) != (b, p) or loc.dtype != torch.int32:
+        raise RuntimeError(f"{what}: out {tuple(val.shape)}, {tuple(loc.shape)} {loc.dtype} do not match "
+                           f"{(b, p)} float32 / int32")
+    _chk(val, what + " value out")
+    if not (loc.is_cuda and loc.is_contiguous()):
+        raise RuntimeError(f"{what}: loc out must be a contiguous device tensor")
+    return val, loc
+
+
+def map_argmax(map_nhwc: Tensor, out=None) -> Tuple[Tensor, Tensor]:
+    """Maximum and its location of a stored fp32 map [B,h,w,P] (NHWC memory) per (image, prototype):
+    (val [B,P], loc [B,P] int32 = h_idx * w + w_idx), the location rule of softmax_pool_argmax.
+    ``out`` = (val, loc) to write into."""
+    _chk(map_nhwc, "prototype map")
+    b, h, w, p = map_nhwc.shape
+    val, loc = _argmax_out(out, b, p, map_nhwc.device, "map_argmax")
+    _lib.call("pipnet_map_argmax_f32", map_nhwc.data_ptr(), b, h, w, p, val.data_ptr(), loc.data_ptr(),
+              _stream(map_nhwc))
+    return val, loc
+
+
+class TopkState:
+    """Device state of the streaming top-k (pipnet_topk_update): per (group, prototype) the k best
+    (score, dataset index, loc) so far, the fill counts and the abstain counter."""
+
+    def __init__(self, groups: int, prototypes: int, k: int, device):
+        if not 1 <= k <= 32:
+            raise ValueError(f"top-k: k must be in 1..32, got {k}")
+        if groups < 1 or prototypes < 1:
+            raise ValueError("top-k: needs at least one group and one prototype")
+        self.groups, self.prototypes, self.k = groups, prototypes, k
+        self.score = torch.zeros((groups, prototypes, k), device=device, dtype=torch.float32)
+        self.index = torch.full((groups, prototypes, k), -1, device=device, dtype=torch.int64)
+        self.loc = torch.full((groups, prototypes, k), -1, device=device, dtype=torch.int32)
+        self.fill = torch.zeros((groups, prototypes), device=device, dtype=torch.int32)
+        self.abstained = torch.zeros((1,), device=device, dtype=torch.int64)
+
+
+def topk_update(state: TopkState, score: Tensor, loc: Tensor, i0: int, group: Optional[Tensor] = None,
+                min_score: Optional[float] = None, out: Optional[Tensor] = None) -> TopkState:
+    """Merge one batch into ``state``: score / loc [B,P] (image b = dataset index ``i0 + b``),
+    ``group`` [B] int32 (None: all in group 0; -1 skips the image), ``min_score`` skips candidates
+    below it, ``out`` [B,K] logits feed the abstain counter.  Enqueues one kernel, no host sync."""
+    _chk(score, "top-k scores")
+    b, p = score.shape
+    if p != state.prototypes or tuple(loc.shape) != (b, p) or loc.dtype != torch.int32 or not loc.is_contiguous():
+        raise RuntimeError(f"topk_update: score {tuple(score.shape)} / loc {tuple(loc.shape)} {loc.dtype} do not "
+                           f"match {state.prototypes} prototypes")
+    if group is not None and (tuple(group.shape) != (b,) or group.dtype != torch.int32 or not group.is_cuda
+                              or not group.is_contiguous()):
+        raise RuntimeError("topk_update: group must be a contiguous int32 device tensor [B]")
+    if out is not None:
+        _chk(out, "logits")
+        if out.dim() != 2 or out.shape[0] != b:
+            raise RuntimeError(f"topk_update: logits {tuple(out.shape)} vs batch {b}")
+    _lib.call("pipnet_topk_update", score.data_ptr(), loc.data_ptr(), b, p, int(i0), _ptr(group), state.groups,
+              0 if min_score is None else 1, 0.0 if min_score is None else float(min_score), _ptr(out),
+              0 if out is None else out.shape[1], state.k, state.score.data_ptr(), state.index.data_ptr(),
+              state.loc.data_ptr(), state.fill.data_ptr(), state.abstained.data_ptr(), _stream(score))
+    return state
 
 
 def softmax_pool_linear(feat_nhwc: Tensor, w: Tensor, bias: Optional[Tensor], thresh: Optional[float],

@@ -97,6 +97,30 @@ class PIPNet(nn.Module):
         bit-identical to the one-stream forward; the head writes straight into batch slices of
         the full outputs (no concatenation copy)."""
         dev = xs.device
+        main, streams, logits = self._split_logits(xs, n)
+        b = xs.shape[0]
+        _, h, w, pn = logits[0].shape
+        k = self._classification.weight.shape[0]
+        proto = torch.empty((b, h, w, pn), device=dev, dtype=torch.float32)
+        pooled = torch.empty((b, pn), device=dev, dtype=torch.float32)
+        clamped = torch.empty((b, pn), device=dev, dtype=torch.float32)
+        out = torch.empty((b, k), device=dev, dtype=torch.float32)
+        i0 = 0
+        for s, lg in zip(streams, logits):
+            i1 = i0 + lg.shape[0]
+            s.wait_stream(main)                            # outputs allocated on main before any write
+            with torch.cuda.stream(s):
+                self._hip_head(lg, inference, out=(proto[i0:i1], pooled[i0:i1], clamped[i0:i1], out[i0:i1]))
+            i0 = i1
+        for s in streams:
+            main.wait_stream(s)
+        return nhwc_as_nchw(proto), (clamped if inference else pooled), out
+
+    def _split_logits(self, xs: Tensor, n: int):
+        """The split forward up to the prototype logits: (main stream, the n side streams, each
+        sub-batch's NHWC logits, enqueued on its stream).  The caller runs its head per stream and
+        joins the streams back into main."""
+        dev = xs.device
         main = torch.cuda.current_stream(dev)
         streams = _side_streams(dev, n)
         parts = xs.chunk(n)
@@ -117,23 +141,7 @@ class PIPNet(nn.Module):
             for s, p in zip(streams, parts):
                 with torch.cuda.stream(s):
                     logits.append(self._hip_logits(p))
-        b = xs.shape[0]
-        _, h, w, pn = logits[0].shape
-        k = self._classification.weight.shape[0]
-        proto = torch.empty((b, h, w, pn), device=dev, dtype=torch.float32)
-        pooled = torch.empty((b, pn), device=dev, dtype=torch.float32)
-        clamped = torch.empty((b, pn), device=dev, dtype=torch.float32)
-        out = torch.empty((b, k), device=dev, dtype=torch.float32)
-        i0 = 0
-        for s, lg in zip(streams, logits):
-            i1 = i0 + lg.shape[0]
-            s.wait_stream(main)                            # outputs allocated on main before any write
-            with torch.cuda.stream(s):
-                self._hip_head(lg, inference, out=(proto[i0:i1], pooled[i0:i1], clamped[i0:i1], out[i0:i1]))
-            i0 = i1
-        for s in streams:
-            main.wait_stream(s)
-        return nhwc_as_nchw(proto), (clamped if inference else pooled), out
+        return main, streams, logits
 
 
 # Concurrent sub-batches: batches of at least STREAM_SPLIT_MIN_BATCH images run as n

@@ -54,7 +54,9 @@ extern "C" {
  * mutable library state -- and the one-launch fused head pipnet_softmax_pool_linear_f32 / _bf16
  * (+ _part_floats) and pipnet_matmul2_f64acc_f32 are new (round 5).  A caller built against an older version must not bind this library.
  * Round 6 only ADDS entry points (pipnet_philox_exp1_f32, pipnet_conv2d_nhwc_bf16_plan,
- * pipnet_linear_f32_plan, pipnet_cnblock_mlp_plan); no signature changed. */
+ * pipnet_linear_f32_plan, pipnet_cnblock_mlp_plan); no signature changed.  The prototype
+ * explanation entry points (pipnet_softmax_pool_argmax_f32, pipnet_map_argmax_f32,
+ * pipnet_topk_update) are additions as well. */
 #define PIPNET_AMD_ABI_VERSION 3
 int pipnet_amd_abi_version(void);
 const char* pipnet_amd_status_string(int status);
@@ -291,6 +293,36 @@ int pipnet_layernorm_f32(const float* x, int64_t rows, int C, const float* w, co
  * feat, proto: [B,HW,P]; pooled: [B,P] (zeroed by this call before accumulation). */
 int pipnet_softmax_pool_f32(const float* feat, int B, int HW, int P, int pool_mode, float* proto,
                             float* pooled, void* stream);
+
+/* ---- prototype explanations (util/vis_pipnet.py:187-275, 652-755: the top-k patches per
+ * prototype; csrc/explain.hip) -------------------------------------------------------------
+ * Location rule, everywhere below: the reference's two-step max (vis_pipnet.py:235-238)
+ *   max_h, h_idx = torch.max(map, dim=0); max_w, w_idx = torch.max(max_h, dim=0)
+ * i.e. among the pixels holding the map's maximum the smallest w, then the smallest h in that
+ * column (column-major first, NOT the flat row-major argmax).  loc = h * W + w.
+ *
+ * pipnet_softmax_pool_argmax_f32: pipnet_softmax_pool_f32 (pool_mode 0) that also reports where
+ *   each prototype's maximum sits.  feat [B,H,W,P] NHWC logits; pooled [B,P] and proto (when
+ *   non-NULL; NULL skips the store of the map) are bit for bit pipnet_softmax_pool_f32's; loc
+ *   [B,P] int32; an all-zero map gives value 0 at (0,0).  workspace: B * P * 8 bytes, 8-B aligned
+ *   (zeroed by this call).  B <= 65535.
+ * pipnet_map_argmax_f32: value and location of the maximum of a stored fp32 NHWC map [B,H,W,P] of
+ *   any sign (the CountPIPNet 0/1 map, the bf16 head's fp32 proto map).  NaN entries are passed over.
+ * pipnet_topk_update: one batch merged into the running top-k of every (group, prototype):
+ *   score / loc [B,P] (loc >= 0), image b has dataset index i0 + b; group [B] int32 or NULL (all in group 0),
+ *   an id outside [0, G) -- e.g. -1 -- skips the image; use_min: candidates with score < min_score
+ *   are skipped.  State (caller-owned, device): st_score [G,P,k] fp32, st_index [G,P,k] int64
+ *   (initialise to -1 = empty slot), st_loc [G,P,k] int32, st_fill [G,P] int32 (initialise to 0).
+ *   After any sequence of calls the state is the reference's one-image-at-a-time list
+ *   (vis_pipnet.py:248-274): the k best by (score descending, dataset index ascending).
+ *   1 <= k <= 32.  out [B,K] (NULL to skip): images with amax(out) == 0 are added to *abstained
+ *   (device int64; vis_pipnet.py:217-219), whatever their group. */
+int pipnet_softmax_pool_argmax_f32(const float* feat, int B, int H, int W, int P, float* proto, float* pooled,
+                                   int32_t* loc, void* workspace, void* stream);
+int pipnet_map_argmax_f32(const float* map, int B, int H, int W, int P, float* val, int32_t* loc, void* stream);
+int pipnet_topk_update(const float* score, const int32_t* loc, int B, int P, int64_t i0, const int32_t* group,
+                       int G, int use_min, float min_score, const float* out, int K, int k, float* st_score,
+                       int64_t* st_index, int32_t* st_loc, int32_t* st_fill, int64_t* abstained, void* stream);
 
 /* Fused CNBlock MLP of the narrow ConvNeXt stages (torchvision CNBlock block.3-5 + layer_scale +
  * residual; the Linear / GELU / Linear of features.1 and features.3):

@@ -1,0 +1,346 @@
+"""Device-side prototype top-k (count_pipnet_amd.topk, csrc/explain.hip) on the GPU.
+
+* the fused softmax + max-pool + arg-location kernel against the existing, unchanged
+  K.softmax_pool (pooled / proto bitwise) and the reference's two-step torch.max on the CPU;
+* the map arg-location kernel on random and 0/1 maps;
+* the streaming top-k against the CPU sort by (-score, index), whatever the batching;
+* prototype_topk end to end against a restatement of the reference loop
+  (util/vis_pipnet.py:187-275, :652-755) on the existing forward's own outputs, and against the
+  CPU oracle where the oracle's own values are decisive.
+"""
+import argparse
+
+import numpy as np
+import pytest
+import torch
+
+from count_pipnet_amd import kernels as K
+from count_pipnet_amd.synthetic import synth_exponential, synth_images
+from count_pipnet_amd.topk import COUNT_MIN_SCORE, img_coordinates, patch_size, prototype_topk
+from golden_util import golden_args, load_golden
+from model_util import build_model
+from oracle import ref_cpu
+
+pytestmark = pytest.mark.gpu
+
+
+def two_step_loc(proto_nchw):
+    """vis_pipnet.py:235-238 for every (image, prototype) of a CPU [B,P,H,W] map -> (h_idx, w_idx)."""
+    max_h, h_idx = torch.max(proto_nchw, dim=2)          # over H: [B,P,W]
+    _, w_idx = torch.max(max_h, dim=2)                   # over W: [B,P]
+    return h_idx.gather(2, w_idx.unsqueeze(-1)).squeeze(-1), w_idx
+
+
+# ---- kernel (a) -------------------------------------------------------------------------------
+def _planted_logits(b, h, w, p, seed):
+    """N(0,1) logits with exact ties: identical saturated pixel rows (softmax exactly 1.0f at p0) at
+    (3,1), (0,4), (2,1) -- column-first winner (2,1), flat argmax would say (0,4); on 5x7 maps the
+    pair (4,5) / (0,6) for p1 sits in two workgroups (pixels 33 and 6) -- winner (4,5); channel p2
+    is -200 everywhere: softmax exactly 0, location (0,0)."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(b, h, w, p, generator=g)
+    p0, p1, p2 = 3, 7, 11
+    row0 = torch.randn(p, generator=g)
+    row0[p0] = 40.0
+    for hh, ww in ((3, 1), (0, 4), (2, 1)):
+        x[:, hh, ww] = row0
+    planted = {p0: (2, 1)}
+    if (h, w) == (5, 7):
+        row1 = torch.randn(p, generator=g)
+        row1[p1] = 40.0
+        x[:, 4, 5] = row1
+        x[:, 0, 6] = row1
+        planted[p1] = (4, 5)
+    x[..., p2] = -200.0
+    planted[p2] = (0, 0)
+    return x, planted
+
+
+@pytest.mark.parametrize("shape", [(3, 5, 7, 32), (2, 8, 8, 100), (2, 13, 13, 768)])
+def test_softmax_pool_argmax_matches_existing_head_and_two_step_max(gpu, shape):
+    b, h, w, p = shape
+    x, planted = _planted_logits(b, h, w, p, seed=sum(shape))
+    xd = x.to(gpu)
+    proto0, pooled0 = K.softmax_pool(xd, 0)
+    none, pooled1, loc1 = K.softmax_pool_argmax(xd)
+    proto2, pooled2, loc2 = K.softmax_pool_argmax(xd, write_proto=True)
+    torch.cuda.synchronize()
+    assert none is None
+    assert torch.equal(pooled1, pooled0) and torch.equal(pooled2, pooled0)          # bitwise
+    assert torch.equal(proto2, proto0)
+    assert torch.equal(loc1, loc2)
+    h_ref, w_ref = two_step_loc(proto0.cpu().permute(0, 3, 1, 2))
+    loc = loc1.cpu().long()
+    assert torch.equal(loc // w, h_ref) and torch.equal(loc % w, w_ref)
+    for ch, (hh, ww) in planted.items():
+        assert (loc[:, ch] == hh * w + ww).all(), (ch, loc[:, ch])
+    assert (pooled1[:, 3] == 1.0).all() and (pooled1[:, 11] == 0.0).all()
+
+
+def test_softmax_pool_argmax_writes_into_batch_slices(gpu):
+    x, _ = _planted_logits(4, 5, 7, 32, seed=5)
+    xd = x.to(gpu)
+    _, pooled, loc = K.softmax_pool_argmax(xd)
+    pooled_s = torch.full((4, 32), -1.0, device=gpu)
+    loc_s = torch.full((4, 32), -7, device=gpu, dtype=torch.int32)
+    K.softmax_pool_argmax(xd[1:3], out=(pooled_s[1:3], loc_s[1:3]))
+    assert torch.equal(pooled_s[1:3], pooled[1:3]) and torch.equal(loc_s[1:3], loc[1:3])
+    assert (pooled_s[0] == -1).all() and (loc_s[3] == -7).all()
+
+
+# ---- kernel (b) -------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", [(3, 5, 7, 32), (2, 16, 16, 16)])
+@pytest.mark.parametrize("kind", ["random", "onehot"])
+def test_map_argmax(gpu, shape, kind):
+    b, h, w, p = shape
+    g = torch.Generator().manual_seed(17 + h)
+    if kind == "random":
+        m = torch.randn(b, h, w, p, generator=g)           # any sign
+    else:
+        m = (torch.rand(b, h, w, p, generator=g) < 0.1).float()
+        m[0, :, :, 0] = 0.0                                 # an all-zero map: value 0 at (0,0)
+    val, loc = K.map_argmax(m.to(gpu))
+    nchw = m.permute(0, 3, 1, 2)
+    h_ref, w_ref = two_step_loc(nchw)
+    loc = loc.cpu().long()
+    assert torch.equal(val.cpu(), nchw.amax(dim=(2, 3)))
+    assert torch.equal(loc // w, h_ref) and torch.equal(loc % w, w_ref)
+    if kind == "onehot":
+        assert val[0, 0] == 0 and loc[0, 0] == 0
+
+
+# ---- kernel (c) -------------------------------------------------------------------------------
+def _topk_expected(score, loc, k, groups=None, g=0, min_score=None):
+    """The k best by (score descending, dataset index ascending) per prototype, -1 padded."""
+    n, p = score.shape
+    s_out = np.zeros((p, k), np.float32)
+    i_out = -np.ones((p, k), np.int64)
+    l_out = -np.ones((p, k), np.int32)
+    for pp in range(p):
+        cand = [(-float(score[i, pp]), i) for i in range(n)
+                if (groups is None or groups[i] == g) and (min_score is None or score[i, pp] >= min_score)]
+        for j, (ns, i) in enumerate(sorted(cand)[:k]):
+            s_out[pp, j], i_out[pp, j], l_out[pp, j] = -ns, i, loc[i, pp]
+    return s_out, i_out, l_out
+
+
+def _topk_inputs(n, p, seed):
+    g = torch.Generator().manual_seed(seed)
+    levels = torch.tensor([0.0, 0.1, 0.25, 0.5, 1.0])
+    score = levels[torch.randint(0, 5, (n, p), generator=g)]
+    loc = torch.randint(0, 64, (n, p), generator=g, dtype=torch.int32)
+    return score, loc
+
+
+def _feed(gpu, score, loc, k, splits, groups=None, n_groups=1, min_score=None, out=None):
+    st = K.TopkState(n_groups, score.shape[1], k, gpu)
+    i0 = 0
+    for nb in splits:
+        sl = slice(i0, i0 + nb)
+        K.topk_update(st, score[sl].to(gpu), loc[sl].to(gpu), i0,
+                      group=None if groups is None else groups[sl].to(gpu), min_score=min_score,
+                      out=None if out is None else out[sl].to(gpu))
+        i0 += nb
+    assert i0 == score.shape[0]
+    return st
+
+
+@pytest.mark.parametrize("n,k", [(40, 1), (40, 10), (6, 10)])
+def test_topk_update_is_batching_invariant_and_matches_cpu_sort(gpu, n, k):
+    p = 70
+    score, loc = _topk_inputs(n, p, seed=n + k)
+    splits = [[1] * n, [7] * (n // 7) + ([n % 7] if n % 7 else []), [n]]
+    states = [_feed(gpu, score, loc, k, s) for s in splits]
+    s_ref, i_ref, l_ref = _topk_expected(score.numpy(), loc.numpy(), k)
+    for st in states:
+        assert np.array_equal(st.score[0].cpu().numpy(), s_ref)
+        assert np.array_equal(st.index[0].cpu().numpy(), i_ref)
+        assert np.array_equal(st.loc[0].cpu().numpy(), l_ref)
+        assert (st.fill[0].cpu() == min(n, k)).all()
+    if n < k:
+        assert (states[0].index[0, :, n:] == -1).all()
+
+
+def test_topk_update_groups_min_score_and_abstain(gpu):
+    n, p, k, ng = 40, 70, 10, 3
+    score, loc = _topk_inputs(n, p, seed=99)
+    g = torch.Generator().manual_seed(3)
+    groups = torch.randint(-1, ng, (n,), generator=g, dtype=torch.int32)
+    assert (groups == -1).any()
+    out = torch.rand(n, 9, generator=g)
+    out[::5] = 0.0                                         # abstained images, whatever their group
+    out[1] = -out[1]                                       # largest logit below zero: not abstained
+    for splits in ([1] * n, [7, 7, 7, 7, 7, 5], [n]):
+        st = _feed(gpu, score, loc, k, splits, groups=groups, n_groups=ng, min_score=0.2, out=out)
+        for gi in range(ng):
+            s_ref, i_ref, l_ref = _topk_expected(score.numpy(), loc.numpy(), k, groups.numpy(), gi, 0.2)
+            assert np.array_equal(st.score[gi].cpu().numpy(), s_ref)
+            assert np.array_equal(st.index[gi].cpu().numpy(), i_ref)
+            assert np.array_equal(st.loc[gi].cpu().numpy(), l_ref)
+        assert int(st.abstained) == 8
+
+
+# ---- end to end, PIP-Net ------------------------------------------------------------------------
+def _reference_lists(outputs, k, protos, min_score=None, groups=None):
+    """The reference loop (vis_pipnet.py:227-274 / :698-754), one image at a time on CPU copies of a
+    forward's outputs: outputs[i] = (proto [1,P,H,W], pooled [1,P], out [1,K]); groups[i] selects the
+    list an image goes to.  Returns ({(p, group): [(score, index, h_idx, w_idx), ...]}, abstained)."""
+    lists, abstained = {}, 0
+    for i, (proto, pooled, out) in enumerate(outputs):
+        if torch.amax(out, dim=1)[0].item() == 0.0:
+            abstained += 1
+        for p in protos:
+            score = pooled.squeeze(0)[p].item()
+            if min_score is not None and score < min_score:
+                continue
+            fmap = proto.squeeze(0)[p]
+            max_h, h_idx = torch.max(fmap, dim=0)
+            _, w_idx = torch.max(max_h, dim=0)
+            item = (score, i, h_idx[w_idx].item(), w_idx.item())
+            lst = lists.setdefault((p, None if groups is None else groups[i]), [])
+            if len(lst) < k:
+                lst.append(item)
+                lst.sort(key=lambda t: t[0], reverse=True)
+            elif score > lst[-1][0]:
+                lst[-1] = item
+                lst.sort(key=lambda t: t[0], reverse=True)
+    return lists, abstained
+
+
+def _assert_lists(res, lists, k, image_size):
+    """Every slot of a (host) PrototypeTopK equals the reference lists, coordinates included."""
+    pn, ng = res.scores.shape[:2]
+    _, _, h, w = res.proto_shape
+    _, skip = patch_size(argparse.Namespace(image_size=image_size, wshape=w))
+    for p in range(pn):
+        for gi, gval in enumerate(res.groups):
+            lst = lists.get((p, gval), [])
+            for j in range(k):
+                if j < len(lst):
+                    score, idx, hh, ww = lst[j]
+                    assert res.scores[p, gi, j].item() == score, (p, gval, j)
+                    assert res.index[p, gi, j].item() == idx, (p, gval, j)
+                    assert (res.h_idx[p, gi, j].item(), res.w_idx[p, gi, j].item()) == (hh, ww), (p, gval, j)
+                    assert tuple(res.coords[p, gi, j].tolist()) == img_coordinates(image_size, res.proto_shape, 32,
+                                                                                   skip, hh, ww)
+                else:
+                    assert res.index[p, gi, j].item() == -1 and res.scores[p, gi, j].item() == 0.0
+                    assert res.h_idx[p, gi, j].item() == -1 and (res.coords[p, gi, j] == -1).all()
+
+
+def _batches(xs, ys, bs):
+    return [(xs[i:i + bs], ys[i:i + bs]) for i in range(0, xs.shape[0], bs)]
+
+
+@pytest.fixture(scope="module")
+def pipnet_case(gpu):
+    meta, _ = load_golden("pipnet_mid_addon")
+    net = build_model(meta).to(gpu)
+    xs = torch.cat([synth_images(4, 64, seed=700 + i) for i in range(3)])
+    with torch.no_grad():
+        outputs = [tuple(t.float().cpu() for t in net(xs[i:i + 1].to(gpu), inference=True)) for i in range(12)]
+    return meta, net, xs, outputs
+
+
+def test_prototype_topk_pipnet_matches_reference_loop(gpu, pipnet_case):
+    meta, net, xs, outputs = pipnet_case
+    ys = torch.zeros(12, dtype=torch.int64)
+    k = 3
+    lists, abstained = _reference_lists(outputs, k, range(32))
+    results = [prototype_topk(net, _batches(xs, ys, bs), k, image_size=64).cpu() for bs in (1, 5, 12)]
+    for res in results:
+        assert res.proto_shape == (1, 32, 8, 8) and res.groups == [None]
+        assert tuple(res.scores.shape) == (32, 1, k) and tuple(res.coords.shape) == (32, 1, k, 4)
+        _assert_lists(res, lists, k, 64)
+        assert int(res.abstained) == abstained
+        for a, b in zip((res.scores, res.index, res.h_idx, res.w_idx, res.coords, res.selected, res.unused),
+                        (results[0].scores, results[0].index, results[0].h_idx, results[0].w_idx, results[0].coords,
+                         results[0].selected, results[0].unused)):
+            assert torch.equal(a, b)
+        importance = net._classification.weight.detach().cpu().max(dim=0).values
+        assert torch.equal(res.selected, importance > 0.1)
+        used = torch.tensor([any(t[0] > 0.1 for t in lists.get((p, None), [])) for p in range(32)])
+        assert torch.equal(res.unused, res.selected & ~used)
+    # wrappers: a .module holder and ShardedInference at world size 1; pretraining selects all
+    from count_pipnet_amd.dist import ShardedInference
+    res_w = prototype_topk(ShardedInference(net), _batches(xs, ys, 12), k, image_size=64, pretraining=True).cpu()
+    assert torch.equal(res_w.index, results[0].index) and bool(res_w.selected.all())
+
+
+def test_prototype_topk_pipnet_against_cpu_oracle(gpu, pipnet_case):
+    """Locations on every (image, prototype) whose two largest spatial values differ by more than
+    2e-3 in the oracle (twice the project's 1e-3 parity), top-k indices on every prototype whose
+    neighbouring top-(k+1) oracle scores differ by more than 2e-3; at most 5 % of the pairs and
+    15 % of the prototypes may be excluded (the oracle alone: 2.1 % and 9.4 % on these images)."""
+    meta, net, xs, _ = pipnet_case
+    k, n, pn = 3, 12, 32
+    sd = {key: v.cpu() for key, v in net.state_dict().items()}
+    with torch.no_grad():
+        r_proto, r_pooled, _ = ref_cpu.pipnet_forward(xs, sd, golden_args(meta), inference=True)
+    ys = torch.zeros(n, dtype=torch.int64)
+    full = prototype_topk(net, _batches(xs, ys, 5), n, image_size=64).cpu()        # k = 12: every image kept
+    assert (full.index >= 0).all()
+    loc = torch.empty(n, pn, dtype=torch.int64)
+    loc.scatter_(0, full.index[:, 0].t(), (full.h_idx[:, 0] * 8 + full.w_idx[:, 0]).t())
+    top2 = r_proto.flatten(2).topk(2, dim=2).values
+    decisive = (top2[..., 0] - top2[..., 1]) > 2e-3
+    h_ref, w_ref = two_step_loc(r_proto)
+    excluded = 1.0 - decisive.float().mean().item()
+    print(f"location pairs excluded: {100 * excluded:.1f} %")
+    assert excluded <= 0.05
+    assert torch.equal(loc[decisive], (h_ref * 8 + w_ref)[decisive])
+    res = prototype_topk(net, _batches(xs, ys, 5), k, image_size=64).cpu()
+    order = sorted(range(n))
+    kept = 0
+    for p in range(pn):
+        ranked = sorted(order, key=lambda i: (-float(r_pooled[i, p]), i))[:k + 1]
+        sc = [float(r_pooled[i, p]) for i in ranked]
+        if all(sc[j] - sc[j + 1] > 2e-3 for j in range(k)):
+            kept += 1
+            assert res.index[p, 0].tolist() == ranked[:k], p
+    print(f"prototypes excluded: {100 * (1 - kept / pn):.1f} %")
+    assert 1 - kept / pn <= 0.15
+
+
+# ---- end to end, CountPIPNet ----------------------------------------------------------------------
+def test_prototype_topk_count_matches_reference_loop(gpu):
+    """count_onehot golden (9 classes, hard Gumbel head) with injected Exp(1) noise, the same per-image
+    slices for the batch-1 reference forwards: group routing by class, the 0.01 floor and the
+    column-first location on the 0/1 maps."""
+    meta, _ = load_golden("count_onehot")
+    net = build_model(meta).to(gpu)
+    n, k = 12, 3
+    xs = torch.cat([synth_images(4, 64, seed=800 + i) for i in range(3)])
+    ys = torch.randint(0, 9, (n,), generator=torch.Generator().manual_seed(8))
+    noise = synth_exponential((n, 16, 8, 8), seed=77).to(gpu)
+    head = net._add_on[-1]
+
+    def loader(bs):
+        for i in range(0, n, bs):
+            head.exp_noise = noise[i:i + bs]
+            yield xs[i:i + bs], ys[i:i + bs]
+
+    outputs = []
+    with torch.no_grad():
+        for i in range(n):
+            head.exp_noise = noise[i:i + 1]
+            outputs.append(tuple(t.float().cpu() for t in net(xs[i:i + 1].to(gpu), inference=True)))
+    groups = [int(y) // 3 + 1 for y in ys]                  # classes 1-3 -> 1, 4-6 -> 2, 7-9 -> 3 (labels 0-based)
+    lists, abstained = _reference_lists(outputs, k, range(16), min_score=COUNT_MIN_SCORE, groups=groups)
+    assert any(o[1].min() < COUNT_MIN_SCORE for o in outputs), "no count below the floor: the floor is untested"
+    first = None
+    for bs in (1, 5, 12):
+        res = prototype_topk(net, loader(bs), k, image_size=64).cpu()
+        assert res.groups == [1, 2, 3] and tuple(res.scores.shape) == (16, 3, k)
+        _assert_lists(res, lists, k, 64)
+        assert int(res.abstained) == abstained
+        first = first or res
+        assert torch.equal(res.index, first.index) and torch.equal(res.coords, first.coords)
+    importance = torch.tensor([net.get_prototype_importance(p) for p in range(16)])
+    assert torch.equal(first.selected, importance > 0.1)
+    # a class outside the mapping is an error, as in the reference
+    head.exp_noise = noise[:1]
+    with pytest.raises(ValueError):
+        prototype_topk(net, [(xs[:1], torch.tensor([9]))], k, image_size=64)
+    with pytest.raises(ValueError):
+        prototype_topk(net, [(xs[:1], torch.tensor([9], device=gpu))], k, image_size=64)
