@@ -345,7 +345,7 @@ def convnext_features_hip_steps(features: nn.Sequential, x: Tensor, cache: Dict,
                                 sd_keep: Optional[Dict[int, object]] = None, precision: str = "fp32"):
     """Generator form of convnext_features_hip: yields after the stem, every CNBlock and every
     downsample (the launches of that stage are enqueued by then), returns the NHWC features --
-    so concurrent sub-batch forwards can enqueue block by block (pipnet._forward_hip_split).
+    so concurrent sub-batch forwards can enqueue block by block (pipnet.sub_batch_logits).
     Run a (possibly truncated, stride-patched) ConvNeXt ``features`` on the HIP kernels.
     ``sd_keep``: train-mode stochastic depth, block id (0..17 in module order) -> per-sample
     keep mask for every block with p > 0 (eval / None: no stochastic depth).

@@ -20,12 +20,11 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import kernels as K
-from .backend import cross_stream_forward, packed_ready, use_hip
-from .convnext_features import as_nhwc, convnext_tiny_13_features, convnext_tiny_26_features, nhwc_as_nchw
+from .backend import packed_ready, use_hip
+from .convnext_features import convnext_tiny_13_features, convnext_tiny_26_features, nhwc_as_nchw
 from .count_pipnet_utils import (BilinearIntermediate, ClampSTE, GumbelSoftmax, IdentityIntermediate,
                                  LinearFull, LinearIntermediate, OneHotEncoder, STE_Round)
-from . import pipnet as _pipnet
-from .pipnet import _side_streams, add_on_logits_hip, interleaved_features, stream_split
+from .pipnet import add_on_activation, rows, run_heads, stream_split, sub_batch_logits
 
 
 class CountPIPNet(nn.Module):
@@ -67,93 +66,51 @@ class CountPIPNet(nn.Module):
 
     # -- HIP inference path ---------------------------------------------------------------
     def _forward_hip(self, xs, inference):
+        """Backbone, add-on and count head per sub-batch (pipnet.sub_batch_logits / run_heads; one
+        sub-batch on the current stream by default), then the count -> classifier layers once on
+        the whole batch (the Bilinear intermediate streams 101 MB of folded weights per call).
+        Per-image results are batch-invariant and the Gumbel noise of the sub-batch that starts at
+        image i0 starts at Philox block i0*h*w*P/4, so the outputs do not depend on the split."""
         K.require_device(xs, "input images")
         n = stream_split(self, xs)
-        # (the Philox offset of a sub-batch, b0*h*w*P/4 blocks, is exact for P % 4 == 0)
-        if n > 1 and self._num_prototypes % 4 == 0 and not torch.cuda.is_current_stream_capturing():
-            with cross_stream_forward():
-                return self._forward_hip_split(xs, inference, n)
-        feats = as_nhwc(self._net(xs))
-        act = list(self._add_on)[-1] if isinstance(self._add_on, nn.Sequential) else self._add_on
-        do_round = bool(self._use_ste or inference)
-        if isinstance(act, GumbelSoftmax):
-            logits = add_on_logits_hip(self._add_on, feats, activation=GumbelSoftmax)
-            noise = act.exp_noise
-            if noise is not None:
-                noise = noise.to(device=logits.device, dtype=torch.float32).contiguous()
-                proto, hist = K.count_gumbel(logits, act.tau, noise, 0)
-            elif torch.cuda.is_current_stream_capturing():
-                # HIP-graph capture: the key must live in device memory so that every replay
-                # draws fresh noise (count_pipnet_amd.graph)
-                proto, hist = K.count_gumbel_devseed(logits, act.tau, self._graph_seed_state(logits.device))
-            else:
-                seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())   # fresh noise per call
-                proto, hist = K.count_gumbel(logits, act.tau, None, seed)
-            counts, clamped = K.count_finish(hist, None, self._max_count, do_round)
-        else:
-            logits = add_on_logits_hip(self._add_on, feats, activation=nn.Softmax)
-            proto, sums = K.softmax_pool(logits, pool_mode=1)
-            counts, clamped = K.count_finish(None, sums, self._max_count, do_round)
-        inter = intermediate_hip(self._intermediate, clamped)
-        cls = self._classification
-        _, out = K.nonneg_linear(inter, cls.weight, cls.bias, None)
-        return nhwc_as_nchw(proto), (clamped if inference else counts), out
-
-    def _forward_hip_split(self, xs, inference, n):
-        """The backbone, add-on and count head of n sub-batches on n concurrent HIP streams
-        (pipnet.PIPNet._forward_hip_split), joined before the count -> classifier layers, which
-        run once on the whole batch (the Bilinear intermediate streams 101 MB of folded weights
-        per call).  Per-image results are batch-invariant and the Gumbel noise of sub-batch image
-        b0 starts at Philox block b0*h*w*P/4, so the outputs equal the one-stream forward's."""
-        dev = xs.device
-        main = torch.cuda.current_stream(dev)
-        streams = _side_streams(dev, n)
-        parts = xs.chunk(n)
-        act = list(self._add_on)[-1] if isinstance(self._add_on, nn.Sequential) else self._add_on
+        # (the Philox offset of a sub-batch, i0*h*w*P/4 blocks, is exact for P % 4 == 0)
+        if n > 1 and (self._num_prototypes % 4 != 0 or torch.cuda.is_current_stream_capturing()):
+            n = 1
+        act = add_on_activation(self._add_on)
         gumbel = isinstance(act, GumbelSoftmax)
-        kind = GumbelSoftmax if gumbel else nn.Softmax
-        for s in streams:
-            s.wait_stream(main)
-        if _pipnet.INTERLEAVE and hasattr(self._net, "hip_steps") and use_hip(self._net):
-            feats = interleaved_features(self._net, parts, streams)
-        else:
-            feats = []
-            for s, p in zip(streams, parts):
-                with torch.cuda.stream(s):
-                    feats.append(as_nhwc(self._net(p)))
-        logits = []
-        for s, f in zip(streams, feats):
-            with torch.cuda.stream(s):
-                logits.append(add_on_logits_hip(self._add_on, f, activation=kind))
+        streams, logits = sub_batch_logits(self, xs, n, GumbelSoftmax if gumbel else nn.Softmax)
+        dev = xs.device
         b = xs.shape[0]
         _, h, w, pn = logits[0].shape
-        proto = torch.empty((b, h, w, pn), device=dev, dtype=torch.float32)
-        noise = seed = None
+        noise = seed_state = None
+        seed = 0
         if gumbel:
-            hist = torch.empty((b, pn), device=dev, dtype=torch.int32)
             noise = act.exp_noise
             if noise is not None:
                 noise = noise.to(device=dev, dtype=torch.float32).contiguous()
+            elif torch.cuda.is_current_stream_capturing():
+                # HIP-graph capture: the key must live in device memory so that every replay
+                # draws fresh noise (count_pipnet_amd.graph)
+                seed_state = self._graph_seed_state(dev)
             else:
-                seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
-        else:
-            sums = torch.empty((b, pn), device=dev, dtype=torch.float32)
-        i0 = 0
-        for s, lg in zip(streams, logits):
-            i1 = i0 + lg.shape[0]
-            s.wait_stream(main)                            # outputs allocated on main before any write
-            with torch.cuda.stream(s):
-                if gumbel:
-                    K.count_gumbel(lg, act.tau, None if noise is None else noise[i0:i1], seed or 0,
-                                   offset=i0 * h * w * pn // 4, out=(proto[i0:i1], hist[i0:i1]))
-                else:
-                    K.softmax_pool(lg, pool_mode=1, out=(proto[i0:i1], sums[i0:i1]))
-            i0 = i1
-        for s in streams:
-            main.wait_stream(s)
-        do_round = bool(self._use_ste or inference)
-        counts, clamped = K.count_finish(hist if gumbel else None, None if gumbel else sums, self._max_count,
-                                         do_round)
+                seed = _fresh_seed()                       # fresh noise per call, one key per batch
+        outs = (torch.empty((b, h, w, pn), device=dev, dtype=torch.float32),                       # proto
+                torch.empty((b, pn), device=dev, dtype=torch.int32 if gumbel else torch.float32))  # hist | sums
+
+        def head(lg, i0, i1):
+            out = rows(outs, i0, i1)
+            if not gumbel:
+                K.softmax_pool(lg, pool_mode=1, out=out)
+            elif seed_state is not None:
+                K.count_gumbel_devseed(lg, act.tau, seed_state, out=out)
+            else:
+                K.count_gumbel(lg, act.tau, None if noise is None else noise[i0:i1], seed,
+                               offset=i0 * h * w * pn // 4, out=out)
+
+        run_heads(streams, logits, head)
+        proto, pooled = outs
+        counts, clamped = K.count_finish(pooled if gumbel else None, None if gumbel else pooled, self._max_count,
+                                         bool(self._use_ste or inference))
         inter = intermediate_hip(self._intermediate, clamped)
         cls = self._classification
         _, out = K.nonneg_linear(inter, cls.weight, cls.bias, None)
@@ -162,8 +119,7 @@ class CountPIPNet(nn.Module):
     def _graph_seed_state(self, device):
         st = getattr(self, "_hip_seed_state", None)
         if st is None or st.device != device:
-            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
-            st = torch.tensor([seed, 0], dtype=torch.int64, device=device)
+            st = torch.tensor([_fresh_seed(), 0], dtype=torch.int64, device=device)
             self._hip_seed_state = st           # plain attribute: not a parameter / buffer
         return st
 
@@ -189,6 +145,11 @@ class CountPIPNet(nn.Module):
             if isinstance(module, GumbelSoftmax):
                 module.tau = new_temperature
                 break
+
+
+def _fresh_seed() -> int:
+    """A Philox key from torch's CPU generator (so ``torch.manual_seed`` pins the Gumbel noise)."""
+    return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
 
 
 def intermediate_hip(layer: nn.Module, x: torch.Tensor) -> torch.Tensor:

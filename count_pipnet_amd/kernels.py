@@ -846,20 +846,25 @@ def count_gumbel(logits_nhwc: Tensor, tau: float, exp_noise_nchw: Optional[Tenso
         _chk(exp_noise_nchw, "exp noise")
         if tuple(exp_noise_nchw.shape) != (b, p, h, w):
             raise RuntimeError(f"exp noise shape {tuple(exp_noise_nchw.shape)} != {(b, p, h, w)}")
-    if out is None:
-        proto = torch.empty_like(logits_nhwc)
-        hist = torch.empty((b, p), device=logits_nhwc.device, dtype=torch.int32)
-    else:
-        proto, hist = out
-        if tuple(proto.shape) != (b, h, w, p) or tuple(hist.shape) != (b, p) or hist.dtype != torch.int32:
-            raise RuntimeError(f"count_gumbel: out {tuple(proto.shape)}, {tuple(hist.shape)} {hist.dtype} do not "
-                               f"match {(b, h, w, p)}, {(b, p)} int32")
-        _chk(proto, "proto out")
-        if not (hist.is_cuda and hist.is_contiguous()):
-            raise RuntimeError("count_gumbel: hist out must be a contiguous device tensor")
+    proto, hist = _gumbel_out(out, logits_nhwc)
     _lib.call("pipnet_count_gumbel_f32", logits_nhwc.data_ptr(), b, h * w, p, float(tau), _ptr(exp_noise_nchw),
               int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), proto.data_ptr(), hist.data_ptr(),
               _stream(logits_nhwc))
+    return proto, hist
+
+
+def _gumbel_out(out, logits_nhwc: Tensor) -> Tuple[Tensor, Tensor]:
+    """Caller-provided (proto [B,h,w,P] float32, hist [B,P] int32) contiguous outputs, or new ones."""
+    b, h, w, p = logits_nhwc.shape
+    if out is None:
+        return torch.empty_like(logits_nhwc), torch.empty((b, p), device=logits_nhwc.device, dtype=torch.int32)
+    proto, hist = out
+    if tuple(proto.shape) != (b, h, w, p) or tuple(hist.shape) != (b, p) or hist.dtype != torch.int32:
+        raise RuntimeError(f"count_gumbel: out {tuple(proto.shape)}, {tuple(hist.shape)} {hist.dtype} do not "
+                           f"match {(b, h, w, p)}, {(b, p)} int32")
+    _chk(proto, "proto out")
+    if not (hist.is_cuda and hist.is_contiguous()):
+        raise RuntimeError("count_gumbel: hist out must be a contiguous device tensor")
     return proto, hist
 
 
@@ -991,15 +996,14 @@ def philox_exp1(seed: int, offset: int, n: int, device, log_e: bool = False) -> 
     return out
 
 
-def count_gumbel_devseed(logits_nhwc: Tensor, tau: float, seed_state: Tensor) -> Tuple[Tensor, Tensor]:
+def count_gumbel_devseed(logits_nhwc: Tensor, tau: float, seed_state: Tensor, out=None) -> Tuple[Tensor, Tensor]:
     """count_gumbel with the Philox key in device memory (seed_state: int64[2] on the device),
-    advanced on the stream per call -- the form a captured HIP graph replays."""
+    advanced on the stream per call -- the form a captured HIP graph replays.  ``out`` as there."""
     _chk(logits_nhwc, "prototype logits")
     if not (seed_state.is_cuda and seed_state.dtype == torch.int64 and seed_state.numel() == 2):
         raise RuntimeError("count_gumbel_devseed: seed_state must be a 2-element int64 device tensor")
     b, h, w, p = logits_nhwc.shape
-    proto = torch.empty_like(logits_nhwc)
-    hist = torch.empty((b, p), device=logits_nhwc.device, dtype=torch.int32)
+    proto, hist = _gumbel_out(out, logits_nhwc)
     _lib.call("pipnet_count_gumbel_devseed_f32", logits_nhwc.data_ptr(), b, h * w, p, float(tau),
               seed_state.data_ptr(), proto.data_ptr(), hist.data_ptr(), _stream(logits_nhwc))
     return proto, hist

@@ -23,9 +23,10 @@ from torch import Tensor
 from . import _lib
 from . import kernels as K
 from .backend import cross_stream_forward, use_hip
-from .convnext_features import as_nhwc, convnext_tiny_13_features, convnext_tiny_26_features, nhwc_as_nchw
-from .resnet_features import (resnet18_features, resnet34_features, resnet50_features, resnet50_features_inat,
-                              resnet101_features, resnet152_features)
+from .convnext_features import (ConvNeXt, as_nhwc, convnext_tiny_13_features, convnext_tiny_26_features,
+                                nhwc_as_nchw)
+from .resnet_features import (ResNet_features, resnet18_features, resnet34_features, resnet50_features,
+                              resnet50_features_inat, resnet101_features, resnet152_features)
 
 PRESENCE_THRESHOLD = 0.1   # pipnet.py:36
 # The head as ONE launch (softmax_pool_linear: the classifier GEMV in each image's last workgroup)
@@ -62,24 +63,32 @@ class PIPNet(nn.Module):
 
     # -- HIP inference path ---------------------------------------------------------------
     def _forward_hip(self, xs: Tensor, inference: bool):
+        """Backbone -> add-on logits -> head per sub-batch (``sub_batch_logits`` / ``run_heads``; one
+        sub-batch on the current stream unless ``stream_split`` says otherwise).  The head writes
+        straight into batch slices of the full outputs (no concatenation copy)."""
         K.require_device(xs, "input images")
         if not (isinstance(self._pool, nn.Sequential) and isinstance(self._pool[0], nn.AdaptiveMaxPool2d)):
             raise RuntimeError("PIPNet HIP path expects _pool = Sequential(AdaptiveMaxPool2d(1), Flatten())")
-        if stream_split(self, xs) > 1:
-            with cross_stream_forward():
-                return self._forward_hip_split(xs, inference, stream_split(self, xs))
-        logits = self._hip_logits(xs)
-        proto, pooled, clamped, out = self._hip_head(logits, inference)
+        streams, logits = sub_batch_logits(self, xs, stream_split(self, xs))
+        dev = xs.device
+        b = xs.shape[0]
+        _, h, w, pn = logits[0].shape
+        k = self._classification.weight.shape[0]
+        outs = (torch.empty((b, h, w, pn), device=dev, dtype=torch.float32),      # proto
+                torch.empty((b, pn), device=dev, dtype=torch.float32),            # pooled
+                torch.empty((b, pn), device=dev, dtype=torch.float32),            # clamped
+                torch.empty((b, k), device=dev, dtype=torch.float32))             # out
+        run_heads(streams, logits, lambda lg, i0, i1: self._hip_head(lg, inference, out=rows(outs, i0, i1)))
+        proto, pooled, clamped, out = outs
         return nhwc_as_nchw(proto), (clamped if inference else pooled), out
 
     def _hip_logits(self, xs: Tensor) -> Tensor:
-        feats = as_nhwc(self._net(xs))                     # [B,h,w,C] NHWC
-        return add_on_logits_hip(self._add_on, feats)      # [B,h,w,P]
+        return sub_batch_logits(self, xs, 1)[1][0]         # [B,h,w,P] NHWC
 
     def _hip_head(self, logits: Tensor, inference: bool, out=None):
         """softmax + max-pool (pipnet_softmax_pool_*), then threshold + NonNegLinear
         (pipnet_nonneg_linear_f32) -- or the same as one launch (FUSED_HEAD); ``out`` = (proto,
-        pooled, clamped, logits) tensors to write into (batch slices of the split forward)."""
+        pooled, clamped, logits) tensors to write into (batch slices of the full outputs)."""
         cls = self._classification
         thresh = PRESENCE_THRESHOLD if inference else None
         if FUSED_HEAD:
@@ -88,60 +97,6 @@ class PIPNet(nn.Module):
         proto, pooled = pool(logits, 0, out=None if out is None else out[:2])
         clamped, res = K.nonneg_linear(pooled, cls.weight, cls.bias, thresh, out=None if out is None else out[2:])
         return proto, pooled, clamped, res
-
-    def _forward_hip_split(self, xs: Tensor, inference: bool, n: int):
-        """The batch as n concurrent sub-batches on n HIP streams: one sub-batch's
-        bandwidth-bound kernels (depthwise conv + LayerNorm, LayerNorm, head) co-run on the CUs
-        with another's MFMA-bound GEMMs.  Every kernel's result per image is independent of
-        the batch it runs in (fixed K order, batch-invariant tile choice), so the outputs are
-        bit-identical to the one-stream forward; the head writes straight into batch slices of
-        the full outputs (no concatenation copy)."""
-        dev = xs.device
-        main, streams, logits = self._split_logits(xs, n)
-        b = xs.shape[0]
-        _, h, w, pn = logits[0].shape
-        k = self._classification.weight.shape[0]
-        proto = torch.empty((b, h, w, pn), device=dev, dtype=torch.float32)
-        pooled = torch.empty((b, pn), device=dev, dtype=torch.float32)
-        clamped = torch.empty((b, pn), device=dev, dtype=torch.float32)
-        out = torch.empty((b, k), device=dev, dtype=torch.float32)
-        i0 = 0
-        for s, lg in zip(streams, logits):
-            i1 = i0 + lg.shape[0]
-            s.wait_stream(main)                            # outputs allocated on main before any write
-            with torch.cuda.stream(s):
-                self._hip_head(lg, inference, out=(proto[i0:i1], pooled[i0:i1], clamped[i0:i1], out[i0:i1]))
-            i0 = i1
-        for s in streams:
-            main.wait_stream(s)
-        return nhwc_as_nchw(proto), (clamped if inference else pooled), out
-
-    def _split_logits(self, xs: Tensor, n: int):
-        """The split forward up to the prototype logits: (main stream, the n side streams, each
-        sub-batch's NHWC logits, enqueued on its stream).  The caller runs its head per stream and
-        joins the streams back into main."""
-        dev = xs.device
-        main = torch.cuda.current_stream(dev)
-        streams = _side_streams(dev, n)
-        parts = xs.chunk(n)
-        for s in streams:
-            s.wait_stream(main)
-        net = self._net
-        if INTERLEAVE and hasattr(net, "hip_steps") and use_hip(net):
-            # enqueue the sub-batch forwards block by block, round robin, so every stream has
-            # work from the start (enqueued one after the other, the second stream trailed the
-            # first by the host's enqueue time of a whole backbone)
-            feats = interleaved_features(net, parts, streams)
-            logits = []
-            for s, f in zip(streams, feats):
-                with torch.cuda.stream(s):
-                    logits.append(add_on_logits_hip(self._add_on, f))
-        else:
-            logits = []
-            for s, p in zip(streams, parts):
-                with torch.cuda.stream(s):
-                    logits.append(self._hip_logits(p))
-        return main, streams, logits
 
 
 # Concurrent sub-batches: batches of at least STREAM_SPLIT_MIN_BATCH images run as n
@@ -157,6 +112,69 @@ STREAM_SPLIT_MIN_BATCH = 32
 # than one whole backbone after the other.
 INTERLEAVE = True
 _SIDE_STREAMS = {}
+
+
+def sub_batch_logits(model: nn.Module, xs: Tensor, n: int, activation=nn.Softmax):
+    """The HIP forward of ``model`` (``_net``, ``_add_on``) up to the prototype logits, as n
+    sub-batches: (streams, each sub-batch's NHWC logits).  n == 1 is the plain forward on the
+    current stream (streams None).  n > 1 runs ``xs.chunk(n)`` on side streams (there may be fewer
+    parts than streams), each part enqueued on its own stream: one sub-batch's bandwidth-bound
+    kernels (depthwise conv + LayerNorm, LayerNorm, head) co-run on the CUs with another's
+    MFMA-bound GEMMs.  Every kernel's result per image is independent of the batch it runs in
+    (fixed K order, batch-invariant tile choice), so the bits do not depend on n.  ``run_heads``
+    runs the caller's head per part and joins the streams."""
+    net = model._net
+    if n == 1:
+        return None, [add_on_logits_hip(model._add_on, as_nhwc(net(xs)), activation)]
+    main = torch.cuda.current_stream(xs.device)
+    streams = _side_streams(xs.device, n)
+    parts = xs.chunk(n)
+    with cross_stream_forward():
+        for s in streams:
+            s.wait_stream(main)
+        feats = None
+        if INTERLEAVE and hasattr(net, "hip_steps") and use_hip(net):
+            # enqueue the sub-batch forwards block by block, round robin, so every stream has
+            # work from the start (enqueued one after the other, the second stream trailed the
+            # first by the host's enqueue time of a whole backbone)
+            feats = interleaved_features(net, parts, streams)
+        logits = []
+        for i, (s, p) in enumerate(zip(streams, parts)):
+            with torch.cuda.stream(s):
+                f = as_nhwc(net(p)) if feats is None else feats[i]
+                logits.append(add_on_logits_hip(model._add_on, f, activation))
+    return streams, logits
+
+
+def run_heads(streams, logits, head) -> None:
+    """``head(logits_i, i0, i1)`` for every part of ``sub_batch_logits`` (images [i0, i1) of the
+    batch) on the part's stream, then the side streams joined back into the current one.  The
+    caller allocates the full outputs on the current stream before this and the head writes
+    ``rows(outputs, i0, i1)``; with one part (streams None) it is a plain call."""
+    if streams is None:
+        head(logits[0], 0, logits[0].shape[0])
+        return
+    main = torch.cuda.current_stream(logits[0].device)
+    with cross_stream_forward():
+        i0 = 0
+        for s, lg in zip(streams, logits):
+            i1 = i0 + lg.shape[0]
+            s.wait_stream(main)                            # outputs allocated on main before any write
+            with torch.cuda.stream(s):
+                head(lg, i0, i1)
+            i0 = i1
+        for s in streams:
+            main.wait_stream(s)
+
+
+def rows(ts, i0: int, i1: int):
+    """Rows [i0, i1) of each tensor; the tensors themselves where that is all their rows."""
+    return ts if i1 - i0 == ts[0].shape[0] else tuple(t[i0:i1] for t in ts)
+
+
+def add_on_activation(add_on: nn.Module) -> nn.Module:
+    """The activation module that ends ``_add_on``."""
+    return add_on[-1] if isinstance(add_on, nn.Sequential) else add_on
 
 
 def interleaved_features(net, parts, streams):
@@ -194,8 +212,6 @@ def set_stream_split(net: nn.Module, n: int) -> nn.Module:
 def stream_split(model: nn.Module, xs: Tensor) -> int:
     n = getattr(model, "_hip_stream_split", None)
     if n is None:
-        from .convnext_features import ConvNeXt
-        from .resnet_features import ResNet_features
         net = getattr(model, "_net", None)
         full_convnext = isinstance(net, ConvNeXt) and not hasattr(model, "_max_count")
         n = 2 if isinstance(net, ResNet_features) or full_convnext else 1
@@ -296,8 +312,7 @@ def set_hip_dtype(model: nn.Module, dtype) -> nn.Module:
       * "bf16x3": ConvNeXt backbones -- fp32 activations, the CNBlock Linears and downsample
         convs as split-bf16 GEMMs (x = hi + lo, three bf16 products, fp32 accumulation;
         ~1e-5 relative per product, include/pipnet_amd.h pipnet_conv2d_nhwc_s3)."""
-    from .convnext_features import ConvNeXt, MidLayerConvNeXt
-    from .resnet_features import ResNet_features
+    from .convnext_features import MidLayerConvNeXt
     if dtype in ("bf16x3", "split_bf16"):
         found = False
         for m in model.modules():

@@ -147,7 +147,7 @@ def resnet_features_hip(model, x: Tensor, cache: Dict) -> Tensor:
 def resnet_features_hip_steps(model, x: Tensor, cache: Dict):
     """Generator form of resnet_features_hip: yields after the stem and after every block
     (their launches enqueued), returns the NHWC features -- concurrent sub-batch forwards
-    enqueue block by block (pipnet._forward_hip_split)."""
+    enqueue block by block (pipnet.sub_batch_logits)."""
     K.require_device(x, "network input")
     x = x.contiguous()
     if x.shape[1] != 3:

@@ -23,9 +23,8 @@ import torch
 from torch import Tensor
 
 from . import kernels as K
-from .backend import cross_stream_forward
 from .convnext_features import as_nhwc
-from .pipnet import PRESENCE_THRESHOLD, stream_split
+from .pipnet import PRESENCE_THRESHOLD, run_heads, stream_split, sub_batch_logits
 
 PATCH_SIZE = 32
 COUNT_MIN_SCORE = 0.01          # vis_pipnet.py:703: counts below it are not candidates
@@ -138,22 +137,9 @@ def _pipnet_batch(net, xs: Tensor, small_map: Optional[bool]):
         K.nonneg_linear(pooled[i0:i1], cls.weight, cls.bias, PRESENCE_THRESHOLD, out=(clamped[i0:i1], out[i0:i1]))
 
     n = stream_split(net, xs) if small_map is False else 1
-    if n <= 1:
-        with K.per_image_gemm_plan(b):
-            logits = net._hip_logits(xs)
-        head(logits, 0, b)
-        return clamped, loc, out, tuple(logits.shape[1:3])
-    with cross_stream_forward():                # the plain forward's concurrent sub-batches
-        main, streams, logits = net._split_logits(xs, n)
-        i0 = 0
-        for s, lg in zip(streams, logits):
-            i1 = i0 + lg.shape[0]
-            s.wait_stream(main)                 # outputs allocated on main before any write
-            with torch.cuda.stream(s):
-                head(lg, i0, i1)
-            i0 = i1
-        for s in streams:
-            main.wait_stream(s)
+    with K.per_image_gemm_plan(b if n == 1 else 1):    # n > 1: the plain forward's concurrent sub-batches
+        streams, logits = sub_batch_logits(net, xs, n)
+    run_heads(streams, logits, head)
     return clamped, loc, out, tuple(logits[0].shape[1:3])
 
 

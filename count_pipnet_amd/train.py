@@ -226,14 +226,15 @@ def _count_train_forward(m: nn.Module, xs: Tensor, sd_keep: Dict[int, Tensor], j
     (``feats``, ``suffix``) together with the head's temperature (``tau``)."""
     from . import _lib
     from .count_pipnet_utils import BilinearIntermediate, GumbelSoftmax
-    from .pipnet import add_on_logits_hip
+    from .count_pipnet import _fresh_seed
+    from .pipnet import add_on_activation, add_on_logits_hip
     saved = {}
     if j is None:
         feats = _backbone_train_forward(m, xs, sd_keep)
     else:
         feats, saved["suffix"] = _backbone_forward_saving(m, xs, j, sd_keep)
         saved["feats"] = feats
-    act = list(m._add_on)[-1] if isinstance(m._add_on, nn.Sequential) else m._add_on
+    act = add_on_activation(m._add_on)
     if isinstance(act, GumbelSoftmax):
         logits = add_on_logits_hip(m._add_on, feats, activation=GumbelSoftmax)
         noise = act.exp_noise
@@ -241,8 +242,7 @@ def _count_train_forward(m: nn.Module, xs: Tensor, sd_keep: Dict[int, Tensor], j
             proto, sums = K.count_gumbel_soft(logits, act.tau, noise.to(device=logits.device,
                                                                         dtype=torch.float32).contiguous(), 0)
         else:
-            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())   # fresh noise per call
-            proto, sums = K.count_gumbel_soft(logits, act.tau, None, seed)
+            proto, sums = K.count_gumbel_soft(logits, act.tau, None, _fresh_seed())   # fresh noise per call
         saved["tau"] = float(act.tau)
     else:
         logits = add_on_logits_hip(m._add_on, feats, activation=nn.Softmax)

@@ -151,3 +151,75 @@ def test_count_stream_split_bit_identical(gpu, noise):
     for n in (2, 3):
         for a, r in zip(outs[n], outs[1]):
             assert torch.equal(a, r)
+
+
+def _small_split_outputs(monkeypatch, gpu, name, batch, n, noise=None, **case):
+    """Outputs of a ``batch``-image forward of fixture ``name`` (``case`` overrides its settings)
+    with n streams requested and with one, the split threshold lowered to 2 images."""
+    from count_pipnet_amd import pipnet
+    from count_pipnet_amd.synthetic import synth_exponential, synth_images
+    monkeypatch.setattr(pipnet, "STREAM_SPLIT_MIN_BATCH", 2)
+    meta, _ = load_golden(name)
+    meta["case"].update(case)
+    net = build_model(meta).to(gpu)
+    xs = synth_images(batch, 64, seed=17).to(gpu)
+    if noise is not None:
+        shape = (batch, net._num_prototypes, 8, 8)
+        list(net._add_on)[-1].exp_noise = synth_exponential(shape, seed=7).to(gpu) if noise == "injected" else None
+    outs = {}
+    with torch.no_grad():
+        for k in (n, 1):
+            pipnet.set_stream_split(net, k)
+            assert pipnet.stream_split(net, xs) == k
+            torch.manual_seed(4321)                      # same Philox key for both
+            outs[k] = [t.clone() for t in net(xs, inference=True)]
+    torch.cuda.synchronize()
+    return outs[n], outs[1]
+
+
+@pytest.mark.parametrize("batch,n", [(5, 2), (4, 3)])
+@pytest.mark.parametrize("name,noise", [("pipnet_mid_addon", None), ("c1_count_identity", "injected"),
+                                        ("c1_count_identity", "philox")])
+def test_stream_split_uneven_and_idle_streams(gpu, monkeypatch, name, noise, batch, n):
+    """5 images on 2 streams are parts of 3 and 2; 4 images on 3 streams are two parts of 2 and
+    the third stream stays idle (it is still joined).  Both equal the one-stream forward."""
+    assert [len(p) for p in torch.empty(batch).chunk(n)] == ([3, 2] if batch == 5 else [2, 2])
+    split, one = _small_split_outputs(monkeypatch, gpu, name, batch, n, noise)
+    for a, b in zip(split, one):
+        assert torch.equal(a, b)
+
+
+def test_count_split_requested_under_capture(gpu, monkeypatch):
+    """A CountPIPNet with a split requested captures on one stream with the device-seed Gumbel
+    head: replays draw fresh noise and are hard one-hot maps."""
+    from count_pipnet_amd import count_pipnet, pipnet
+    from count_pipnet_amd.graph import GraphedForward
+    from count_pipnet_amd.synthetic import synth_images
+    monkeypatch.setattr(pipnet, "STREAM_SPLIT_MIN_BATCH", 2)
+    net, _, _ = _net("c1_count_identity", gpu)
+    xs = synth_images(6, 64, seed=19).to(gpu)
+    list(net._add_on)[-1].exp_noise = None
+    pipnet.set_stream_split(net, 2)
+    assert pipnet.stream_split(net, xs) == 2
+    parts, real = [], count_pipnet.sub_batch_logits
+    monkeypatch.setattr(count_pipnet, "sub_batch_logits",
+                        lambda model, x, k, *a: parts.append(k) or real(model, x, k, *a))
+    g = GraphedForward(net)
+    p1 = g(xs)[0].clone()
+    assert parts == [2, 2, 1]                            # two eager warm-up forwards, then the capture
+    p2 = g(xs)[0].clone()
+    torch.cuda.synchronize()
+    assert not torch.equal(p1, p2)                       # new Philox key per replay
+    for p in (p1, p2):                                   # still hard one-hot maps
+        s = p.sum(dim=1)
+        assert torch.allclose(s, torch.ones_like(s))
+        assert torch.equal((p > 0).sum(dim=1), torch.ones_like(s, dtype=torch.int64))
+
+
+def test_count_split_requested_prototypes_not_multiple_of_4(gpu, monkeypatch):
+    """P % 4 != 0 (18 prototypes, softmax head: the Gumbel kernels need P % 4 == 0): a requested
+    split runs on one stream and equals the forward with none requested."""
+    split, one = _small_split_outputs(monkeypatch, gpu, "c1_count_identity", 5, 2,
+                                      num_features=18, activation="softmax")
+    for a, b in zip(split, one):
+        assert torch.equal(a, b)
