@@ -67,6 +67,7 @@ SIGNATURES = {
     "pipnet_softmax_pool_argmax_f32": [P, I32, I32, I32, I32, P, P, P, P, P],
     "pipnet_map_argmax_f32": [P, I32, I32, I32, I32, P, P, P],
     "pipnet_topk_update": [P, P, I32, I32, I64, P, I32, I32, F32, P, I32, I32, P, P, P, P, P, P],
+    "pipnet_local_explain_f32": [P, P, P, P, I64, I32, I32, I32, I32, I32, F64, P, P, P, P, P, P, P, P, P],
     "pipnet_softmax_pool_linear_part_floats": [I32, I32, I32],
     "pipnet_softmax_pool_linear_f32": [P, I32, I32, I32, P, P, P, P, I32, I32, F32, P, P, P, P, P],
     "pipnet_softmax_pool_linear_bf16": [P, I32, I32, I32, P, P, P, P, I32, I32, F32, P, P, P, P, P],

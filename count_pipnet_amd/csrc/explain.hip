@@ -5,6 +5,8 @@
 //   * map_argmax    the same location rule on a stored fp32 NHWC map (CountPIPNet's 0/1 Gumbel
 //                   map, the bf16 head's fp32 proto map)
 //   * topk_update   streaming per-(group, prototype) top-k over the dataset + abstain count
+//   * local_explain per image: the top classes and, for each, the prototypes that contribute to it
+//                   (util/visualize_prediction.py:63-75, :139-154)
 // Location rule = the reference's two-step max (vis_pipnet.py:235-238):
 //   max_h, h_idx = torch.max(map, dim=0); max_w, w_idx = torch.max(max_h, dim=0)
 // torch.max returns the first index among equal maxima, so of all pixels holding the map's
@@ -325,6 +327,166 @@ extern "C" int pipnet_topk_update(const float* score, const int32_t* loc, int B,
   a.min_score = min_score;
   const int blocks = (G * P + TOPK_THREADS - 1) / TOPK_THREADS + (out ? (B + TOPK_ROWS - 1) / TOPK_ROWS : 0);
   hipLaunchKernelGGL(topk_update_kernel, dim3(blocks), dim3(TOPK_THREADS), 0, (hipStream_t)stream, a);
+  PIPNET_CHECK_LAUNCH();
+  return PIPNET_OK;
+}
+
+// ---- local explanations (util/visualize_prediction.py:63-75, :139-154) --------------------------
+// Per image: classes by logit descending, prototypes by pooled score descending (both with the
+// lower index first among equals: a stable descending sort), and for each of the C best classes
+// the prototypes p with |pooled[p] * W[c, p]| > min_abs, in prototype order.
+namespace {
+
+constexpr int LX_THREADS = 256;
+constexpr int LX_MAX = 2048;        // prototypes / classes per image: the head's largest nj_bucket
+
+// float -> uint32 whose unsigned order is the float order (-0 made +0 first: equal values must
+// share their bits, the index half of the key breaks the tie); order_value is the inverse.
+PIPNET_DEV uint32_t order_bits(float v) {
+  if (v == 0.f) v = 0.f;
+  const uint32_t u = __float_as_uint(v);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+PIPNET_DEV float order_value(uint32_t o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o); }
+
+// (value, index) as one key: descending key order = value descending, then index ascending.  No
+// real key is 0 (that needs index 0xFFFFFFFF), so 0 pads a sort to a power of two at its end.
+PIPNET_DEV unsigned long long order_key(float v, int index) {
+  return ((unsigned long long)order_bits(v) << 32) | (unsigned long long)(~(uint32_t)index);
+}
+PIPNET_DEV int key_index(unsigned long long k) { return (int)(~(uint32_t)k); }
+
+// Descending bitonic sort of key[0, n2) in LDS by the whole workgroup, n2 a power of two.  Keys
+// are distinct (apart from the zero pads), so the result is the one total order whatever the
+// values: NaN bit patterns sort somewhere and nothing depends on a float comparison.
+PIPNET_DEV void sort_desc(unsigned long long* key, int n2) {
+  for (int k = 2; k <= n2; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = threadIdx.x; i < n2; i += LX_THREADS) {
+        const int l = i ^ j;
+        if (l > i) {
+          const unsigned long long a = key[i], b = key[l];
+          if ((i & k) == 0 ? a < b : a > b) {
+            key[i] = b;
+            key[l] = a;
+          }
+        }
+      }
+      __syncthreads();
+    }
+}
+
+PIPNET_DEV int next_pow2(int n) {
+  int p = 1;
+  while (p < n) p <<= 1;
+  return p;
+}
+
+// One workgroup per image.  (1) the prototypes with a non-zero score (a zero score makes a zero
+// product, never kept for min_abs >= 0) are compacted into LDS as keys -- wave ballot + prefix
+// over the waves' counts, 256 prototypes a round -- and sorted over the next power of two of
+// their number, not of P; (2) the K class keys are sorted the same way; (3) one wave per class
+// rank walks the sorted active list 64 entries at a time: gather W[c, p], the keep test on the
+// fp64 product (exact for two fp32 factors, so the decision is the reference's Python-float one),
+// ballot, and store at slot (kept so far + lanes below) while that is < M.  Every output element
+// is written here: kept slots, then the (-1, 0, 0, 0, -1) padding.
+__global__ __launch_bounds__(LX_THREADS) void local_explain_kernel(
+    const float* __restrict__ pooled, const int32_t* __restrict__ loc, const float* __restrict__ out,
+    const float* __restrict__ W, int64_t ldw, int P, int K, int C, int M, double min_abs, int32_t* __restrict__ cls,
+    float* __restrict__ cls_logit, int32_t* __restrict__ n_out, int32_t* __restrict__ e_proto,
+    float* __restrict__ e_sim, float* __restrict__ e_w, float* __restrict__ e_simw, int32_t* __restrict__ e_loc) {
+  __shared__ unsigned long long pkey[LX_MAX];
+  __shared__ unsigned long long ckey[LX_MAX];
+  __shared__ int wave_cnt[LX_THREADS / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int64_t b = blockIdx.x;
+  const float* score = pooled + b * P;
+  const float* logit = out + b * K;
+
+  int na = 0;                                         // active prototypes so far (uniform)
+  for (int p0 = 0; p0 < P; p0 += LX_THREADS) {
+    const int p = p0 + tid;
+    const float v = p < P ? score[p] : 0.f;
+    const bool active = v != 0.f;                     // NaN is active; its product is never kept
+    const unsigned long long mask = __ballot(active);
+    if (lane == 0) wave_cnt[wv] = __popcll(mask);
+    __syncthreads();
+    int base = na, total = 0;
+#pragma unroll
+    for (int w = 0; w < LX_THREADS / 64; ++w) {
+      if (w < wv) base += wave_cnt[w];
+      total += wave_cnt[w];
+    }
+    if (active) pkey[base + __popcll(mask & ((1ull << lane) - 1ull))] = order_key(v, p);
+    na += total;
+    __syncthreads();                                  // wave_cnt is rewritten next round
+  }
+  const int na2 = next_pow2(na), k2 = next_pow2(K);
+  for (int i = na + tid; i < na2; i += LX_THREADS) pkey[i] = 0ull;
+  for (int i = tid; i < k2; i += LX_THREADS) ckey[i] = i < K ? order_key(logit[i], i) : 0ull;
+  __syncthreads();
+  sort_desc(pkey, na2);
+  sort_desc(ckey, k2);
+
+  for (int r = wv; r < C; r += LX_THREADS / 64) {
+    const int c = key_index(ckey[r]);
+    const float* wrow = W + (int64_t)c * ldw;
+    const int64_t row = b * C + r;
+    const int64_t e0 = row * M;
+    int kept = 0;
+    for (int i0 = 0; i0 < na; i0 += 64) {
+      const int i = i0 + lane;
+      bool keep = false;
+      int p = 0;
+      float s = 0.f, w = 0.f;
+      double sw = 0.0;
+      if (i < na) {
+        const unsigned long long k = pkey[i];
+        p = key_index(k);
+        s = order_value((uint32_t)(k >> 32));
+        w = wrow[p];
+        sw = (double)s * (double)w;
+        keep = fabs(sw) > min_abs;
+      }
+      const unsigned long long mask = __ballot(keep);
+      const int slot = kept + __popcll(mask & ((1ull << lane) - 1ull));
+      if (keep && slot < M) {
+        e_proto[e0 + slot] = p;
+        e_sim[e0 + slot] = s;
+        e_w[e0 + slot] = w;
+        e_simw[e0 + slot] = (float)sw;
+        e_loc[e0 + slot] = loc[b * P + p];
+      }
+      kept += __popcll(mask);
+    }
+    for (int j = (kept < M ? kept : M) + lane; j < M; j += 64) {
+      e_proto[e0 + j] = -1;
+      e_sim[e0 + j] = 0.f;
+      e_w[e0 + j] = 0.f;
+      e_simw[e0 + j] = 0.f;
+      e_loc[e0 + j] = -1;
+    }
+    if (lane == 0) {
+      cls[row] = c;
+      cls_logit[row] = logit[c];
+      n_out[row] = kept;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int pipnet_local_explain_f32(const float* pooled, const int32_t* loc, const float* out, const float* W,
+                                        int64_t ldw, int B, int P, int K, int C, int M, double min_abs, int32_t* cls,
+                                        float* cls_logit, int32_t* n, int32_t* e_proto, float* e_sim, float* e_w,
+                                        float* e_simw, int32_t* e_loc, void* stream) {
+  if (B < 0 || P < 1 || P > LX_MAX || K < 1 || K > LX_MAX || C < 1 || C > K || M < 1 || ldw < P) return PIPNET_ERR_ARG;
+  if (!(min_abs >= 0.0)) return PIPNET_ERR_ARG;      // a NaN threshold as well
+  if (!pooled || !loc || !out || !W || !cls || !cls_logit || !n || !e_proto || !e_sim || !e_w || !e_simw || !e_loc)
+    return PIPNET_ERR_ARG;
+  if (B == 0) return PIPNET_OK;
+  hipLaunchKernelGGL(local_explain_kernel, dim3(B), dim3(LX_THREADS), 0, (hipStream_t)stream, pooled, loc, out, W, ldw,
+                     P, K, C, M, min_abs, cls, cls_logit, n, e_proto, e_sim, e_w, e_simw, e_loc);
   PIPNET_CHECK_LAUNCH();
   return PIPNET_OK;
 }

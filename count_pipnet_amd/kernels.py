@@ -746,6 +746,53 @@ def topk_update(state: TopkState, score: Tensor, loc: Tensor, i0: int, group: Op
     return state
 
 
+LOCAL_EXPLAIN_MAX = 2048         # prototypes / classes per image (csrc/explain.hip LX_MAX)
+
+
+def local_explain(pooled: Tensor, loc: Tensor, out: Tensor, weight: Tensor, top_classes: int, max_entries: int,
+                  min_abs: float = 0.01):
+    """Per image the ``top_classes`` best classes and each one's contributing prototypes
+    (pipnet_local_explain_f32; util/visualize_prediction.py:63-75): pooled [B,P] scores, loc [B,P]
+    int32, out [B,K] logits, weight [K,P] (any row stride) -> (cls [B,C] int32, cls_logit [B,C],
+    n [B,C] int32, e_proto [B,C,M] int32, e_sim, e_w, e_simw [B,C,M] float32, e_loc [B,C,M] int32)
+    with C = top_classes, M = max_entries.  Classes by logit, prototypes by score, both descending
+    with the lower index first among equals; (c, p) kept iff |pooled * weight| > min_abs in fp64;
+    n is the true count, empty slots hold (-1, 0, 0, 0, -1).  One kernel, no host sync."""
+    _chk(pooled, "pooled scores")
+    _chk(out, "logits")
+    require_device(weight, "explanation weight")
+    if pooled.dim() != 2 or out.dim() != 2 or weight.dim() != 2:
+        raise RuntimeError("local_explain: pooled, out and weight must be 2-D")
+    b, p = pooled.shape
+    k = out.shape[1]
+    if tuple(loc.shape) != (b, p) or loc.dtype != torch.int32 or not loc.is_cuda or not loc.is_contiguous():
+        raise RuntimeError(f"local_explain: loc {tuple(loc.shape)} {loc.dtype} must be a contiguous int32 device "
+                           f"tensor {(b, p)}")
+    if out.shape[0] != b or tuple(weight.shape) != (k, p):
+        raise RuntimeError(f"local_explain: pooled {tuple(pooled.shape)}, out {tuple(out.shape)} and weight "
+                           f"{tuple(weight.shape)} do not match")
+    if weight.stride(1) != 1 and p > 1:
+        raise RuntimeError("local_explain: weight must have unit column stride")
+    c, m = int(top_classes), int(max_entries)
+    if not (1 <= c <= k <= LOCAL_EXPLAIN_MAX and 1 <= p <= LOCAL_EXPLAIN_MAX and m >= 1):
+        raise RuntimeError(f"local_explain: needs 1 <= top_classes ({c}) <= classes ({k}) <= {LOCAL_EXPLAIN_MAX}, "
+                           f"1 <= prototypes ({p}) <= {LOCAL_EXPLAIN_MAX} and max_entries ({m}) >= 1")
+    if not float(min_abs) >= 0.0:
+        raise RuntimeError(f"local_explain: min_abs must be >= 0, got {min_abs}")
+    dev = pooled.device
+    ldw = weight.stride(0) if k > 1 else max(weight.stride(0), p)
+    i32 = dict(device=dev, dtype=torch.int32)
+    f32 = dict(device=dev, dtype=torch.float32)
+    res = (torch.empty((b, c), **i32), torch.empty((b, c), **f32), torch.empty((b, c), **i32),
+           torch.empty((b, c, m), **i32), torch.empty((b, c, m), **f32), torch.empty((b, c, m), **f32),
+           torch.empty((b, c, m), **f32), torch.empty((b, c, m), **i32))
+    if b == 0:
+        return res
+    _lib.call("pipnet_local_explain_f32", pooled.data_ptr(), loc.data_ptr(), out.data_ptr(), weight.data_ptr(), ldw,
+              b, p, k, c, m, float(min_abs), *[t.data_ptr() for t in res], _stream(pooled))
+    return res
+
+
 def softmax_pool_linear(feat_nhwc: Tensor, w: Tensor, bias: Optional[Tensor], thresh: Optional[float],
                         out=None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """The PIP-Net head in one launch (pipnet.py:33-37): fp32 or bf16 logits [B,h,w,P] ->

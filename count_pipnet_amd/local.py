@@ -1,0 +1,145 @@
+"""Local explanations, on the device -- the per-image pass of ``util/visualize_prediction.py``.
+
+For one prediction the reference asks which prototypes were found in the image, where, and how
+much each adds to each top class (``vis_pred`` :63-88: the 3 best classes; ``vis_pred_experiments``
+:138-168: every class).  It runs at batch size 1 and does, per (class, prototype) pair, two
+``.item()`` reads and a Python multiply, and per kept pair the two-step ``torch.max`` on a map.
+``explain_predictions`` computes the same lists for a whole batch with no host synchronisation:
+
+  PIP-Net      backbone + add-on logits -> fused softmax + max-pool + arg-location (the proto map
+               is never written) -> threshold + NonNegLinear -> per-image selection kernel
+  CountPIPNet  the existing forward -> arg-location on its 0/1 map -> per-image selection kernel
+
+The selection (pipnet_local_explain_f32) ranks the classes, orders the prototypes and compacts, for
+each top class, the prototypes whose contribution passes the reference's test.  Decoding the image,
+cropping, drawing the rectangle, PNG writing and file names stay with the caller.
+"""
+from __future__ import annotations
+
+import argparse
+from dataclasses import dataclass, fields
+from typing import Optional, Tuple
+
+import torch
+from torch import Tensor
+
+from . import kernels as K
+from .convnext_features import as_nhwc
+from .topk import PATCH_SIZE, _pipnet_batch, _unwrap, img_coordinates, patch_size
+
+MIN_SIMWEIGHT = 0.01            # visualize_prediction.py:75: abs(simweight) > 0.01
+
+
+@dataclass
+class LocalExplanation:
+    """Result of ``explain_predictions``; tensors stay on the device until ``.cpu()`` is asked for.
+    C = class ranks (rank 0 = the largest logit), M = ``max_entries`` slots per (image, class) in
+    prototype order (pooled score descending, lower index first among equals).  Empty slots hold
+    -1 in every index, coordinate and rectangle field and 0 in the float fields."""
+    classes: Tensor       # [B, C] int64 class index by rank
+    logits: Tensor        # [B, C] float32 logit of each ranked class
+    count: Tensor         # [B, C] int64 kept prototypes of the class; > max_entries: the list is truncated
+    prototype: Tensor     # [B, C, M] int64
+    similarity: Tensor    # [B, C, M] float32 pooled score (count) of the kept prototype
+    weight: Tensor        # [B, C, M] float32 weight entry used
+    simweight: Tensor     # [B, C, M] float32 their product
+    h_idx: Tensor         # [B, C, M] int64 latent row of the prototype's maximum
+    w_idx: Tensor         # [B, C, M] int64 latent column
+    coords: Tensor        # [B, C, M, 4] int64 (h_min, h_max, w_min, w_max): the patch the reference crops
+    rect: Tensor          # [B, C, M, 4] int64 (x0, y0, x1, y1): the rectangle the reference draws (:87)
+    proto_shape: Tuple[int, int, int, int]   # (1, P, H, W) handed to img_coordinates
+
+    def cpu(self) -> "LocalExplanation":
+        return LocalExplanation(**{f.name: (getattr(self, f.name).cpu() if torch.is_tensor(getattr(self, f.name))
+                                            else getattr(self, f.name)) for f in fields(self)})
+
+
+def count_importance_matrix(net) -> Tensor:
+    """[K, P] with column p = ``net.get_prototype_importance_per_class(p)``: what one unit of
+    prototype p's classifier inputs adds to each class.  ``vis_pred`` indexes
+    ``_classification.weight[c, p]``, which means that only while the classifier's input width is
+    P; for the identity intermediate layer the two are equal."""
+    return torch.stack([net.get_prototype_importance_per_class(p) for p in range(net._num_prototypes)], dim=1)
+
+
+def _map_is_small(net, xs: Tensor) -> Optional[bool]:
+    """Whether the latent map of this input size has at most K.SPLITK_MAX_M pixels; None until a
+    first call has seen it (``_note_map``)."""
+    hw = net.__dict__.get("_explain_hw", {}).get(tuple(xs.shape[2:]))
+    return None if hw is None else hw[0] * hw[1] <= K.SPLITK_MAX_M
+
+
+def _note_map(net, xs: Tensor, hw) -> None:
+    net.__dict__.setdefault("_explain_hw", {})[tuple(xs.shape[2:])] = tuple(hw)     # plain attribute, not a buffer
+
+
+def explain_predictions(net, xs: Tensor, top_classes: Optional[int] = 3, *, image_size: int,
+                        min_simweight: float = MIN_SIMWEIGHT, max_entries: int = 64,
+                        weight: Optional[Tensor] = None) -> LocalExplanation:
+    """For every image of the batch ``xs`` the ``top_classes`` best classes (None: all, as
+    ``vis_pred_experiments``; 3: ``vis_pred``) and, for each, the prototypes p with
+    ``abs(pooled[p] * weight[c, p]) > min_simweight`` in the reference's order, with their scores,
+    weights, products, latent locations, image patches and rectangles -- the lists of
+    visualize_prediction.py:63-88 / :138-168 at any batch size.
+
+    ``net``: a PIPNet / CountPIPNet on a ROCm device, bare, under a ``.module`` wrapper, or in a
+    world-size-1 ShardedInference; it is put in eval mode, as the reference does.  Every image gets
+    the bits of its own batch-1 forward, so the result does not depend on the batching.  Ties are
+    decided by the lower index (classes and prototypes alike) and the keep test is evaluated on the
+    fp64 product, as the reference's Python floats are.  ``weight`` [K, P] replaces the default:
+    ``_classification.weight`` for PIP-Net, the per-class prototype importance for CountPIPNet
+    (``count_importance_matrix``).  ``count`` holds the true number of kept prototypes; only the
+    first ``max_entries`` are stored.  Nothing in the call waits for the device."""
+    net = _unwrap(net)
+    net.eval()
+    count = hasattr(net, "_max_count")
+    pn = net._num_prototypes
+    kc = net._classification.weight.shape[0]
+    c = kc if top_classes is None else int(top_classes)
+    if not 1 <= c <= kc:
+        raise ValueError(f"explain_predictions: top_classes must be in 1..{kc} (or None), got {top_classes}")
+    if max_entries < 1:
+        raise ValueError(f"explain_predictions: max_entries must be at least 1, got {max_entries}")
+    if not min_simweight >= 0:
+        raise ValueError(f"explain_predictions: min_simweight must be >= 0, got {min_simweight}")
+    K.require_device(xs, "input images")
+    dev = xs.device
+    with torch.no_grad():
+        if weight is not None:
+            if tuple(weight.shape) != (kc, pn):
+                raise ValueError(f"explain_predictions: weight {tuple(weight.shape)} must be "
+                                 f"[classes, prototypes] = {(kc, pn)}")
+            w = weight.detach().to(device=dev, dtype=torch.float32)
+            if w.stride(1) != 1:
+                w = w.contiguous()
+        elif count:
+            w = count_importance_matrix(net).to(device=dev, dtype=torch.float32)
+        else:
+            w = net._classification.weight.detach()
+        small = _map_is_small(net, xs)
+        if count:
+            # small maps: per-image GEMM plan, as in prototype_topk (a Gumbel near-tie must not flip
+            # with the batch size)
+            with K.per_image_gemm_plan(xs.shape[0] if small is not False else 1):
+                proto, clamped, out = net(xs, inference=True)
+            _, loc = K.map_argmax(as_nhwc(proto))
+            hw = tuple(proto.shape[2:])
+        else:
+            clamped, loc, out, hw = _pipnet_batch(net, xs, small)
+        _note_map(net, xs, hw)
+        cls, cls_logit, n, e_proto, e_sim, e_w, e_simw, e_loc = K.local_explain(
+            clamped, loc, out, w, c, max_entries, min_simweight)
+        h, wd = hw
+        shape = (1, pn, h, wd)
+        _, skip = patch_size(argparse.Namespace(image_size=image_size, wshape=wd))
+        empty = e_proto < 0
+        l = e_loc.long().clamp(min=0)
+        h_idx, w_idx = l // wd, l % wd
+        coords = torch.stack(img_coordinates(image_size, shape, PATCH_SIZE, skip, h_idx, w_idx), dim=-1)
+        rect = torch.stack((w_idx * skip, h_idx * skip, torch.clamp(w_idx * skip + PATCH_SIZE, max=image_size),
+                            torch.clamp(h_idx * skip + PATCH_SIZE, max=image_size)), dim=-1)
+        return LocalExplanation(
+            classes=cls.long(), logits=cls_logit, count=n.long(), prototype=e_proto.long(), similarity=e_sim,
+            weight=e_w, simweight=e_simw, h_idx=h_idx.masked_fill(empty, -1), w_idx=w_idx.masked_fill(empty, -1),
+            coords=coords.masked_fill(empty.unsqueeze(-1), -1), rect=rect.masked_fill(empty.unsqueeze(-1), -1),
+            proto_shape=shape)

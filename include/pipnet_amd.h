@@ -56,7 +56,7 @@ extern "C" {
  * Round 6 only ADDS entry points (pipnet_philox_exp1_f32, pipnet_conv2d_nhwc_bf16_plan,
  * pipnet_linear_f32_plan, pipnet_cnblock_mlp_plan); no signature changed.  The prototype
  * explanation entry points (pipnet_softmax_pool_argmax_f32, pipnet_map_argmax_f32,
- * pipnet_topk_update) are additions as well. */
+ * pipnet_topk_update) are additions as well, and so is pipnet_local_explain_f32. */
 #define PIPNET_AMD_ABI_VERSION 3
 int pipnet_amd_abi_version(void);
 const char* pipnet_amd_status_string(int status);
@@ -323,6 +323,32 @@ int pipnet_map_argmax_f32(const float* map, int B, int H, int W, int P, float* v
 int pipnet_topk_update(const float* score, const int32_t* loc, int B, int P, int64_t i0, const int32_t* group,
                        int G, int use_min, float min_score, const float* out, int K, int k, float* st_score,
                        int64_t* st_index, int32_t* st_loc, int32_t* st_fill, int64_t* abstained, void* stream);
+
+/* ---- local explanations (util/visualize_prediction.py:63-75, 139-154: which prototypes were
+ * found in this image, where, and what each adds to each top class; csrc/explain.hip) ---------
+ * pipnet_local_explain_f32: per image the C best classes and, for each, its contributing
+ *   prototypes.  pooled [B,P] (clamped pooled scores or counts), loc [B,P] (h * W + w, as the
+ *   arg-location entry points write it), out [B,K] logits, W [K,P] with row stride ldw >= P.
+ *   Class order: logit descending, equal logits lower class index first (C == K: all classes,
+ *     vis_pred_experiments; C = 3: vis_pred).
+ *   Prototype order: pooled descending, equal scores lower prototype index first -- a stable
+ *     descending sort (torch.sort leaves ties open; counts tie all the time).
+ *   Keep test: pair (c, p) is kept iff |pooled[p] * W[c,p]| > min_abs, the product taken in fp64
+ *     (exact for two fp32 factors): the decision of the reference's Python-float product for
+ *     every input.  min_abs >= 0, so a score of +-0 is never kept.
+ *   Per (image, class rank r): cls [B,C] the class, cls_logit [B,C] its logit, n [B,C] the number
+ *     of kept pairs -- the true number, also when it exceeds M.  Per slot, e_* [B,C,M]: slots
+ *     0 .. min(n, M) - 1 hold the kept pairs in prototype order (prototype, pooled, weight, the
+ *     product rounded to fp32, loc), the others (-1, 0, 0, 0, -1).  Every output element is
+ *     written by the one kernel (no zeroed buffer, no memset: graph-capturable).
+ *   1 <= C <= K <= 2048, 1 <= P <= 2048, M >= 1, B >= 0; a limit violation, a negative (or NaN)
+ *   min_abs or a NULL pointer returns PIPNET_ERR_ARG before any HIP call; B == 0 is PIPNET_OK.
+ *   Non-finite scores / logits land somewhere in the order (a NaN product is never kept); they
+ *   cannot make the kernel read or write out of bounds or loop. */
+int pipnet_local_explain_f32(const float* pooled, const int32_t* loc, const float* out, const float* W, int64_t ldw,
+                             int B, int P, int K, int C, int M, double min_abs, int32_t* cls, float* cls_logit,
+                             int32_t* n, int32_t* e_proto, float* e_sim, float* e_w, float* e_simw, int32_t* e_loc,
+                             void* stream);
 
 /* Fused CNBlock MLP of the narrow ConvNeXt stages (torchvision CNBlock block.3-5 + layer_scale +
  * residual; the Linear / GELU / Linear of features.1 and features.3):
