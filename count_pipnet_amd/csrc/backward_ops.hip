@@ -723,6 +723,7 @@ extern "C" int pipnet_head_bwd_f32(const float* proto, const float* pooled, int 
   if (Bh <= 0 || HW <= 0 || P <= 0 || (P & 3) || !proto || !pooled || !argmax_ws || !dpool_ws || !d_logits)
     return PIPNET_ERR_ARG;
   if (d_out && (!W || K <= 0)) return PIPNET_ERR_ARG;
+  if (P > 2048) return PIPNET_ERR_ARG;       // widest head_bwd_kernel (PIPNET_BY_NJ4): refuse before any launch
   if (!aligned16(proto) || !aligned16(d_logits)) return PIPNET_ERR_ALIGN;
   hipStream_t s = (hipStream_t)stream;
   const int64_t NP = (int64_t)2 * Bh * P;
@@ -859,6 +860,7 @@ extern "C" int pipnet_count_head_bwd_f32(const float* proto, const float* counts
                                          const float* d_counts_in, float w_align, float w_tanh, float tanh_coeff,
                                          float inv_tau, float* dcnt_ws, float* d_logits, void* stream) {
   if (Bh <= 0 || HW <= 0 || P <= 0 || (P & 3) || !proto || !counts || !dcnt_ws || !d_logits) return PIPNET_ERR_ARG;
+  if (P > 2048) return PIPNET_ERR_ARG;       // as pipnet_head_bwd_f32: before pool_grad_kernel is enqueued
   if (!aligned16(proto) || !aligned16(d_logits)) return PIPNET_ERR_ALIGN;
   hipStream_t s = (hipStream_t)stream;
   const int64_t NP = (int64_t)2 * Bh * P;
