@@ -52,6 +52,8 @@ def gemm_kernel_name(m: int, n: int, k: int, epilogue: int, aload: int) -> str:
     """The rocprof name of the GEMM instantiation the library picks (dense, unit-stride, 16-B
     aligned torch operands -- so ``vec_epi`` holds whenever N % 4 == 0)."""
     v = gemm_variant(m, n, k, epilogue, aload)
+    if epilogue == _lib.EPI_BIAS_GELU and (v == 0 or n % 4):
+        epilogue = _lib.EPI_BIAS        # scalar epilogue: bias in the GEMM, GELU in a second pass (gelu_rows_kernel)
     if v == 1:
         return f"pipnet_gemm::gemm_f32_tn_kernel<16, 2, {epilogue}, {aload}, 2, 3, 0, false>"
     if v == 0:
@@ -141,17 +143,44 @@ def _chk(t: Tensor, what: str, contiguous: bool = True) -> None:
         raise RuntimeError(f"count_pipnet_amd: {what} must be contiguous")
 
 
+_EPI_READS_R = (_lib.EPI_RESID, _lib.EPI_MUL, _lib.EPI_BIAS_RESID_RELU, _lib.EPI_RESID_ROWSCALE, _lib.EPI_GELU_BWD)
+
+
+def _chk_gemm_operands(fn: str, a: Tensor, m: int, n: int, epilogue: int, bias: Optional[Tensor],
+                       scale: Optional[Tensor], r: Optional[Tensor], out: Optional[Tensor]) -> None:
+    """The library takes raw pointers: a wrong dtype, device, shape or stride of an epilogue operand
+    would read or write the wrong memory silently, so every one is checked before any launch."""
+    for t, what in ((bias, "bias"), (scale, "scale")):
+        if t is None:
+            continue
+        require_device(t, f"{fn} {what}")
+        if t.device != a.device or t.numel() != n or not t.is_contiguous():
+            raise RuntimeError(f"{fn}: {what} must be {n} contiguous floats on {a.device} "
+                               f"(got shape {tuple(t.shape)}, stride {t.stride()}, device {t.device})")
+    for t, what in ((r, "r"), (out, "out")):
+        if t is None:
+            continue
+        require_device(t, f"{fn} {what}")
+        if t.device != a.device or t.dim() != 2 or tuple(t.shape) != (m, n) or (n > 1 and t.stride(1) != 1) or \
+                (m > 1 and t.stride(0) < n):
+            raise RuntimeError(f"{fn}: {what} must be a ({m}, {n}) row-major view with unit column stride on "
+                               f"{a.device} (got shape {tuple(t.shape)}, stride {t.stride()}, device {t.device})")
+    if r is None and epilogue in _EPI_READS_R:
+        raise RuntimeError(f"{fn}: epilogue {epilogue} reads r, which is missing")
+
+
 def linear(a: Tensor, w: Tensor, bias: Optional[Tensor] = None, epilogue: int = _lib.EPI_NONE,
            scale: Optional[Tensor] = None, r: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
-    """out[M,N] = epi(a[M,K] @ w[N,K]^T).  a may be any 2-D row-major view with unit col stride."""
+    """out[M,N] = epi(a[M,K] @ w[N,K]^T).  a, r and out may be any 2-D row-major views with unit col stride."""
     require_device(a, "linear input")
     _chk(w, "weight")
-    if a.dim() != 2 or w.dim() != 2 or a.stride(1) != 1:
-        raise RuntimeError("linear: expects 2-D operands with unit column stride")
+    if a.dim() != 2 or w.dim() != 2 or a.stride(1) != 1 or w.device != a.device:
+        raise RuntimeError("linear: expects 2-D operands with unit column stride on one device")
     m, k = a.shape
     n = w.shape[0]
     if w.shape[1] != k:
         raise RuntimeError(f"linear: K mismatch {tuple(a.shape)} x {tuple(w.shape)}")
+    _chk_gemm_operands("linear", a, m, n, epilogue, bias, scale, r, out)
     if out is None:
         out = torch.empty((m, n), device=a.device, dtype=torch.float32)
     ldr = r.stride(0) if r is not None else 0
@@ -225,11 +254,15 @@ def linear_rowscale(a: Tensor, w: Tensor, bias: Optional[Tensor], scale: Tensor,
     require_device(a, "linear input")
     _chk(w, "weight")
     _chk(row_scale, "row scale")
+    if a.dim() != 2 or w.dim() != 2 or a.stride(1) != 1 or w.device != a.device or row_scale.device != a.device:
+        raise RuntimeError("linear_rowscale: expects 2-D operands with unit column stride on one device")
     m, k = a.shape
     n = w.shape[0]
-    if w.shape[1] != k or tuple(r.shape) != (m, n) or a.stride(1) != 1 or r.stride(1) != 1:
-        raise RuntimeError(f"linear_rowscale: shapes a {tuple(a.shape)}, w {tuple(w.shape)}, r {tuple(r.shape)}")
-    if row_scale.numel() * rows_per_scale < m:
+    if w.shape[1] != k or r is None or tuple(r.shape) != (m, n):
+        raise RuntimeError(f"linear_rowscale: shapes a {tuple(a.shape)}, w {tuple(w.shape)}, "
+                           f"r {None if r is None else tuple(r.shape)}")
+    _chk_gemm_operands("linear_rowscale", a, m, n, _lib.EPI_RESID_ROWSCALE, bias, scale, r, None)
+    if rows_per_scale <= 0 or row_scale.numel() * rows_per_scale < m:
         raise RuntimeError("linear_rowscale: row_scale does not cover every row")
     _launch(gemm_kernel_name(m, n, k, _lib.EPI_RESID_ROWSCALE, 0), 2.0 * m * n * k,
             lambda: _lib.call("pipnet_linear_rowscale_f32", a.data_ptr(), a.stride(0), w.data_ptr(), _ptr(bias),
