@@ -101,6 +101,7 @@ SIGNATURES = {
     "pipnet_cnblock_mlp_f32": [P, P, P, P, P, P, P, I64, I32, P],
     "pipnet_cnblock_mlp_hw_f32": [P, P, P, P, P, P, P, I64, I32, I32, P],
     "pipnet_bn_workspace_floats": [I32],
+    "pipnet_bn_slabs": [I64, I32],
     "pipnet_bn_stats_f32": [P, I64, I32, F32, F32, P, P, P, P, P, P],
     "pipnet_bn_apply_f32": [P, I64, I32, P, P, P, P, P, I32, P, P],
     "pipnet_bn_backward_f32": [P, P, P, I64, I32, P, P, P, P, P, P, P, P, P],

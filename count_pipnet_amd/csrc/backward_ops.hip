@@ -186,6 +186,10 @@ extern "C" int64_t pipnet_wgrad_workspace_bytes(int M, int N1, int N2) {
 namespace {
 int wgrad_launch(const float* A, int64_t lda, const float* B, int64_t ldb, int M, int N1, int N2, float* C,
                  int64_t ldc, int accumulate, float* workspace, hipStream_t s, const Conv2x2Geom* cg) {
+  // No rows: C += 0 is C.  (The workspace of M = 0 has no bytes -- pipnet_wgrad_workspace_bytes --
+  // so the one-slab workspace path below must not run; without accumulate the direct path stores
+  // the zero result straight into C.)
+  if (M == 0 && accumulate) return PIPNET_OK;
   const int splits = M > 0 ? wgrad_splits(M, N1, N2) : 1;
   const int t2n = (N2 + WB2 - 1) / WB2;
   const int tiles = ((N1 + WB1 - 1) / WB1) * t2n;
@@ -216,7 +220,8 @@ int wgrad_launch(const float* A, int64_t lda, const float* B, int64_t ldb, int M
 
 extern "C" int pipnet_wgrad_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int M, int N1, int N2,
                                 float* C, int64_t ldc, int accumulate, float* workspace, void* stream) {
-  if (M < 0 || N1 <= 0 || N2 <= 0 || !A || !B || !C) return PIPNET_ERR_ARG;
+  // M = 0 reads no row: an empty torch tensor's NULL data pointer is accepted there
+  if (M < 0 || N1 <= 0 || N2 <= 0 || (M > 0 && (!A || !B)) || !C) return PIPNET_ERR_ARG;
   if ((N1 & 3) || (N2 & 3) || (lda & 3) || (ldb & 3) || lda < N1 || ldb < N2 || ldc < N2) return PIPNET_ERR_ARG;
   if (!aligned16(A) || !aligned16(B)) return PIPNET_ERR_ALIGN;
   return wgrad_launch(A, lda, B, ldb, M, N1, N2, C, ldc, accumulate, workspace, (hipStream_t)stream, nullptr);
@@ -252,7 +257,7 @@ extern "C" int pipnet_colsum_workspace_bytes(int N) { return N > 0 ? CS_SPLITS *
 
 extern "C" int pipnet_colsum_f32(const float* A, int64_t lda, int M, int N, float* out, int accumulate,
                                  float* workspace, void* stream) {
-  if (M < 0 || N <= 0 || lda < N || !A || !out || !workspace) return PIPNET_ERR_ARG;
+  if (M < 0 || N <= 0 || lda < N || (M > 0 && !A) || !out || !workspace) return PIPNET_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   const unsigned gx = (unsigned)((N + 255) / 256);
   hipLaunchKernelGGL(colsum_partial_kernel, dim3(gx, CS_SPLITS), dim3(256), 0, s, A, lda, M, N, workspace);

@@ -330,6 +330,10 @@ bool bn_shape_ok(int64_t M, int C) {
 
 extern "C" int64_t pipnet_bn_workspace_floats(int C) { return C > 0 ? ((int64_t)BN_GMAX * 3 + 2) * C : 0; }
 
+// Host only: the row slabs pipnet_bn_stats_f32 / pipnet_bn_backward_f32 reduce (M, C) over (0 for a
+// shape they reject).
+extern "C" int pipnet_bn_slabs(int64_t M, int C) { return bn_shape_ok(M, C) ? bn_slabs(M, C) : 0; }
+
 extern "C" int pipnet_bn_stats_f32(const float* x, int64_t M, int C, float eps, float momentum, float* mean,
                                    float* invstd, float* running_mean, float* running_var, float* workspace,
                                    void* stream) {

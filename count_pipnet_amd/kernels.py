@@ -169,6 +169,46 @@ def _chk_gemm_operands(fn: str, a: Tensor, m: int, n: int, epilogue: int, bias: 
         raise RuntimeError(f"{fn}: epilogue {epilogue} reads r, which is missing")
 
 
+def _chk_rows(fn: str, t: Tensor, what: str, ndim: int) -> None:
+    """The primary operand of a training kernel: a contiguous float32 device tensor of ``ndim`` dimensions."""
+    require_device(t, f"{fn} {what}")
+    if t.dim() != ndim or not t.is_contiguous():
+        raise RuntimeError(f"{fn}: {what} must be a contiguous {ndim}-D tensor "
+                           f"(got shape {tuple(t.shape)}, stride {t.stride()})")
+
+
+def _chk_same(fn: str, ref: Tensor, **operands: Optional[Tensor]) -> None:
+    """Optional operands the library indexes exactly as ``ref``: same shape, contiguous, same device."""
+    for what, t in operands.items():
+        if t is None:
+            continue
+        require_device(t, f"{fn} {what}")
+        if t.device != ref.device or t.shape != ref.shape or not t.is_contiguous():
+            raise RuntimeError(f"{fn}: {what} must be a contiguous {tuple(ref.shape)} tensor on {ref.device} "
+                               f"(got shape {tuple(t.shape)}, stride {t.stride()}, device {t.device})")
+
+
+def _chk_vec(fn: str, ref: Tensor, n: int, at_least: bool = False, **operands: Optional[Tensor]) -> None:
+    """Optional per-channel (or per-row-group) operands: ``n`` contiguous floats (or more, ``at_least``)
+    on ``ref``'s device.  As for the GEMM epilogue operands the library only sees a pointer."""
+    for what, t in operands.items():
+        if t is None:
+            continue
+        require_device(t, f"{fn} {what}")
+        ok = t.numel() >= n if at_least else t.numel() == n
+        if t.device != ref.device or not ok or not t.is_contiguous():
+            raise RuntimeError(f"{fn}: {what} must be {'at least ' if at_least else ''}{n} contiguous floats on "
+                               f"{ref.device} (got shape {tuple(t.shape)}, stride {t.stride()}, device {t.device})")
+
+
+def _chk_row_scale(fn: str, ref: Tensor, m: int, row_scale: Optional[Tensor], rows_per_scale: int) -> None:
+    if row_scale is None:
+        return
+    if rows_per_scale <= 0:
+        raise RuntimeError(f"{fn}: rows_per_scale must be positive with a row_scale (got {rows_per_scale})")
+    _chk_vec(fn, ref, -(-m // rows_per_scale), at_least=True, row_scale=row_scale)
+
+
 def linear(a: Tensor, w: Tensor, bias: Optional[Tensor] = None, epilogue: int = _lib.EPI_NONE,
            scale: Optional[Tensor] = None, r: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
     """out[M,N] = epi(a[M,K] @ w[N,K]^T).  a, r and out may be any 2-D row-major views with unit col stride."""
@@ -1290,12 +1330,19 @@ def wgrad(a: Tensor, b: Tensor, out: Optional[Tensor] = None, accumulate: bool =
 def colsum(a: Tensor, out: Optional[Tensor] = None, accumulate: bool = False) -> Tensor:
     """out[N] (+)= a[M,N].sum(0), deterministic."""
     require_device(a, "colsum input")
+    if a.dim() != 2 or a.shape[1] < 1 or (a.shape[1] > 1 and a.stride(1) != 1) or \
+            (a.shape[0] > 1 and a.stride(0) < a.shape[1]):
+        raise RuntimeError(f"colsum: expects a 2-D row-major view with unit column stride "
+                           f"(got shape {tuple(a.shape)}, stride {a.stride()})")
     m, n = a.shape
+    _chk_vec("colsum", a, n, out=out)
     if out is None:
+        if accumulate:
+            raise RuntimeError("colsum: accumulate needs out")
         out = torch.empty(n, device=a.device, dtype=torch.float32)
     ws = torch.empty(_lib.load().pipnet_colsum_workspace_bytes(n) // 4, device=a.device, dtype=torch.float32)
-    _lib.call("pipnet_colsum_f32", a.data_ptr(), a.stride(0), m, n, out.data_ptr(), int(accumulate), ws.data_ptr(),
-              _stream(a))
+    _lib.call("pipnet_colsum_f32", a.data_ptr(), a.stride(0) if m > 1 else n, m, n, out.data_ptr(), int(accumulate),
+              ws.data_ptr(), _stream(a))
     return out
 
 
@@ -1313,9 +1360,11 @@ def gelu_fwd(h: Tensor) -> Tensor:
 def resid_scale(x: Tensor, y2: Tensor, ls: Tensor, row_scale: Optional[Tensor], rows_per_scale: int,
                 out: Optional[Tensor] = None) -> Tensor:
     """out = x + row_scale[m // rows_per_scale] * (ls * y2) on [M, C] rows."""
-    for t, what in ((x, "residual"), (y2, "branch"), (ls, "layer scale")):
-        _chk(t, what)
+    _chk_rows("resid_scale", x, "residual", 2)
     m, c = x.shape
+    _chk_same("resid_scale", x, branch=y2, out=out)
+    _chk_vec("resid_scale", x, c, layer_scale=ls)
+    _chk_row_scale("resid_scale", x, m, row_scale, rows_per_scale)
     out = torch.empty_like(x) if out is None else out
     _lib.call("pipnet_resid_scale_f32", x.data_ptr(), y2.data_ptr(), ls.data_ptr(), _ptr(row_scale), rows_per_scale,
               m, c, out.data_ptr(), _stream(x))
@@ -1325,9 +1374,11 @@ def resid_scale(x: Tensor, y2: Tensor, ls: Tensor, row_scale: Optional[Tensor], 
 def ls_backward(dy: Tensor, y2: Tensor, ls: Tensor, row_scale: Optional[Tensor], rows_per_scale: int,
                 d_ls: Tensor, d_b2: Tensor, accumulate: bool = False) -> Tensor:
     """Backward of resid_scale w.r.t. y2 (returned), ls and the Linear2 bias (into d_ls / d_b2)."""
-    _chk(dy, "dy")
-    _chk(y2, "y2")
+    _chk_rows("ls_backward", dy, "dy", 2)
     m, c = dy.shape
+    _chk_same("ls_backward", dy, y2=y2)
+    _chk_vec("ls_backward", dy, c, layer_scale=ls, d_ls=d_ls, d_b2=d_b2)
+    _chk_row_scale("ls_backward", dy, m, row_scale, rows_per_scale)
     dy2 = torch.empty_like(dy)
     _lib.call("pipnet_ls_bwd_f32", dy.data_ptr(), y2.data_ptr(), ls.data_ptr(), _ptr(row_scale), rows_per_scale, m, c,
               dy2.data_ptr(), d_ls.data_ptr(), d_b2.data_ptr(), int(accumulate), _partials(c, dy.device).data_ptr(),
@@ -1338,9 +1389,10 @@ def ls_backward(dy: Tensor, y2: Tensor, ls: Tensor, row_scale: Optional[Tensor],
 def ln_backward(z: Tensor, dt: Tensor, gamma: Tensor, d_gamma: Tensor, d_beta: Tensor, want_dz: bool = True,
                 accumulate: bool = False) -> Optional[Tensor]:
     """LayerNorm(C, eps 1e-6) backward from the pre-norm rows z [M, C]."""
-    _chk(z, "LN input")
-    _chk(dt, "LN output gradient")
+    _chk_rows("ln_backward", z, "LN input", 2)
     m, c = z.shape
+    _chk_same("ln_backward", z, dt=dt)
+    _chk_vec("ln_backward", z, c, gamma=gamma, d_gamma=d_gamma, d_beta=d_beta)
     dz = torch.empty_like(z) if want_dz else None
     _lib.call("pipnet_ln_bwd_f32", z.data_ptr(), dt.data_ptr(), gamma.data_ptr(), m, c, _ptr(dz), d_gamma.data_ptr(),
               d_beta.data_ptr(), int(accumulate), _partials(c, z.device).data_ptr(), _stream(z))
@@ -1350,8 +1402,13 @@ def ln_backward(z: Tensor, dt: Tensor, gamma: Tensor, d_gamma: Tensor, d_beta: T
 def dwconv7_plain(x_nhwc: Tensor, w_packed: Tensor, bias: Optional[Tensor], out: Optional[Tensor] = None,
                   accumulate: bool = False) -> Tensor:
     """(out +)= [bias] + depthwise 7x7 pad 3 of x (w_packed [49, C])."""
-    _chk(x_nhwc, "dwconv input")
+    _chk_rows("dwconv7_plain", x_nhwc, "input", 4)
     b, h, w, c = x_nhwc.shape
+    _chk_same("dwconv7_plain", x_nhwc, out=out)
+    _chk_vec("dwconv7_plain", x_nhwc, 49 * c, w_packed=w_packed)
+    _chk_vec("dwconv7_plain", x_nhwc, c, bias=bias)
+    if out is None and accumulate:
+        raise RuntimeError("dwconv7_plain: accumulate needs out")
     out = torch.empty_like(x_nhwc) if out is None else out
     _lib.call("pipnet_dwconv7_plain_f32", x_nhwc.data_ptr(), b, h, w, c, w_packed.data_ptr(), _ptr(bias),
               int(accumulate), out.data_ptr(), _stream(x_nhwc))
@@ -1359,7 +1416,12 @@ def dwconv7_plain(x_nhwc: Tensor, w_packed: Tensor, bias: Optional[Tensor], out:
 
 
 def dwconv7_wgrad(dz_nhwc: Tensor, x_nhwc: Tensor, dw_packed: Tensor, db: Tensor, accumulate: bool = False) -> None:
+    """(dw_packed [49, C], db [C]) (+)= the depthwise 7x7 weight / bias gradient from dz and the conv's input x."""
+    _chk_rows("dwconv7_wgrad", x_nhwc, "input", 4)
     b, h, w, c = x_nhwc.shape
+    _chk_same("dwconv7_wgrad", x_nhwc, dz=dz_nhwc)
+    _chk_vec("dwconv7_wgrad", x_nhwc, 49 * c, dw_packed=dw_packed)
+    _chk_vec("dwconv7_wgrad", x_nhwc, c, db=db)
     _lib.call("pipnet_dwconv7_wgrad_f32", dz_nhwc.data_ptr(), x_nhwc.data_ptr(), b, h, w, c, dw_packed.data_ptr(),
               db.data_ptr(), int(accumulate), _partials(c, x_nhwc.device).data_ptr(), _stream(x_nhwc))
 
@@ -1383,8 +1445,15 @@ def wgrad_conv(dy_nhwc: Tensor, x_nhwc: Tensor, kh: int, kw: int, stride: int, o
 
 def wgrad_conv2x2(dy_nhwc: Tensor, x_nhwc: Tensor, stride: int, out: Tensor, accumulate: bool = False) -> Tensor:
     """Packed [Cout, 4*Cin] weight gradient of the 2x2 downsample conv."""
+    _chk_rows("wgrad_conv2x2", x_nhwc, "conv input", 4)
+    _chk_rows("wgrad_conv2x2", dy_nhwc, "d conv output", 4)
     b, h, w, cin = x_nhwc.shape
     cout = dy_nhwc.shape[-1]
+    if stride not in (1, 2) or h < 2 or w < 2 or dy_nhwc.device != x_nhwc.device or \
+            tuple(dy_nhwc.shape) != (b, (h - 2) // stride + 1, (w - 2) // stride + 1, cout):
+        raise RuntimeError(f"wgrad_conv2x2: dY {tuple(dy_nhwc.shape)} on {dy_nhwc.device}, x {tuple(x_nhwc.shape)} "
+                           f"on {x_nhwc.device}, stride {stride}")
+    _chk_vec("wgrad_conv2x2", x_nhwc, cout * 4 * cin, out=out)
     nbytes = _lib.load().pipnet_wgrad_workspace_bytes(dy_nhwc.numel() // cout, cout, 4 * cin)
     ws = torch.empty(max(nbytes // 4, 1), device=x_nhwc.device, dtype=torch.float32)
     _lib.call("pipnet_wgrad_conv2x2_f32", dy_nhwc.data_ptr(), x_nhwc.data_ptr(), b, h, w, cin, stride, cout,
@@ -1396,8 +1465,19 @@ def head_backward(proto_nhwc: Tensor, pooled: Tensor, d_out: Optional[Tensor], w
                   w_align: float, w_tanh: float, tanh_coeff: float = 1.0) -> Tensor:
     """d loss / d logits of the PIP-Net head (softmax + max-pool) for the align / tanh /
     classifier terms of calculate_loss (pipnet/train.py:154-265)."""
-    _chk(proto_nhwc, "proto features")
+    _chk_rows("head_backward", proto_nhwc, "proto features", 4)
     n, h, ww, p = proto_nhwc.shape
+    if n % 2 or n == 0:
+        raise RuntimeError(f"head_backward: the batch holds both views, so it must be even and non-empty (got {n})")
+    _chk_vec("head_backward", proto_nhwc, n * p, pooled=pooled)
+    if d_out is not None:
+        if w is None:
+            raise RuntimeError("head_backward: d_out needs the classifier weight")
+        require_device(w, "head_backward classifier weight")
+        if w.dim() != 2 or w.shape[1] != p or w.shape[0] < 1 or not w.is_contiguous() or w.device != proto_nhwc.device:
+            raise RuntimeError(f"head_backward: the classifier weight must be a contiguous (K, {p}) tensor on "
+                               f"{proto_nhwc.device} (got shape {tuple(w.shape)}, stride {w.stride()})")
+        _chk_vec("head_backward", proto_nhwc, n * w.shape[0], d_out=d_out)
     d_logits = torch.empty_like(proto_nhwc)
     amax = torch.empty((n, p), device=proto_nhwc.device, dtype=torch.int32)
     dpool = torch.empty((n, p), device=proto_nhwc.device, dtype=torch.float32)
@@ -1418,13 +1498,15 @@ def bn_stats(x: Tensor, eps: float, momentum: float, running_mean: Optional[Tens
     """Batch mean / invstd over the rows of NHWC ``x`` (train-mode BatchNorm2d); updates the
     running statistics in place when given (momentum, unbiased variance)."""
     _chk(x, "BN input")
+    if x.dim() < 2 or x.shape[-1] < 1:
+        raise RuntimeError(f"bn_stats: expects channel-last rows [..., C] (got shape {tuple(x.shape)})")
     c = x.shape[-1]
     m = x.numel() // c
+    if (running_mean is None) != (running_var is None):
+        raise RuntimeError("bn_stats: running_mean and running_var go together")
+    _chk_vec("bn_stats", x, c, running_mean=running_mean, running_var=running_var)
     mean = torch.empty(c, device=x.device, dtype=torch.float32)
     invstd = torch.empty_like(mean)
-    for t, what in ((running_mean, "running_mean"), (running_var, "running_var")):
-        if t is not None:
-            _chk(t, what)
     _lib.call("pipnet_bn_stats_f32", x.data_ptr(), m, c, eps, momentum, mean.data_ptr(), invstd.data_ptr(),
               _ptr(running_mean), _ptr(running_var), _bn_ws(c, x.device).data_ptr(), _stream(x))
     if running_mean is not None:
@@ -1436,13 +1518,11 @@ def bn_apply(x: Tensor, mean: Tensor, invstd: Tensor, gamma: Tensor, beta: Tenso
              relu: bool = False, out: Optional[Tensor] = None) -> Tensor:
     """gamma * (x - mean) * invstd + beta [+ residual] [ReLU] on NHWC rows."""
     _chk(x, "BN input")
-    for t, what in ((gamma, "BN weight"), (beta, "BN bias")):
-        _chk(t, what)
-    if residual is not None:
-        _chk(residual, "residual")
-        if residual.shape != x.shape:
-            raise RuntimeError(f"bn_apply: residual {tuple(residual.shape)} vs {tuple(x.shape)}")
+    if x.dim() < 2 or x.shape[-1] < 1:
+        raise RuntimeError(f"bn_apply: expects channel-last rows [..., C] (got shape {tuple(x.shape)})")
     c = x.shape[-1]
+    _chk_vec("bn_apply", x, c, mean=mean, invstd=invstd, gamma=gamma, beta=beta)
+    _chk_same("bn_apply", x, residual=residual, out=out)
     y = torch.empty_like(x) if out is None else out
     _lib.call("pipnet_bn_apply_f32", x.data_ptr(), x.numel() // c, c, mean.data_ptr(), invstd.data_ptr(),
               gamma.data_ptr(), beta.data_ptr(), _ptr(residual), int(relu), y.data_ptr(), _stream(x))
@@ -1455,10 +1535,11 @@ def bn_backward(x: Tensor, dy: Tensor, mean: Tensor, invstd: Tensor, gamma: Tens
     """Train-mode BatchNorm2d backward from the pre-norm rows ``x``; ``relu_out`` (the output of
     the ReLU that follows, when there is one) masks dy.  Returns (dx, masked dy, d_gamma, d_beta)."""
     _chk(x, "BN input")
-    _chk(dy, "BN output gradient")
-    if relu_out is not None:
-        _chk(relu_out, "ReLU output")
+    if x.dim() < 2 or x.shape[-1] < 1:
+        raise RuntimeError(f"bn_backward: expects channel-last rows [..., C] (got shape {tuple(x.shape)})")
     c = x.shape[-1]
+    _chk_same("bn_backward", x, dy=dy, relu_out=relu_out)
+    _chk_vec("bn_backward", x, c, mean=mean, invstd=invstd, gamma=gamma)
     dx = torch.empty_like(x) if want_dx else None
     dm = torch.empty_like(x) if want_masked else None
     dg = torch.empty(c, device=x.device, dtype=torch.float32)

@@ -491,6 +491,8 @@ int pipnet_clamp_min_f32(float* x, int64_t n, float lo, void* stream);
  *   (fixed pixel slabs, fixed-order reduction).  N1, N2, lda, ldb % 4 == 0, A/B 16-B
  *   aligned; workspace: pipnet_wgrad_workspace_bytes(M, N1, N2) bytes (needed unless the
  *   call runs as a single slab without accumulate; pass it whenever that size is > 0).
+ *   M = 0 is the empty sum (C = 0, or C unchanged with accumulate; A, B may be NULL, the
+ *   workspace is not touched).
  * pipnet_colsum_f32: out[n] = (accumulate ? out[n] : 0) + sum_m A[m][n] (bias gradients);
  *   workspace of pipnet_colsum_workspace_bytes(N) bytes. */
 int64_t pipnet_wgrad_workspace_bytes(int M, int N1, int N2);
@@ -597,8 +599,11 @@ int pipnet_matmul2_f64acc_f32(const float* A0, const float* A1, int64_t lda, con
  *   workspace: pipnet_bn_workspace_floats(C) floats, for both calls.
  * pipnet_stride_scatter_f32: out[B][H][W][C] (+)= in[B][OH][OW][C] placed on the stride
  *   lattice (zeros elsewhere): the input gradient of a stride-s 1x1 conv, and the
- *   zero-inserted gradient a stride-s 3x3 conv's input gradient is convolved from. */
+ *   zero-inserted gradient a stride-s 3x3 conv's input gradient is convolved from.
+ * pipnet_bn_slabs: host only, the number of row slabs the two column reductions split (M, C)
+ *   over (1 .. 1024; 0 for a shape they reject). */
 int64_t pipnet_bn_workspace_floats(int C);
+int pipnet_bn_slabs(int64_t M, int C);
 int pipnet_bn_stats_f32(const float* x, int64_t M, int C, float eps, float momentum, float* mean, float* invstd,
                         float* running_mean, float* running_var, float* workspace, void* stream);
 int pipnet_bn_apply_f32(const float* x, int64_t M, int C, const float* mean, const float* invstd, const float* gamma,
