@@ -106,6 +106,11 @@ SIGNATURES = {
     "pipnet_bn_apply_f32": [P, I64, I32, P, P, P, P, P, I32, P, P],
     "pipnet_bn_backward_f32": [P, P, P, I64, I32, P, P, P, P, P, P, P, P, P],
     "pipnet_stride_scatter_f32": [P, I32, I32, I32, I32, I32, I32, I32, I32, P, P],
+    "pipnet_attr_path_images_f32": [P, P, F32, P, I32, I32, I32, P, P],
+    "pipnet_attr_head_bwd_f32": [P, P, P, I32, I32, I32, I32, F32, P, P],
+    "pipnet_attr_stem_dx_f32": [P, P, I32, I32, I32, I32, I64, P, P],
+    "pipnet_attr_path_weights_f32": [P, P, P, I32, I32, F32, P, P, P],
+    "pipnet_attr_path_reduce_f32": [P, I64, P, P, P, F32, I32, I64, P, P],
 }
 _RESTYPE_EXTRA = {"pipnet_wgrad_workspace_bytes": ctypes.c_int64, "pipnet_train_partials_floats": ctypes.c_int64,
                   "pipnet_bn_workspace_floats": ctypes.c_int64,

@@ -1565,3 +1565,124 @@ def stride_scatter(x: Tensor, h: int, w: int, stride: int, out: Optional[Tensor]
     _lib.call("pipnet_stride_scatter_f32", x.data_ptr(), b, oh, ow, c, h, w, stride, int(accumulate), out.data_ptr(),
               _stream(x))
     return out
+
+
+# ---- integrated-gradients attribution (csrc/attribution.hip) ------------------------------
+
+ATTR_METHOD = {"ig": 0, "lig": 1, "idg": 2}
+LIG_ALPHA_STAR = 0.9             # interpret_idg.py:105
+
+
+def _attr_baseline(fn: str, x: Tensor, baseline) -> Tuple[Optional[Tensor], float]:
+    """(baseline image pointer operand or None, constant baseline value)."""
+    if torch.is_tensor(baseline):
+        _chk_same(fn, x, baseline=baseline)
+        return baseline, 0.0
+    return None, float(baseline)
+
+
+def attr_path_images(x: Tensor, baseline, alpha: Tensor) -> Tensor:
+    """x [3,H,W], baseline (float or [3,H,W]), alpha [S] -> the path images baseline + alpha_i (x - baseline) as
+    [S,H,W,4] NHWC with a zero fourth channel (``nchw_to_nhwc(..., 4)``'s layout)."""
+    _chk_rows("attr_path_images", x, "image", 3)
+    if x.shape[0] != 3:
+        raise RuntimeError(f"attr_path_images: image must be [3,H,W], got {tuple(x.shape)}")
+    _chk_rows("attr_path_images", alpha, "alpha", 1)
+    if alpha.device != x.device:
+        raise RuntimeError("attr_path_images: alpha must be on the image's device")
+    bt, bv = _attr_baseline("attr_path_images", x, baseline)
+    _, h, w = x.shape
+    out = torch.empty((alpha.numel(), h, w, 4), device=x.device, dtype=torch.float32)
+    _lib.call("pipnet_attr_path_images_f32", x.data_ptr(), _ptr(bt), bv, alpha.data_ptr(), alpha.numel(), h, w,
+              out.data_ptr(), _stream(x))
+    return out
+
+
+def attr_head_backward(soft_nhwc: Tensor, u: Tensor, loc: Optional[Tensor], pool_mode: int, tau: float = 1.0) -> Tensor:
+    """d target / d logits [B,h,w,P] of the prototype head for the upstream vector u [B,P]: pool_mode 0 =
+    softmax + max-pool (loc [B,P] int32 from softmax_pool_argmax), 1 = (Gumbel-)softmax at temperature tau +
+    spatial sum.  Any P and any batch."""
+    _chk_rows("attr_head_backward", soft_nhwc, "soft map", 4)
+    b, h, w, p = soft_nhwc.shape
+    _chk_rows("attr_head_backward", u, "upstream vector", 2)
+    if tuple(u.shape) != (b, p) or u.device != soft_nhwc.device:
+        raise RuntimeError(f"attr_head_backward: u {tuple(u.shape)} vs map {tuple(soft_nhwc.shape)}")
+    if pool_mode not in (0, 1):
+        raise RuntimeError(f"attr_head_backward: pool_mode {pool_mode}")
+    if pool_mode == 0:
+        if loc is None or tuple(loc.shape) != (b, p) or loc.dtype != torch.int32 or not loc.is_contiguous() \
+                or loc.device != soft_nhwc.device:
+            raise RuntimeError("attr_head_backward: max mode needs loc [B,P] int32 contiguous on the map's device")
+    d = torch.empty_like(soft_nhwc)
+    _lib.call("pipnet_attr_head_bwd_f32", soft_nhwc.data_ptr(), u.data_ptr(), _ptr(loc) if pool_mode == 0 else None,
+              b, h * w, p, pool_mode, 1.0 / float(tau), d.data_ptr(), _stream(soft_nhwc))
+    return d
+
+
+def attr_stem_dx(dz_nhwc: Tensor, w: Tensor, h: int, wd: int, out: Optional[Tensor] = None) -> Tensor:
+    """Input gradient of Conv2d(3, O, 4, stride 4): dz [B,h/4,w/4,O] NHWC, w [O,3,4,4] -> [B,3,h,w] NCHW.
+    ``out``: [B, ld] rows (ld >= 3 h w) to write the images into (a slice of the path's gradient store)."""
+    _chk_rows("attr_stem_dx", dz_nhwc, "dz", 4)
+    b, zh, zw, o = dz_nhwc.shape
+    _chk_rows("attr_stem_dx", w, "stem weight", 4)
+    if tuple(w.shape) != (o, 3, 4, 4) or w.device != dz_nhwc.device or (zh, zw) != (h // 4, wd // 4):
+        raise RuntimeError(f"attr_stem_dx: dz {tuple(dz_nhwc.shape)}, weight {tuple(w.shape)}, image {(h, wd)}")
+    n = 3 * h * wd
+    if out is None:
+        out = torch.empty((b, 3, h, wd), device=dz_nhwc.device, dtype=torch.float32)
+        ld = n
+    else:
+        require_device(out, "attr_stem_dx out")
+        if out.dim() != 2 or out.shape[0] != b or out.shape[1] < n or out.stride(1) != 1 or out.stride(0) < n \
+                or out.device != dz_nhwc.device:
+            raise RuntimeError(f"attr_stem_dx: out {tuple(out.shape)} stride {out.stride()} cannot hold {(b, n)}")
+        ld = out.stride(0)
+    _lib.call("pipnet_attr_stem_dx_f32", dz_nhwc.data_ptr(), w.data_ptr(), b, h, wd, o, ld, out.data_ptr(),
+              _stream(dz_nhwc))
+    return out
+
+
+def attr_path_weights(scores: Tensor, method: str, alphas: Optional[Tensor] = None,
+                      substep: Optional[Tensor] = None, out=None) -> Tuple[Tensor, Tensor]:
+    """(weights [S], cutoff [] int64) of one target from its scores [S] (ig / lig / idg), on the device.
+    ``out`` = (weights, cutoff) to write into (rows of the per-target outputs)."""
+    _chk_rows("attr_path_weights", scores, "scores", 1)
+    s = scores.numel()
+    if method not in ATTR_METHOD:
+        raise ValueError(f"attr_path_weights: unknown method {method!r}")
+    if method == "idg":
+        if alphas is None or substep is None:
+            raise RuntimeError("attr_path_weights: idg needs alphas and substep")
+        _chk_same("attr_path_weights", scores, alphas=alphas, substep=substep)
+    if out is None:
+        weights = torch.empty(s, device=scores.device, dtype=torch.float32)
+        cutoff = torch.empty((), device=scores.device, dtype=torch.int64)
+    else:
+        weights, cutoff = out
+        _chk_same("attr_path_weights", scores, weights=weights)
+        if cutoff.numel() != 1 or cutoff.dtype != torch.int64 or cutoff.device != scores.device:
+            raise RuntimeError("attr_path_weights: cutoff out must be one int64 on the scores' device")
+    _lib.call("pipnet_attr_path_weights_f32", scores.data_ptr(), _ptr(alphas) if method == "idg" else None,
+              _ptr(substep) if method == "idg" else None, s, ATTR_METHOD[method], LIG_ALPHA_STAR, weights.data_ptr(),
+              cutoff.data_ptr(), _stream(scores))
+    return weights, cutoff
+
+
+def attr_path_reduce(grads: Tensor, weights: Tensor, x: Tensor, baseline, out: Optional[Tensor] = None) -> Tensor:
+    """(x - baseline) * sum_i weights[i] * grads[i] summed in step order: grads [S, ld] rows holding one image's
+    gradient each (the first x.numel() floats of a row), x of any shape -> a map of x's shape."""
+    require_device(grads, "attr_path_reduce grads")
+    _chk(x, "attr_path_reduce image")
+    n = x.numel()
+    if grads.dim() != 2 or grads.shape[1] < n or grads.stride(1) != 1 or grads.stride(0) < n or grads.device != x.device:
+        raise RuntimeError(f"attr_path_reduce: grads {tuple(grads.shape)} stride {grads.stride()} vs image {n}")
+    s = grads.shape[0]
+    _chk_vec("attr_path_reduce", x, s, weights=weights)
+    bt, bv = _attr_baseline("attr_path_reduce", x, baseline)
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _chk_same("attr_path_reduce", x, out=out)
+    _lib.call("pipnet_attr_path_reduce_f32", grads.data_ptr(), grads.stride(0), weights.data_ptr(), x.data_ptr(),
+              _ptr(bt), bv, s, n, out.data_ptr(), _stream(x))
+    return out

@@ -267,10 +267,11 @@ def _count_train_forward(m: nn.Module, xs: Tensor, sd_keep: Dict[int, Tensor], j
 
 
 def _intermediate_backward(layer: nn.Module, x: Tensor, saved: dict, d_inter: Tensor,
-                           need_dx: bool = False) -> Optional[Tensor]:
+                           need_dx: bool = False, param_grads: bool = True) -> Optional[Tensor]:
     """Parameter gradients of the intermediate layer (count_pipnet_utils.py:323-539) and, with
     ``need_dx``, the gradient w.r.t. its input x (the clamped counts) -- None where no gradient
-    flows (a OneHotEncoder without STE: create_modified_encoding is not differentiable)."""
+    flows (a OneHotEncoder without STE: create_modified_encoding is not differentiable).
+    ``param_grads=False``: the input gradient only, no parameter's .grad is touched."""
     from . import _lib
     from .count_pipnet_utils import (BilinearIntermediate, IdentityIntermediate, LinearFull, LinearIntermediate,
                                      OneHotEncoder)
@@ -282,32 +283,32 @@ def _intermediate_backward(layer: nn.Module, x: Tensor, saved: dict, d_inter: Te
         return K.onehot_ste_backward(x, d_inter, layer.positive_grad_strategy, layer.respect_active_grad)
     if isinstance(layer, LinearFull):
         w = layer.linear.weight
-        if w.requires_grad:
+        if param_grads and w.requires_grad:
             _set_grad(w, K.wgrad(d_inter, x))
-        if layer.linear.bias is not None and layer.linear.bias.requires_grad:
+        if param_grads and layer.linear.bias is not None and layer.linear.bias.requires_grad:
             _set_grad(layer.linear.bias, K.colsum(d_inter))
         return K.linear(d_inter, w.detach().t().contiguous(), None, _lib.EPI_NONE) if need_dx else None
     if isinstance(layer, LinearIntermediate):
         w = layer.linear.weight
-        if not (w.requires_grad or need_dx):
+        if not ((param_grads and w.requires_grad) or need_dx):
             return None
         dx, dw = K.linear_intermediate_backward(x, d_inter, w, want_dx=need_dx)
-        if w.requires_grad:
+        if param_grads and w.requires_grad:
             _set_grad(w, dw.view_as(w))
         return dx
     if isinstance(layer, BilinearIntermediate):
         e, u, v = saved["e"], saved["u"], saved["v"]
         du, dv = K.bilinear_bwd_prep(d_inter, u, v)
-        if layer.W.weight.requires_grad:
+        if param_grads and layer.W.weight.requires_grad:
             _set_grad(layer.W.weight, K.wgrad(du, e))
-        if layer.V.weight.requires_grad:
+        if param_grads and layer.V.weight.requires_grad:
             _set_grad(layer.V.weight, K.wgrad(dv, e))
-        if not (layer.embed.weight.requires_grad or need_dx):
+        if not ((param_grads and layer.embed.weight.requires_grad) or need_dx):
             return None
         de = K.linear(du, layer.W.weight.detach().t().contiguous())
         ones = torch.ones(de.shape[1], device=de.device)
         K.linear(dv, layer.V.weight.detach().t().contiguous(), None, _lib.EPI_RESID, scale=ones, r=de, out=de)
-        if layer.embed.weight.requires_grad:
+        if param_grads and layer.embed.weight.requires_grad:
             _set_grad(layer.embed.weight, K.wgrad(de, x))
         return K.linear(de, layer.embed.weight.detach().t().contiguous(), None, _lib.EPI_NONE) if need_dx else None
     raise NotImplementedError(f"HIP count training: no backward for {type(layer).__name__}")
@@ -411,11 +412,15 @@ def hip_train_supported(net: nn.Module) -> bool:
     return trainable_suffix_start(m) < _backbone_units(m)
 
 
-def _forward_saving(m: nn.Module, xs: Tensor, j: int, sd_keep: Dict[int, Tensor]):
+def _forward_saving(m: nn.Module, xs: Tensor, j: int, sd_keep: Dict[int, Tensor], eval_mode: bool = False,
+                    nhwc4: Optional[Tensor] = None):
     """Train-mode forward; features[:j] on the inference executor, features[j:] with plain
     (unfused) kernels whose intermediates are kept: per CNBlock the input x, the depthwise
     output z, the LayerNorm output t, the Linear1 pre-activation h1, GELU output g and the
-    Linear2 output y2; per downsample its input and LayerNorm output."""
+    Linear2 output y2; per downsample its input and LayerNorm output.
+    ``eval_mode``: stochastic depth is the identity (no masks, no 1 / (1 - p) scale: every block
+    runs with rs = None), as under ``net.eval()``.  ``nhwc4`` (j = 0 only): the input already in
+    the stem conv's 4-channel NHWC form, in place of ``xs``."""
     from . import _lib
     from .convnext_features import LayerNorm2d, packed, stochastic_depth_row_scales
     feats, cache = m._net.features, m._net._hip_pack
@@ -424,7 +429,7 @@ def _forward_saving(m: nn.Module, xs: Tensor, j: int, sd_keep: Dict[int, Tensor]
         conv, ln = feats[0][0], feats[0][1]
         if conv.kernel_size != (4, 4) or conv.stride != (4, 4) or conv.in_channels != 3 or conv.padding != (0, 0):
             raise RuntimeError(f"HIP training step: unsupported ConvNeXt stem {conv}")
-        xp = K.nchw_to_nhwc(xs.contiguous(), 4)                     # channels zero-padded 3 -> 4
+        xp = K.nchw_to_nhwc(xs.contiguous(), 4) if nhwc4 is None else nhwc4      # channels zero-padded 3 -> 4
         wp = packed(cache, "0.conv.train", conv.weight,
                     lambda w: torch.nn.functional.pad(w.permute(0, 2, 3, 1), (0, 1)))
         z = K.conv2d_nhwc(xp, wp, conv.bias, 4, 0, _lib.EPI_BIAS)
@@ -434,7 +439,7 @@ def _forward_saving(m: nn.Module, xs: Tensor, j: int, sd_keep: Dict[int, Tensor]
     else:
         h = convnext_features_hip(feats[:j], xs, cache, sd_keep)
         start = j
-    scales = stochastic_depth_row_scales(feats, sd_keep, xs.shape[0], xs.device)
+    scales = {} if eval_mode else stochastic_depth_row_scales(feats, sd_keep, xs.shape[0], xs.device)
     bid = len(_cnblocks(feats[:start]))
     for idx in range(start, len(feats)):
         mod = feats[idx]
@@ -449,9 +454,9 @@ def _forward_saving(m: nn.Module, xs: Tensor, j: int, sd_keep: Dict[int, Tensor]
                 h1 = K.linear(t.view(-1, c), l1.weight, l1.bias, _lib.EPI_BIAS)
                 g = K.gelu_fwd(h1)
                 y2 = K.linear(g, l2.weight, l2.bias, _lib.EPI_BIAS)
-                rs = scales.get(bid) if blk.stochastic_depth.p > 0.0 else None
+                rs = scales.get(bid) if blk.stochastic_depth.p > 0.0 and not eval_mode else None
                 out = K.resid_scale(h.view(-1, c), y2, blk.layer_scale.view(-1), rs, hh * ww).view(b, hh, ww, c)
-                saved.append(("block", blk, key, dict(x=h, z=z, t=t, h1=h1, g=g, y2=y2, rs=rs)))
+                saved.append(("block", blk, key, dict(x=h, z=z, t=t, h1=h1, g=g, y2=y2, rs=rs, key=key)))
                 h = out
                 bid += 1
         elif len(mod) == 2 and isinstance(mod[0], LayerNorm2d) and isinstance(mod[1], nn.Conv2d):
@@ -471,9 +476,13 @@ def _set_grad(p: Tensor, g: Tensor) -> None:
         p.grad = g.reshape(p.shape).contiguous()
 
 
-def _block_backward(blk: CNBlock, sv: dict, dy: Tensor) -> Tensor:
-    """Gradients of one CNBlock (written to the parameters' .grad); returns d input [B,H,W,C]."""
+def _block_backward(blk: CNBlock, sv: dict, dy: Tensor, param_grads: bool = True, cache: Optional[dict] = None) -> Tensor:
+    """Gradients of one CNBlock (written to the parameters' .grad); returns d input [B,H,W,C].
+    ``param_grads=False``: the input gradient only -- no weight-gradient kernel runs, no .grad is
+    touched, the reductions the kernels must write (d_ls, d_gamma, ...) go to scratch and the saved
+    activations are left as they are; ``cache`` then keeps the transposed / flipped weights."""
     from . import _lib
+    from .convnext_features import packed
     dw, ln, l1, l2 = blk.block[0], blk.block[2], blk.block[3], blk.block[5]
     x = sv["x"]
     b, hh, ww, c = x.shape
@@ -481,25 +490,35 @@ def _block_backward(blk: CNBlock, sv: dict, dy: Tensor) -> Tensor:
     d_ls, d_b2 = torch.empty(c, device=dev), torch.empty(c, device=dev)
     dyv = dy.reshape(-1, c)
     dy2 = K.ls_backward(dyv, sv["y2"], blk.layer_scale.view(-1), sv["rs"], hh * ww, d_ls, d_b2)
-    _set_grad(blk.layer_scale, d_ls)
-    _set_grad(l2.bias, d_b2)
-    if l2.weight.requires_grad:
-        _set_grad(l2.weight, K.wgrad(dy2, sv["g"]))
-    dh1 = K.linear(dy2, l2.weight.t().contiguous(), None, _lib.EPI_GELU_BWD, r=sv["h1"])
-    if l1.weight.requires_grad:
-        _set_grad(l1.weight, K.wgrad(dh1, sv["t"].view(-1, c)))
-    if l1.bias.requires_grad:
-        _set_grad(l1.bias, K.colsum(dh1))
-    dt = K.linear(dh1, l1.weight.t().contiguous(), None, _lib.EPI_NONE)
     d_lnw, d_lnb = torch.empty(c, device=dev), torch.empty(c, device=dev)
-    dz = K.ln_backward(sv["z"].view(-1, c), dt, ln.weight, d_lnw, d_lnb, want_dz=True).view(b, hh, ww, c)
-    _set_grad(ln.weight, d_lnw)
-    _set_grad(ln.bias, d_lnb)
-    dwp, d_dwb = torch.empty(49, c, device=dev), torch.empty(c, device=dev)
-    K.dwconv7_wgrad(dz, x, dwp, d_dwb)
-    _set_grad(dw.weight, dwp.t())
-    _set_grad(dw.bias, d_dwb)
-    wflip = dw.weight.detach().flip(2, 3).reshape(c, 49).t().contiguous()
+    if param_grads:
+        _set_grad(blk.layer_scale, d_ls)
+        _set_grad(l2.bias, d_b2)
+        if l2.weight.requires_grad:
+            _set_grad(l2.weight, K.wgrad(dy2, sv["g"]))
+        dh1 = K.linear(dy2, l2.weight.t().contiguous(), None, _lib.EPI_GELU_BWD, r=sv["h1"])
+        if l1.weight.requires_grad:
+            _set_grad(l1.weight, K.wgrad(dh1, sv["t"].view(-1, c)))
+        if l1.bias.requires_grad:
+            _set_grad(l1.bias, K.colsum(dh1))
+        dt = K.linear(dh1, l1.weight.t().contiguous(), None, _lib.EPI_NONE)
+        dz = K.ln_backward(sv["z"].view(-1, c), dt, ln.weight, d_lnw, d_lnb, want_dz=True).view(b, hh, ww, c)
+        _set_grad(ln.weight, d_lnw)
+        _set_grad(ln.bias, d_lnb)
+        dwp, d_dwb = torch.empty(49, c, device=dev), torch.empty(c, device=dev)
+        K.dwconv7_wgrad(dz, x, dwp, d_dwb)
+        _set_grad(dw.weight, dwp.t())
+        _set_grad(dw.bias, d_dwb)
+        wflip = dw.weight.detach().flip(2, 3).reshape(c, 49).t().contiguous()
+    else:
+        cache = {} if cache is None else cache
+        key = sv["key"]
+        w2t = packed(cache, key + ".l2.t", l2.weight, lambda w: w.t())
+        w1t = packed(cache, key + ".l1.t", l1.weight, lambda w: w.t())
+        dh1 = K.linear(dy2, w2t, None, _lib.EPI_GELU_BWD, r=sv["h1"])
+        dt = K.linear(dh1, w1t, None, _lib.EPI_NONE)
+        dz = K.ln_backward(sv["z"].view(-1, c), dt, ln.weight.detach(), d_lnw, d_lnb, want_dz=True).view(b, hh, ww, c)
+        wflip = packed(cache, key + ".dw.flip", dw.weight, lambda w: w.flip(2, 3).reshape(c, 49).t())
     dx = dy.reshape(b, hh, ww, c)                    # residual path; the branch's input grad adds in place
     K.dwconv7_plain(dz, wflip, None, out=dx, accumulate=True)
     return dx
@@ -527,20 +546,21 @@ def _stem_backward(mod: nn.Sequential, sv: dict, dy: Tensor) -> None:
         _set_grad(conv.bias, K.colsum(dz))
 
 
-def _down_backward(mod: nn.Sequential, sv: dict, dy: Tensor, need_dx: bool) -> Optional[Tensor]:
-    """LayerNorm2d + Conv2d(k2, stride 1|2) backward; returns d input when ``need_dx``."""
+def _down_backward(mod: nn.Sequential, sv: dict, dy: Tensor, need_dx: bool, param_grads: bool = True) -> Optional[Tensor]:
+    """LayerNorm2d + Conv2d(k2, stride 1|2) backward; returns d input when ``need_dx``.
+    ``param_grads=False``: the input gradient only (no weight-gradient kernel, no .grad)."""
     from . import _lib
     ln, conv = mod[0], mod[1]
     x, t = sv["x"], sv["t"]
     b, h, w, cin = t.shape
     cout, stride = conv.out_channels, conv.stride[0]
-    if conv.weight.requires_grad:
+    if param_grads and conv.weight.requires_grad:
         gp = torch.empty(cout, 4 * cin, device=t.device)
         K.wgrad_conv2x2(dy, t, stride, gp)
         _set_grad(conv.weight, gp.view(cout, 2, 2, cin).permute(0, 3, 1, 2))
-    if conv.bias is not None and conv.bias.requires_grad:
+    if param_grads and conv.bias is not None and conv.bias.requires_grad:
         _set_grad(conv.bias, K.colsum(dy.reshape(-1, cout)))
-    if not (ln.weight.requires_grad or ln.bias.requires_grad or need_dx):
+    if not (need_dx or (param_grads and (ln.weight.requires_grad or ln.bias.requires_grad))):
         return None
     wd = conv.weight.detach()
     if stride == 1:        # transposed conv = conv of dy (pad 1) with the flipped, transposed taps
@@ -553,15 +573,21 @@ def _down_backward(mod: nn.Sequential, sv: dict, dy: Tensor, need_dx: bool) -> O
         dt = torch.zeros(b, h, w, cin, device=t.device)
         dt[:, :2 * oh, :2 * ow] = gm.view(b, oh, ow, 2, 2, cin).permute(0, 1, 3, 2, 4, 5).reshape(b, 2 * oh, 2 * ow, cin)
     d_lnw, d_lnb = torch.empty(cin, device=t.device), torch.empty(cin, device=t.device)
-    dx = K.ln_backward(x.reshape(-1, cin), dt.reshape(-1, cin), ln.weight, d_lnw, d_lnb, want_dz=need_dx)
-    _set_grad(ln.weight, d_lnw)
-    _set_grad(ln.bias, d_lnb)
+    dx = K.ln_backward(x.reshape(-1, cin), dt.reshape(-1, cin), ln.weight.detach(), d_lnw, d_lnb, want_dz=need_dx)
+    if param_grads:
+        _set_grad(ln.weight, d_lnw)
+        _set_grad(ln.bias, d_lnb)
     return None if dx is None else dx.view(b, h, w, cin)
 
 
-def _addon_suffix_backward(m: nn.Module, feats: Tensor, saved: list, d_logits: Tensor) -> None:
+def _addon_suffix_backward(m: nn.Module, feats: Tensor, saved: list, d_logits: Tensor,
+                           param_grads: bool = True) -> Optional[Tensor]:
     """Backward from d logits (before the prototype softmax) through the add-on (1x1 conv when
-    present) and the saved backbone suffix; every parameter with requires_grad gets .grad."""
+    present) and the saved backbone suffix; every parameter with requires_grad gets .grad.
+    ``param_grads=False``: the input-gradient chain only -- no weight-gradient kernel, no .grad,
+    ``saved`` is left intact (it serves several backward passes) -- and the gradient at the input of
+    the first saved entry comes back: for a saved stem that is d (stem LayerNorm output), the
+    caller's to take through the stem (attribution._stem_dx)."""
     from . import _lib
     mods = list(m._add_on) if isinstance(m._add_on, nn.Sequential) else [m._add_on]
     if len(mods) == 2:                           # 1x1 prototype conv before the softmax
@@ -569,9 +595,9 @@ def _addon_suffix_backward(m: nn.Module, feats: Tensor, saved: list, d_logits: T
         bsz, hh, ww, cf = feats.shape
         pn = conv.out_channels
         dl = d_logits.view(-1, pn)
-        if conv.weight.requires_grad:
+        if param_grads and conv.weight.requires_grad:
             _set_grad(conv.weight, K.wgrad(dl, feats.view(-1, cf)))
-        if conv.bias is not None and conv.bias.requires_grad:
+        if param_grads and conv.bias is not None and conv.bias.requires_grad:
             _set_grad(conv.bias, K.colsum(dl))
         dy = K.linear(dl, conv.weight.detach().view(pn, cf).t().contiguous(), None, _lib.EPI_NONE)
         dy = dy.view(bsz, hh, ww, cf)
@@ -582,6 +608,15 @@ def _addon_suffix_backward(m: nn.Module, feats: Tensor, saved: list, d_logits: T
         resnet_train.backward(m._net, saved[0][3], dy)
         saved.clear()
         return
+    if not param_grads:
+        cache = m._net._hip_pack
+        for i in range(len(saved) - 1, -1, -1):
+            kind, mod, _, sv = saved[i]
+            if kind == "block":
+                dy = _block_backward(mod, sv, dy, param_grads=False, cache=cache)
+            elif kind == "down":
+                dy = _down_backward(mod, sv, dy, need_dx=True, param_grads=False)
+        return dy
     for i in range(len(saved) - 1, -1, -1):
         kind, mod, _, sv = saved[i]
         if kind == "block":
@@ -591,6 +626,7 @@ def _addon_suffix_backward(m: nn.Module, feats: Tensor, saved: list, d_logits: T
         else:
             dy = _down_backward(mod, sv, dy, need_dx=i > 0)
         saved[i] = None                          # free the activations as we go
+    return None
 
 
 def _step_train_optimizers(m: nn.Module, optimizer_net, optimizer_classifier, pretrain: bool,

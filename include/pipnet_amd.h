@@ -56,7 +56,8 @@ extern "C" {
  * Round 6 only ADDS entry points (pipnet_philox_exp1_f32, pipnet_conv2d_nhwc_bf16_plan,
  * pipnet_linear_f32_plan, pipnet_cnblock_mlp_plan); no signature changed.  The prototype
  * explanation entry points (pipnet_softmax_pool_argmax_f32, pipnet_map_argmax_f32,
- * pipnet_topk_update) are additions as well, and so is pipnet_local_explain_f32. */
+ * pipnet_topk_update) are additions as well, and so are pipnet_local_explain_f32 and the
+ * attribution entry points (pipnet_attr_*). */
 #define PIPNET_AMD_ABI_VERSION 3
 int pipnet_amd_abi_version(void);
 const char* pipnet_amd_status_string(int status);
@@ -613,6 +614,45 @@ int pipnet_bn_backward_f32(const float* x, const float* dy, const float* relu_ou
                            float* d_gamma, float* d_beta, float* workspace, void* stream);
 int pipnet_stride_scatter_f32(const float* in, int B, int OH, int OW, int C, int H, int W, int stride, int accumulate,
                               float* out, void* stream);
+
+/* ---- Integrated-gradients pixel attribution (util/saliency_methods.py IG / IDG behind the
+ * wrappers of util/interpret_idg.py:101-135; csrc/attribution.hip) ---------------------------
+ * The path is image_i = baseline + alpha_i (x - baseline); g_i = d target / d image_i.  No entry
+ * point here uses an atomic: every result is bitwise reproducible.
+ * pipnet_attr_path_images_f32: x [3,H,W] NCHW, baseline [3,H,W] or NULL (then the constant
+ *   baseline_value), alpha [S] on the device -> out [S,H,W,4] NHWC, channel 3 zero (the layout
+ *   pipnet_nchw_to_nhwc_f32 with cpad = 4 writes, which the unfused stem conv reads); each value
+ *   is fma(alpha, x - b, b).  out 16-byte aligned, S <= 65535.
+ * pipnet_attr_head_bwd_f32: d target / d logits [B,HW,P] of the prototype head from the upstream
+ *   vector u [B,P] and the head's soft map soft [B,HW,P] (NHWC), any P >= 1 and any B <= 65535:
+ *   pool_mode 0 (softmax + max-pool; loc [B,P] int32 = the pixel of each prototype's maximum,
+ *   pipnet_softmax_pool_argmax_f32): d[b,pix,q] = [loc[b,q] == pix] u_q s_q - s_q a[b,pix] with
+ *   a[b,pix] = sum_{p: loc[b,p] == pix} u_p s_p (inv_tau is not read);
+ *   pool_mode 1 (soft-max or Gumbel-softmax + spatial sum; loc not read):
+ *   d[b,pix,q] = inv_tau y_q (u_q - sum_p u_p y_p).
+ * pipnet_attr_stem_dx_f32: input gradient of the ConvNeXt stem's Conv2d(3, O, 4, stride 4):
+ *   dz [B,H/4,W/4,O] NHWC, w [O,3,4,4] (the module's weight) -> image b at dx + b * ldx as NCHW
+ *   [3,H,W], dx[c, 4i+kh, 4j+kw] = sum_o dz[i,j,o] w[o,c,kh,kw]; rows / columns beyond the last
+ *   whole patch get 0.  O <= 128, H, W >= 4, ldx >= 3 H W, B <= 65535.
+ * pipnet_attr_path_weights_f32: the per-step coefficients of one target from its scores [S]:
+ *   method 0 (ig) w_i = 1 / S; 1 (lig) cutoff = the first i with s_i > max(s) * alpha_star (fp32
+ *   product; none -> 1, 0 -> 1), w_i = 1 / cutoff below it and 0 from it; 2 (idg, alphas [S] and
+ *   substep [S] of the gradient pass) slope_0 = 0, slope_i = (s_i - s_{i-1}) / (alpha_i -
+ *   alpha_{i-1}), w_i = slope_i substep_i / S.  *cutoff (device int64) = the steps averaged.
+ * pipnet_attr_path_reduce_f32: out[e] = (x[e] - b[e]) * sum_i weights[i] grads[i * ldg + e], e < N,
+ *   the sum taken in step order (a chain of FMAs); baseline NULL -> baseline_value.  16-byte loads
+ *   and stores where ldg % 4 == 0 and the operands are 16-byte aligned, a scalar tail. */
+int pipnet_attr_path_images_f32(const float* x, const float* baseline, float baseline_value, const float* alpha,
+                                int S, int H, int W, float* out, void* stream);
+int pipnet_attr_head_bwd_f32(const float* soft, const float* u, const int32_t* loc, int B, int HW, int P,
+                             int pool_mode, float inv_tau, float* d_logits, void* stream);
+int pipnet_attr_stem_dx_f32(const float* dz, const float* w, int B, int H, int W, int O, int64_t ldx, float* dx,
+                            void* stream);
+int pipnet_attr_path_weights_f32(const float* scores, const float* alphas, const float* substep, int S, int method,
+                                 float alpha_star, float* weights, int64_t* cutoff, void* stream);
+int pipnet_attr_path_reduce_f32(const float* grads, int64_t ldg, const float* weights, const float* x,
+                                const float* baseline, float baseline_value, int S, int64_t N, float* out,
+                                void* stream);
 
 #ifdef __cplusplus
 }
