@@ -495,12 +495,12 @@ int head_launch(const T* feat, int B, int HW, int P, int pool_mode, float* proto
                 void* stream) {
   const bool lin = hl.W != nullptr;
   if (B < 0 || HW <= 0 || P <= 0 || (pool_mode != 0 && pool_mode != 1) || (lin && pool_mode != 0)) return PIPNET_ERR_ARG;
+  const int nj = nj_bucket(P);
+  if (nj < 0) return PIPNET_ERR_ARG;
+  if (B == 0) return PIPNET_OK;   // an empty batch: its tensors hold no memory, their pointers may be null
   if (!feat || !proto || !pooled) return PIPNET_ERR_ARG;
   if (lin && (hl.K <= 0 || !hl.out || !hl.tickets || !hl.part)) return PIPNET_ERR_ARG;
   if (lin && (P & 3) == 0 && !aligned16(hl.W)) return PIPNET_ERR_ALIGN;
-  if (B == 0) return PIPNET_OK;
-  const int nj = nj_bucket(P);
-  if (nj < 0) return PIPNET_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (!lin && !zero_fill(pooled, (int64_t)B * P, s)) return PIPNET_ERR_LAUNCH;   // the fused head needs none
   const dim3 grid((HW + PIX_PER_BLOCK - 1) / PIX_PER_BLOCK, B);
@@ -579,11 +579,12 @@ extern "C" int pipnet_nonneg_linear_f32(const float* x, int B, int D, const floa
 namespace {
 int count_gumbel_launch(const float* logits, int B, int HW, int P, float tau, const float* exp_noise, uint64_t seed,
                         uint64_t offset, const uint64_t* seed_dev, float* proto, int32_t* hist, void* stream) {
-  if (B < 0 || HW <= 0 || P <= 0 || (P & 3) || !(tau > 0.f) || !logits || !proto || !hist) return PIPNET_ERR_ARG;
-  if (!aligned16(logits) || !aligned16(proto)) return PIPNET_ERR_ALIGN;
-  if (B == 0) return PIPNET_OK;
+  if (B < 0 || HW <= 0 || P <= 0 || (P & 3) || !(tau > 0.f)) return PIPNET_ERR_ARG;
   const int nj = nj_bucket(P);
   if (nj < 0) return PIPNET_ERR_ARG;
+  if (B == 0) return PIPNET_OK;   // an empty batch: its tensors hold no memory, their pointers may be null
+  if (!logits || !proto || !hist) return PIPNET_ERR_ARG;
+  if (!aligned16(logits) || !aligned16(proto)) return PIPNET_ERR_ALIGN;
   hipStream_t s = (hipStream_t)stream;
   if (!zero_fill(hist, (int64_t)B * P, s)) return PIPNET_ERR_LAUNCH;
   const dim3 grid((HW + CG_PIX_PER_BLOCK - 1) / CG_PIX_PER_BLOCK, B);

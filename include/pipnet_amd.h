@@ -228,7 +228,9 @@ int pipnet_nchw_to_s2d_bf16(const float* x, int B, int H, int W, void* y, void* 
 int pipnet_stem_pool_bf16(const void* s2d, int B, int SH, int SW, const void* w, const float* bias, void* y,
                           void* stream);
 
-/* pipnet_softmax_pool_f32 reading bf16 logits (fp32 softmax, fp32 proto / pooled out). */
+/* pipnet_softmax_pool_f32 reading bf16 logits (fp32 softmax, fp32 proto / pooled out).  Both, and
+ * the fused forms below: B == 0 with valid HW, P, pool_mode is PIPNET_OK whatever the pointers
+ * (an empty batch has none). */
 int pipnet_softmax_pool_bf16(const void* feat, int B, int HW, int P, int pool_mode, float* proto,
                              float* pooled, void* stream);
 
@@ -379,7 +381,8 @@ int pipnet_nonneg_linear_f32(const float* x, int B, int D, const float* W, const
  * E ~ Exp(1) is read from exp_noise ([B,P,HW], the NCHW layout of torch's draw) when
  * non-NULL, else generated in-kernel by Philox4x32-10 keyed by (seed, offset + element/4):
  * one 128-bit block feeds channels 4k..4k+3 of a pixel.
- * logits, proto: [B,HW,P], 16-byte aligned, P % 4 == 0; hist: [B,P] int32 (zeroed by this call). */
+ * logits, proto: [B,HW,P], 16-byte aligned, P % 4 == 0; hist: [B,P] int32 (zeroed by this call).
+ * B == 0 with valid HW, P, tau is PIPNET_OK whatever the pointers (an empty batch has none). */
 int pipnet_count_gumbel_f32(const float* logits, int B, int HW, int P, float tau,
                             const float* exp_noise, uint64_t seed, uint64_t offset, float* proto,
                             int32_t* hist, void* stream);
