@@ -78,6 +78,9 @@ SIGNATURES = {
     "pipnet_count_encode_f32": [P, I32, I32, I32, I32, I32, P, P, P],
     "pipnet_resize_plan": [P, I32, I32, I32, P, P],
     "pipnet_resize_normalize_rgb8": [P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P, P],
+    "pipnet_augment_geometry_plan": [P, I32, I32, I32, P, P, P],
+    "pipnet_augment_geometry_rgb8": [P, P, P, P, I32, I32, I32, I32, I32, P, P, P],
+    "pipnet_augment_view_rgb8": [P, P, I32, I32, I32, I32, I32, P, P, F32, U64, P, P, P],
     "pipnet_train_align_partials": [],
     "pipnet_train_align_partial_f32": [P, I32, I32, I32, P, P],
     "pipnet_train_loss_f32": [P, I32, I32, P, P, P, I32, I32, P, I32, F32, F32, F32, F32, I32, P, P, P],

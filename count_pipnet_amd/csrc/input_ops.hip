@@ -19,68 +19,24 @@
 //   * ToTensor + Normalize in fp32 with IEEE division: (u8 / 255 - mean) / std.
 // HBM traffic per image: the decoded pixels (read ~once, taps hit L1/L2) + 12 B per output
 // pixel (+3 B with the optional uint8 HWC copy).
-#include "common.hpp"
+#include "resample.hpp"
 
 namespace {
 
-constexpr int PREC = 22;   // PRECISION_BITS = 32 - 8 - 2
-
-__host__ __device__ inline int ksize_for(int in_size, int out_size) {
-  const double scale = (double)((float)in_size - 0.0f) / out_size;
-  const double support = scale < 1.0 ? 1.0 : scale;
-  return (int)ceil(support) * 2 + 1;
-}
-
-__device__ inline double triangle(double x) {
-  if (x < 0.0) x = -x;
-  return x < 1.0 ? 1.0 - x : 0.0;
-}
+using namespace pipnet_resample;
 
 // Table row = (xmin, n, k[0..kmax)) for one output coordinate of one image axis.
 // Layout: [B][out_h + out_w][2 + kmax] int32, vertical rows first.
 __global__ __launch_bounds__(256) void resize_coeffs_kernel(const int32_t* __restrict__ sizes, int B, int out_h,
                                                             int out_w, int kmax, int32_t* __restrict__ table) {
-#pragma clang fp contract(off)
   const int per = out_h + out_w;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= B * per) return;
   const int b = i / per;
   const int r = i - b * per;
   const bool vert = r < out_h;
-  const int xx = vert ? r : r - out_h;
-  const int in_size = sizes[2 * b + (vert ? 0 : 1)];
-  const int out_size = vert ? out_h : out_w;
-  int32_t* row = table + (int64_t)i * (2 + kmax);
-  const double scale = (double)((float)in_size - 0.0f) / out_size;
-  const double filterscale = scale < 1.0 ? 1.0 : scale;
-  const double support = 1.0 * filterscale;
-  const double center = 0.0 + (xx + 0.5) * scale;
-  const double ss = 1.0 / filterscale;
-  int xmin = (int)(center - support + 0.5);
-  if (xmin < 0) xmin = 0;
-  int xmax = (int)(center + support + 0.5);
-  if (xmax > in_size) xmax = in_size;
-  xmax -= xmin;
-  if (xmax > kmax) xmax = kmax;    // cannot happen (kmax >= ksize); keeps the row in bounds
-  double ww = 0.0;
-  for (int x = 0; x < xmax; ++x) ww += triangle(((double)(x + xmin) - center + 0.5) * ss);
-  for (int x = 0; x < kmax; ++x) {
-    int32_t q = 0;
-    if (x < xmax) {
-      double w = triangle(((double)(x + xmin) - center + 0.5) * ss);
-      if (ww != 0.0) w /= ww;
-      const double f = w * (double)(1 << PREC);
-      q = w < 0 ? (int32_t)(-0.5 + f) : (int32_t)(0.5 + f);
-    }
-    row[2 + x] = q;
-  }
-  row[0] = xmin;
-  row[1] = xmax;
-}
-
-__device__ inline int clip8(int ss) {
-  const int v = ss >> PREC;            // arithmetic shift, as Pillow's clip8 lookup
-  return v < 0 ? 0 : (v > 255 ? 255 : v);
+  coeff_row(sizes[2 * b + (vert ? 0 : 1)], vert ? out_h : out_w, vert ? r : r - out_h, kmax,
+            table + (int64_t)i * (2 + kmax));
 }
 
 // One thread per output pixel (b, y, x), x fastest: coalesced plane stores.
@@ -96,62 +52,11 @@ __global__ __launch_bounds__(256) void resize_normalize_kernel(
   const int y = rem / out_w;
   const int x = rem - y * out_w;
   const int h = sizes[2 * b], w = sizes[2 * b + 1];
-  const uint8_t* img = pix + offsets[b];
   const int rs = 2 + kmax;
   const int32_t* tv = table + ((int64_t)b * (out_h + out_w) + y) * rs;           // vertical row y
   const int32_t* th = table + ((int64_t)b * (out_h + out_w) + out_h + x) * rs;   // horizontal row x
-  const bool need_h = w != out_w, need_v = h != out_h;
   int c3[3];
-  if (!need_h && !need_v) {
-    const uint8_t* p = img + ((int64_t)y * w + x) * 3;
-    c3[0] = p[0], c3[1] = p[1], c3[2] = p[2];
-  } else if (!need_v) {                  // horizontal pass only
-    const int xmin = th[0], n = th[1];
-    const uint8_t* p = img + ((int64_t)y * w + xmin) * 3;
-    int a0 = 1 << (PREC - 1), a1 = a0, a2 = a0;
-    for (int t = 0; t < n; ++t) {
-      const int k = th[2 + t];
-      a0 += p[3 * t] * k, a1 += p[3 * t + 1] * k, a2 += p[3 * t + 2] * k;
-    }
-    c3[0] = clip8(a0), c3[1] = clip8(a1), c3[2] = clip8(a2);
-  } else if (!need_h) {                  // vertical pass only
-    const int ymin = tv[0], n = tv[1];
-    int a0 = 1 << (PREC - 1), a1 = a0, a2 = a0;
-    for (int s = 0; s < n; ++s) {
-      const uint8_t* p = img + ((int64_t)(ymin + s) * w + x) * 3;
-      const int k = tv[2 + s];
-      a0 += p[0] * k, a1 += p[1] * k, a2 += p[2] * k;
-    }
-    c3[0] = clip8(a0), c3[1] = clip8(a1), c3[2] = clip8(a2);
-  } else if (h > 100 * w && out_h < h) {   // Pillow: vertical pass first for very tall images
-    const int ymin = tv[0], nv = tv[1], xmin = th[0], nh = th[1];
-    int a0 = 1 << (PREC - 1), a1 = a0, a2 = a0;
-    for (int t = 0; t < nh; ++t) {
-      int v0 = 1 << (PREC - 1), v1 = v0, v2 = v0;
-      for (int s = 0; s < nv; ++s) {
-        const uint8_t* p = img + ((int64_t)(ymin + s) * w + xmin + t) * 3;
-        const int k = tv[2 + s];
-        v0 += p[0] * k, v1 += p[1] * k, v2 += p[2] * k;
-      }
-      const int k = th[2 + t];
-      a0 += clip8(v0) * k, a1 += clip8(v1) * k, a2 += clip8(v2) * k;
-    }
-    c3[0] = clip8(a0), c3[1] = clip8(a1), c3[2] = clip8(a2);
-  } else {                                // horizontal pass first (the common case)
-    const int ymin = tv[0], nv = tv[1], xmin = th[0], nh = th[1];
-    int a0 = 1 << (PREC - 1), a1 = a0, a2 = a0;
-    for (int s = 0; s < nv; ++s) {
-      const uint8_t* p = img + ((int64_t)(ymin + s) * w + xmin) * 3;
-      int v0 = 1 << (PREC - 1), v1 = v0, v2 = v0;
-      for (int t = 0; t < nh; ++t) {
-        const int k = th[2 + t];
-        v0 += p[3 * t] * k, v1 += p[3 * t + 1] * k, v2 += p[3 * t + 2] * k;
-      }
-      const int k = tv[2 + s];
-      a0 += clip8(v0) * k, a1 += clip8(v1) * k, a2 += clip8(v2) * k;
-    }
-    c3[0] = clip8(a0), c3[1] = clip8(a1), c3[2] = clip8(a2);
-  }
+  resample_pixel(pix + offsets[b], h, w, out_h, out_w, tv, th, y, x, c3);
   if (gray) {
     const int l = (c3[0] * 19595 + c3[1] * 38470 + c3[2] * 7471 + 0x8000) >> 16;
     c3[0] = c3[1] = c3[2] = l;

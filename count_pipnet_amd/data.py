@@ -18,6 +18,11 @@ MI355X split:
     (``pipnet_resize_normalize_rgb8``), bit-identical to Pillow + torchvision
     (oracle/input_ref.py), writing the NCHW fp32 batch the backbone reads.
 
+Training input follows the same split (second half of this module): ``DeviceTrainLoader``'s
+workers decode and pack, ``DeviceTrainTransform`` draws the augmentation parameters on the host
+(``augment.py``) and runs ``TwoAugSupervisedDataset``'s transform1 / transform2
+(util/data.py:261-617) on the device (``csrc/augment_ops.hip``), yielding ``(xs1, xs2, ys)``.
+
 ``ImageFolder`` semantics (class discovery, sample order, extensions, errors) follow
 torchvision.datasets.folder (third party, absent here) so ``classes`` / ``targets`` and the
 order of evaluation match the reference's loaders exactly.
@@ -196,3 +201,106 @@ def get_eval_loader(test_dir: str, img_size: int, batch_size: int, device, num_w
     ds = DecodedImageFolder(test_dir)
     return DeviceEvalLoader(ds, DeviceEvalTransform(img_size, mean, std, grayscale), device, batch_size,
                             num_workers=num_workers, shuffle=shuffle)
+
+
+# ---- training input: the two-view augmentation on the device ----------------------------------
+
+class DeviceTrainTransform:
+    """``TwoAugSupervisedDataset``'s transforms (util/data.py:596-617) on the GPU: a
+    ``PackedImages`` batch -> the two augmented, normalised [B,3,size,size] fp32 views
+    ``(xs1, xs2)`` that ``train_pipnet`` reads (one tensor ``xs`` with ``views=1``, the
+    reference's ``trainset_normal_augment``).  ``policy`` names the dataset family
+    (``augment.POLICIES``, keyed by the reference's dataset strings).
+
+    The random parameters are drawn on the host (``augment.sample_params``) from ``generator``;
+    explicit ``params`` (an ``augment.AugmentParams``) bypass the sampler.  The pixel arithmetic
+    runs in ``pipnet_augment_geometry_rgb8`` / ``pipnet_augment_view_rgb8`` and is, for the same
+    parameters, bit-identical to the reference's Pillow / torchvision transforms."""
+
+    def __init__(self, policy, size: int, mean=IMAGENET_MEAN, std=IMAGENET_STD, views: int = 2):
+        from . import augment
+        self.policy = augment.get_policy(policy)
+        self.size = int(size)
+        self.s1, self.s2 = self.policy.sizes(self.size)
+        self.mean = tuple(float(v) for v in mean)
+        self.std = tuple(float(v) for v in std)
+        self.views = int(views)
+        self._count = 0               # images seen: the id of the next image's parameter stream
+
+    def __call__(self, packed: PackedImages, device, generator: Optional[torch.Generator] = None, params=None,
+                 first_id: Optional[int] = None, noise: Optional[torch.Tensor] = None):
+        from . import augment
+        from . import kernels as K
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("DeviceTrainTransform runs on a ROCm device only (there is no CPU fallback)")
+        sizes_host = packed.sizes.cpu().numpy() if packed.sizes.is_cuda else packed.sizes.numpy()
+        n = int(sizes_host.shape[0])
+        if params is None:
+            if first_id is None:
+                first_id = self._count
+                self._count += n
+            params = augment.sample_params(self.policy, self.size, n, generator, first_id, self.views)
+        seed = int(generator.initial_seed()) if generator is not None else int(torch.initial_seed())
+        pixels = packed.pixels.to(dev, non_blocking=True)
+        offsets = packed.offsets.to(dev, non_blocking=True)
+        sizes = packed.sizes.to(dev, non_blocking=True)
+        u8 = K.augment_geometry_rgb8(pixels, offsets, sizes, sizes_host, params.geom, self.s1, self.s2)
+        xs = K.augment_view_rgb8(u8, params.view, self.size, self.mean, self.std, self.policy.grayscale,
+                                 augment.NOISE_STD, seed, noise)
+        return xs[0] if xs.shape[0] == 1 else tuple(xs.unbind(0))
+
+
+class DeviceTrainLoader:
+    """Iterates ``(xs1, xs2, ys)`` device batches like the reference's ``trainloader``
+    (util/data.py:141-149: ``shuffle`` or a ``WeightedRandomSampler``, ``drop_last=True``)
+    followed by the ``.to(device)`` of pipnet/train.py: host workers decode and pack, the device
+    augments.  ``dataset`` is a ``DecodedImageFolder`` or a ``Subset`` of one.  ``seed`` fixes
+    both the order and the augmentation, so two loaders with one seed yield the same batches;
+    successive epochs of one loader differ.  ``len()`` and ``dataset`` as a DataLoader's."""
+
+    def __init__(self, dataset, transform: DeviceTrainTransform, device, batch_size: int, num_workers: int = 0,
+                 shuffle: bool = True, drop_last: bool = True, sampler=None, seed: Optional[int] = None):
+        if seed is None:
+            seed = int(torch.empty((), dtype=torch.int64).random_().item())
+        self.dataset = dataset
+        self.transform = transform
+        self.device = torch.device(device)
+        self.batch_size = batch_size
+        self.seed = int(seed)
+        self.generator = torch.Generator().manual_seed(self.seed)        # augmentation parameters
+        order = torch.Generator().manual_seed(self.seed)                 # shuffle / sampler draws
+        if sampler is not None and hasattr(sampler, "generator") and sampler.generator is None:
+            sampler.generator = order
+        self.loader = torch.utils.data.DataLoader(dataset, batch_size=batch_size,
+                                                  shuffle=shuffle if sampler is None else False, sampler=sampler,
+                                                  num_workers=num_workers, collate_fn=collate_decoded,
+                                                  pin_memory=True, drop_last=drop_last, generator=order)
+        self._count = 0
+
+    def __len__(self) -> int:
+        return len(self.loader)
+
+    def __iter__(self):
+        for packed in self.loader:
+            n = int(packed.sizes.shape[0])
+            views = self.transform(packed, self.device, generator=self.generator, first_id=self._count)
+            self._count += n
+            ys = packed.targets.to(self.device, non_blocking=True)
+            yield (views, ys) if isinstance(views, torch.Tensor) else (*views, ys)
+
+
+def get_train_loader(train_dir: str, dataset: str, img_size: int, batch_size: int, device, num_workers: int = 8,
+                     mean=IMAGENET_MEAN, std=IMAGENET_STD, shuffle: bool = True, sampler=None,
+                     indices: Optional[Sequence[int]] = None, seed: Optional[int] = None,
+                     views: int = 2) -> DeviceTrainLoader:
+    """The reference's ``trainloader`` (util/data.py:141-149, :237: a ``Subset`` of
+    ``TwoAugSupervisedDataset(ImageFolder(train_dir), transform1, transform2)``, ``drop_last=True``)
+    with the augmentation of ``dataset`` (the reference's ``--dataset`` string; ``'CUB-200-2011-pretrain'``
+    for get_birds' pretraining set) on the GPU.  ``indices`` is the reference's ``train_indices``
+    split, ``sampler`` its ``WeightedRandomSampler``; ``views=1`` gives ``trainloader_normal_augment``."""
+    ds = DecodedImageFolder(train_dir)
+    if indices is not None:
+        ds = torch.utils.data.Subset(ds, list(indices))
+    return DeviceTrainLoader(ds, DeviceTrainTransform(dataset, img_size, mean, std, views), device, batch_size,
+                             num_workers=num_workers, shuffle=shuffle, sampler=sampler, seed=seed)

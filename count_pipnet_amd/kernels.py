@@ -1229,6 +1229,108 @@ def resize_normalize_rgb8(pixels: Tensor, offsets: Tensor, sizes: Tensor, sizes_
     return (out, out_u8) if want_u8 else out
 
 
+# ---- two-view training augmentation (csrc/augment_ops.hip) ----------------------------------
+AUG_GEOM_PARAMS, AUG_VIEW_PARAMS = 13, 8        # include/pipnet_amd.h PIPNET_AUG_*_PARAMS
+AUG_OP_SHARPNESS, AUG_OP_LAST = 4, 8
+
+
+def _host_params(t, shape, what: str) -> Tensor:
+    t = torch.as_tensor(t)
+    if t.is_cuda or t.dtype != torch.float64 or tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"{what}: expected a host float64 tensor of shape {tuple(shape)}, got "
+                           f"{t.dtype} {tuple(t.shape)} on {t.device}")
+    if not bool(torch.isfinite(t).all()):
+        raise RuntimeError(f"{what}: parameters must be finite")
+    return t.contiguous()
+
+
+def augment_geometry_rgb8(pixels: Tensor, offsets: Tensor, sizes: Tensor, sizes_host, gparams, s1: int,
+                          s2: int) -> Tensor:
+    """transform1 of the reference's training sets on a ragged batch packed as for
+    ``resize_normalize_rgb8``: Resize((s1, s1)) -> affine warp (NEAREST) -> flip ->
+    crop(box).resize((s2, s2), BILINEAR).  ``gparams`` is the host [B,13] float64 table of
+    include/pipnet_amd.h (augment.sample_params draws it).  Returns [B,s2,s2,3] uint8."""
+    import ctypes
+
+    import numpy as np
+    if not (pixels.is_cuda and pixels.dtype == torch.uint8 and pixels.is_contiguous()):
+        raise RuntimeError("augment_geometry_rgb8: pixels must be a contiguous uint8 ROCm device tensor "
+                           "(there is no CPU fallback)")
+    if not (offsets.is_cuda and offsets.dtype == torch.int64 and sizes.is_cuda and sizes.dtype == torch.int32):
+        raise RuntimeError("augment_geometry_rgb8: offsets (int64) / sizes (int32) must be device tensors")
+    sizes_np = np.ascontiguousarray(np.asarray(sizes_host, dtype=np.int32).reshape(-1, 2))
+    b = sizes_np.shape[0]
+    if offsets.shape != (b,) or tuple(sizes.shape) != (b, 2):
+        raise RuntimeError(f"augment_geometry_rgb8: {b} images but offsets {tuple(offsets.shape)}, "
+                           f"sizes {tuple(sizes.shape)}")
+    s1, s2 = int(s1), int(s2)
+    gp = _host_params(gparams, (b, AUG_GEOM_PARAMS), "augment_geometry_rgb8 gparams")
+    if b:
+        top, left, ch, cw = (gp[:, k] for k in range(9, 13))
+        if bool(((top < 0) | (left < 0) | (ch < 1) | (cw < 1) | (top + ch > s1) | (left + cw > s1)).any()):
+            raise RuntimeError(f"augment_geometry_rgb8: a crop box leaves the {s1}x{s1} image")
+        if bool(((ch > 100 * cw) & (ch > s2)).any()):
+            raise RuntimeError("augment_geometry_rgb8: crop boxes taller than 100x their width are not supported")
+        if bool((gp[:, 1:7].abs() >= 16384).any()) or bool(((gp[:, 0] < 0) | (gp[:, 0] > 2)).any()):
+            raise RuntimeError("augment_geometry_rgb8: affine matrix out of range")
+    dev = pixels.device
+    kmax1, kmax2, wsb = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+    _lib.call("pipnet_augment_geometry_plan", sizes_np.ctypes.data, b, s1, s2, ctypes.byref(kmax1),
+              ctypes.byref(kmax2), ctypes.byref(wsb))
+    out = torch.empty((b, s2, s2, 3), device=dev, dtype=torch.uint8)
+    ws = torch.empty(max(1, wsb.value // 4), device=dev, dtype=torch.int32)
+    gp_dev = gp.to(dev, non_blocking=True)
+    _lib.call("pipnet_augment_geometry_rgb8", pixels.data_ptr(), offsets.data_ptr(), sizes.data_ptr(),
+              gp_dev.data_ptr(), b, s1, s2, kmax1.value, kmax2.value, ws.data_ptr(), out.data_ptr(),
+              torch.cuda.current_stream(dev).cuda_stream)
+    return out
+
+
+def augment_view_rgb8(images: Tensor, vparams, s: int, mean, std, grayscale: bool = False, noise_std: float = 0.1,
+                      seed: int = 0, noise: Optional[Tensor] = None) -> Tensor:
+    """transform2 of the reference's training sets, once per view: colour operation(s) ->
+    RandomCrop(s) -> [Grayscale(3)] -> ToTensor -> [+ noise] -> Normalize.  ``images``
+    [B,S2,S2,3] uint8 (augment_geometry_rgb8's output), ``vparams`` the host [V,B,8] float64
+    table of include/pipnet_amd.h.  ``noise`` [V,B,3,s,s] injects the addends of the flagged
+    images; None draws N(0, noise_std^2) from Philox keyed by ``seed``.  Returns [V,B,3,s,s] fp32."""
+    import ctypes
+    if not (images.is_cuda and images.dtype == torch.uint8 and images.is_contiguous() and images.dim() == 4
+            and images.shape[1] == images.shape[2] and images.shape[3] == 3):
+        raise RuntimeError("augment_view_rgb8: images must be a contiguous [B,S,S,3] uint8 ROCm device tensor "
+                           "(there is no CPU fallback)")
+    b, s2, s = int(images.shape[0]), int(images.shape[1]), int(s)
+    vp = torch.as_tensor(vparams)
+    if vp.dim() != 3:
+        raise RuntimeError("augment_view_rgb8: vparams must be [V,B,8]")
+    v = int(vp.shape[0])
+    vp = _host_params(vp, (v, b, AUG_VIEW_PARAMS), "augment_view_rgb8 vparams")
+    if not 0 < s <= s2:
+        raise RuntimeError(f"augment_view_rgb8: crop {s} does not fit the {s2}x{s2} image")
+    if b:
+        ops = vp[:, :, [0, 2]]
+        if bool(((ops < 0) | (ops > AUG_OP_LAST) | (ops != ops.round())).any()):
+            raise RuntimeError("augment_view_rgb8: unknown colour operation")
+        if bool((vp[:, :, 2] == AUG_OP_SHARPNESS).any()):
+            raise RuntimeError("augment_view_rgb8: Sharpness cannot be the second operation of a chain")
+        if bool(((vp[:, :, 4:6] < 0) | (vp[:, :, 4:6] > s2 - s)).any()):
+            raise RuntimeError("augment_view_rgb8: a crop offset leaves the image")
+        if bool(((vp[:, :, 7] < 0) | (vp[:, :, 7] >= 2 ** 31)).any()):
+            raise RuntimeError("augment_view_rgb8: image ids must be in [0, 2^31)")
+    dev = images.device
+    if noise is not None:
+        _chk(noise, "noise")
+        if tuple(noise.shape) != (v, b, 3, s, s):
+            raise RuntimeError(f"augment_view_rgb8: noise must be {(v, b, 3, s, s)}, got {tuple(noise.shape)}")
+    out = torch.empty((v, b, 3, s, s), device=dev, dtype=torch.float32)
+    m = (ctypes.c_float * 3)(*[float(x) for x in mean])
+    sd = (ctypes.c_float * 3)(*[float(x) for x in std])
+    vp_dev = vp.to(dev, non_blocking=True)
+    _lib.call("pipnet_augment_view_rgb8", images.data_ptr(), vp_dev.data_ptr(), v, b, s2, s, int(bool(grayscale)),
+              m, sd, float(noise_std), int(seed) & ((1 << 64) - 1), _ptr(noise), out.data_ptr(),
+              torch.cuda.current_stream(dev).cuda_stream)
+    return out
+
+
 # ---- training step, finetune phase (csrc/train_ops.hip) -------------------------------------
 TRAIN_MODE = {"train": 0, "pretrain": 1, "finetune": 2}
 

@@ -454,6 +454,46 @@ int pipnet_resize_normalize_rgb8(const uint8_t* pixels, const int64_t* offsets, 
                                  const float* mean3, const float* std3, int32_t* workspace,
                                  float* out, uint8_t* out_u8, void* stream);
 
+/* ---- two-view training augmentation (util/data.py:261-617) --------------------------------
+ * TwoAugSupervisedDataset's transform1 (once per image) and transform2 (once per view) on a
+ * ragged batch of decoded RGB images.  The random parameters are drawn on the host
+ * (count_pipnet_amd/augment.py) and passed as doubles; given the same parameters the pixel
+ * arithmetic is bit-identical to Pillow 12.2.0 ("Training augmentation").
+ *
+ * gparams [B][PIPNET_AUG_GEOM_PARAMS] (device):
+ *   0      warp path: 0 none, 1 Pillow's 16.16 fixed-point affine (m1 != 0 or m3 != 0),
+ *          2 Pillow's double-precision affine (m1 == m3 == 0: translate / scale only)
+ *   1..6   m0..m5, the output -> input matrix of Image.transform(AFFINE, NEAREST)
+ *   7      fill colour (all three bands)        8  horizontal flip (0 / 1)
+ *   9..12  crop box of RandomResizedCrop in the S1 x S1 image: top, left, height, width
+ * vparams [V][B][PIPNET_AUG_VIEW_PARAMS] (device):
+ *   0, 1   first colour operation and its parameter; 2, 3 the second (never Sharpness)
+ *          0 identity, 1 Brightness, 2 Color, 3 Contrast, 4 Sharpness (parameter = ImageEnhance
+ *          factor), 5 Posterize (bits), 6 Solarize (threshold), 7 AutoContrast, 8 Equalize
+ *   4, 5   RandomCrop offset (top, left) of the s x s window in the S2 x S2 image
+ *   6      add noise (0 / 1)                    7  image id (< 2^32) of the Philox counter
+ *
+ * pipnet_augment_geometry_plan (host only): sizes_host [B][2] = (h, w) -> taps per output
+ *   coordinate of the two resamples and the device workspace size in bytes.
+ * pipnet_augment_geometry_rgb8: Resize((S1, S1)) -> affine warp -> flip -> crop(box)
+ *   .resize((S2, S2), BILINEAR) -> out_u8 [B,S2,S2,3].  pixels / offsets / sizes as
+ *   pipnet_resize_normalize_rgb8.
+ * pipnet_augment_view_rgb8: images [B,S2,S2,3] uint8 -> out [V,B,3,s,s] fp32 = colour
+ *   operations (whole-image statistics from the S2 x S2 image), crop, [Grayscale(3)], / 255,
+ *   [+ noise], (x - mean) / std.  noise: optional [V,B,3,s,s] addends for the flagged images;
+ *   NULL draws N(0, noise_std^2) from Philox4x32-10 keyed by seed, counter (view, image id,
+ *   pixel). */
+#define PIPNET_AUG_GEOM_PARAMS 13
+#define PIPNET_AUG_VIEW_PARAMS 8
+int pipnet_augment_geometry_plan(const int32_t* sizes_host, int B, int S1, int S2, int* kmax1, int* kmax2,
+                                 int64_t* workspace_bytes);
+int pipnet_augment_geometry_rgb8(const uint8_t* pixels, const int64_t* offsets, const int32_t* sizes,
+                                 const double* gparams, int B, int S1, int S2, int kmax1, int kmax2,
+                                 int32_t* workspace, uint8_t* out_u8, void* stream);
+int pipnet_augment_view_rgb8(const uint8_t* images, const double* vparams, int V, int B, int S2, int s,
+                             int grayscale, const float* mean3, const float* std3, float noise_std,
+                             uint64_t seed, const float* noise, float* out, void* stream);
+
 /* ---- training step, finetune phase (pipnet/train.py:75-140) ----
  * The batch is cat([xs1, xs2]) (train.py:84): N = 2*Bh rows, proto features NHWC
  * [N][HW][P] (rows n and Bh*HW + n are the two views of one pixel), pooled [N][P],
