@@ -40,7 +40,11 @@ SIGNATURES = {
     "pipnet_conv2d_nhwc_bf16_tile": [P, I32, I32, I32, I32, P, P, I32, I32, I32, I32, I32, P, I32, P, I32, P],
     "pipnet_conv2d_nhwc_bf16_plan": [I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32],
     "pipnet_linear_f32_plan": [I32, I32, I32, I32, I32],
-    "pipnet_cnblock_mlp_plan": [I64, I32, I32],
+    "pipnet_linear_f32_label": [I32, I32, I32, I32, I32, I32, ctypes.c_char_p, I32],
+    "pipnet_conv2d_nhwc_bf16_label": [I32] * 11 + [ctypes.c_char_p, I32],
+    "pipnet_conv2d_nhwc_s3_label": [I32] * 11 + [ctypes.c_char_p, I32],
+    "pipnet_conv1x1_bf16_dual_label": [I64, I32, I32, I32, ctypes.c_char_p, I32],
+    "pipnet_cnblock_mlp_label": [I64, I32, I32, ctypes.c_char_p, I32],
     "pipnet_count_gumbel_soft_f32": [P, I32, I32, I32, F32, P, U64, U64, P, P, P],
     "pipnet_philox_exp1_f32": [U64, U64, I64, I32, P, P],
     "pipnet_nonneg_linear_dx_f32": [P, P, I32, I32, I32, P, P],
@@ -127,7 +131,7 @@ EPI_GELU_BWD = 8
 EPI_S3_GELU, EPI_F32_BIAS, EPI_F32_RESID = 9, 10, 11      # split-bf16 ("bf16x3") ConvNeXt path
 EPI_DUAL_BIAS_RELU = 12        # pipnet_conv1x1_bf16_dual: downsample + conv1 of a first Bottleneck
 
-ABI_VERSION = 3          # include/pipnet_amd.h PIPNET_AMD_ABI_VERSION
+ABI_VERSION = 4          # include/pipnet_amd.h PIPNET_AMD_ABI_VERSION
 
 _lib = None
 
@@ -180,3 +184,11 @@ def check(status: int, what: str) -> None:
 
 def call(name: str, *args) -> None:
     check(getattr(load(), name)(*args), name)
+
+
+def label(name: str, *args) -> str:
+    """A profiling-label query (pipnet_*_label): the kernel name the launch with these arguments runs."""
+    buf = ctypes.create_string_buffer(256)
+    if getattr(load(), name)(*args, buf, len(buf)) < 0:
+        raise RuntimeError(f"{name}{args}: the library launches no kernel for these arguments")
+    return buf.value.decode()

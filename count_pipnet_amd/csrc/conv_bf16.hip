@@ -42,7 +42,6 @@ using CfgN64 = Cfg<4, 1, 2, 2, 32, 4>; // 256 x 64 (N = 64 layers), BK 32 x 4 st
 // over 64-deep x 2 on the ResNet50 shapes, profiles/r01/conv_bf16_tiles.log).  Every tile the
 // automatic choice can pick walks K in the same 32-deep steps, so the MFMA accumulation order
 // -- and therefore every bf16 rounding -- of a pixel does not depend on the batch it is in.
-// Mirrored by kernels.py:bf16_conv_tile.
 // N >= 256 layers run the ping-pong 16x16x32 kernel (tile 5) at every batch size -- the
 // choice depends on the layer only, never on M, so per-pixel results stay batch-invariant.
 int conv_variant(int M, int N, bool pp_ok, bool s3 = false, int Kv = 0) {
@@ -106,8 +105,8 @@ int halo_nb(int N) { return N >= 256 ? 4 : (N >= 128 ? 2 : 1); }
 constexpr int PP_RB = 8;
 
 // The tile a launch takes (requested tile v >= 0 validated, v < 0 = the automatic choice), or -1
-// when the requested tile cannot run this conv.  The ONE tile rule: launch_conv dispatches on it
-// and pipnet_conv2d_nhwc_bf16_plan exports it, so profiling labels never mirror it in Python.
+// when the requested tile cannot run this conv.  The ONE tile rule: launch_conv and the label queries
+// select on it and pipnet_conv2d_nhwc_bf16_plan exports it.
 template <int ALOAD>
 int plan_conv(const ConvParams& p, int epi, int v) {
   const bool pp_ok = (ALOAD == ALOAD_DENSE || p.Cin % 32 == 0) && p.K % 32 == 0;
@@ -125,164 +124,89 @@ int plan_conv(const ConvParams& p, int epi, int v) {
   return v;
 }
 
+using ConvRef = pipnet::KernelRef<ConvParams>;
+#define PIPNET_BF16_EPIS PIPNET_EPI_NONE, PIPNET_EPI_BIAS, PIPNET_EPI_BIAS_RELU, PIPNET_EPI_BIAS_RESID_RELU
+#define PIPNET_S3_EPIS PIPNET_EPI_S3_GELU, PIPNET_EPI_F32_BIAS, PIPNET_EPI_F32_RESID
+
+// What a launch of requested tile v runs: v becomes plan_conv's answer, the result its instantiation for
+// epilogue epi -- empty when the tile cannot run this conv or has none for epi.
+template <int ALOAD>
+ConvRef select_conv(const ConvParams& p, int epi, int& v) {
+  using pipnet::for_value;
+  v = plan_conv<ALOAD>(p, epi, v);
+  if (v < 0) return {};
+  if (v == 11)                                   // Cin = N = 64 / 128 3x3 on the LDS input halo
+    return for_value<ConvRef, PIPNET_BF16_EPIS>(epi, [&](auto e) -> ConvRef {
+      constexpr int E = decltype(e)::value;
+      if (p.N == 64) return PIPNET_KREF(pipnet_bf16::conv3x3_bf16_hsmall_kernel, 64, E);
+      return PIPNET_KREF(pipnet_bf16::conv3x3_bf16_hsmall_kernel, 128, E);
+    });
+  if (v == 9)                                    // persistent 256 x 256 ping-pong (1x1, N % 256 == 0)
+    return for_value<ConvRef, PIPNET_BF16_EPIS, PIPNET_EPI_DUAL_BIAS_RELU>(epi, [](auto e) -> ConvRef {
+      return PIPNET_KREF(pipnet_bf16::conv_bf16_ppp_kernel, decltype(e)::value, PP_RB);
+    });
+  if (epi == PIPNET_EPI_DUAL_BIAS_RELU) return {};   // persistent 1x1 tile only
+  if (v == 8)                                    // ping-pong with the LDS input halo, 256 x 64 NB
+    return for_value<ConvRef, PIPNET_BF16_EPIS>(epi, [&](auto e) -> ConvRef {
+      constexpr int E = decltype(e)::value;
+      if (halo_nb(p.N) != 4) return {};
+      return PIPNET_KREF(pipnet_bf16::conv3x3_bf16_halo_kernel, E, 4, PP_RB);
+    });
+  if (v == 7)                                    // 256 x 192 ping-pong (split epilogues only)
+    return for_value<ConvRef, PIPNET_S3_EPIS>(epi, [](auto e) -> ConvRef {
+      return PIPNET_KREF(pipnet_bf16::conv_bf16_pp_kernel, decltype(e)::value, ALOAD, 3, 0, 2);
+    });
+  if (v == 5)
+    return for_value<ConvRef, PIPNET_BF16_EPIS, PIPNET_S3_EPIS>(epi, [](auto e) -> ConvRef {
+      return PIPNET_KREF(pipnet_bf16::conv_bf16_pp_kernel, decltype(e)::value, ALOAD, 4, 0, 2);
+    });
+  if (is_s3_epi(epi))     // split-bf16 epilogues: only the tiles the automatic choice picks for N < 256 (0 and 4)
+    return for_value<ConvRef, PIPNET_S3_EPIS>(epi, [&](auto e) -> ConvRef {
+      constexpr int E = decltype(e)::value;
+      if (v == 4 && p.N % 128) return PIPNET_KREF_T(pipnet_bf16::conv_bf16_kernel, CfgM4, E, ALOAD, 2, true);
+      if (v == 4) return PIPNET_KREF_T(pipnet_bf16::conv_bf16_kernel, CfgM4, E, ALOAD, 2, false);
+      if (v == 0) return PIPNET_KREF_T(pipnet_bf16::conv_bf16_kernel, CfgS, E, ALOAD, 3, false);
+      return {};
+    });
+  return for_value<ConvRef, PIPNET_BF16_EPIS>(epi, [&](auto e) -> ConvRef {
+    constexpr int E = decltype(e)::value;
+    if (v == 2) return PIPNET_KREF_T(pipnet_bf16::conv_bf16_kernel, CfgL, E, ALOAD, 1, false);
+    if (v == 3) return PIPNET_KREF_T(pipnet_bf16::conv_bf16_kernel, CfgL4, E, ALOAD, 1, false);
+    if (v == 4) return PIPNET_KREF_T(pipnet_bf16::conv_bf16_kernel, CfgM4, E, ALOAD, 2, false);
+    if (v == 6) return PIPNET_KREF_T(pipnet_bf16::conv_bf16_kernel, CfgN64, E, ALOAD, 2, false);
+    if (v == 1) return PIPNET_KREF_T(pipnet_bf16::conv_bf16_kernel, CfgM, E, ALOAD, 2, false);
+    return PIPNET_KREF_T(pipnet_bf16::conv_bf16_kernel, CfgS, E, ALOAD, 3, false);
+  });
+}
+#undef PIPNET_BF16_EPIS
+#undef PIPNET_S3_EPIS
+
+// rows, columns and threads of tile v's workgroup
+struct TileGeo { int bm, bn, threads; };
+TileGeo tile_geo(const ConvParams& p, int v) {
+  switch (v) {
+    case 11: return {p.N == 64 ? hsm::Shape<64>::BM : hsm::Shape<128>::BM, p.N, 256};
+    case 9: return {32 * PP_RB, 256, 512};
+    case 8: return {32 * PP_RB, 64 * halo_nb(p.N), 512};
+    case 7: return {256, 192, 512};
+    case 5: case 2: case 3: return {256, 256, 512};
+    case 6: return {256, 64, 256};
+    case 0: return {64, 128, 256};
+    default: return {128, 128, 256};       // 1, 4
+  }
+}
+
 template <int ALOAD>
 int launch_conv(ConvParams& p, int epi, int v, hipStream_t s) {
-  v = plan_conv<ALOAD>(p, epi, v);
-  if (v < 0) return PIPNET_ERR_ARG;
-  if (v == 11) {                                 // Cin = N = 64 / 128 3x3 on the LDS input halo
-    const int bm = p.N == 64 ? hsm::Shape<64>::BM : hsm::Shape<128>::BM;
-    p.nt = 1;
-    p.mt = (p.M + bm - 1) / bm;
-    const dim3 grid(p.mt);
-#define PIPNET_HSM(CIN)                                                                                  \
-    switch (epi) {                                                                                       \
-      case PIPNET_EPI_NONE: hipLaunchKernelGGL((conv3x3_bf16_hsmall_kernel<CIN, PIPNET_EPI_NONE>), grid, dim3(256), 0, s, p); break; \
-      case PIPNET_EPI_BIAS: hipLaunchKernelGGL((conv3x3_bf16_hsmall_kernel<CIN, PIPNET_EPI_BIAS>), grid, dim3(256), 0, s, p); break; \
-      case PIPNET_EPI_BIAS_RELU:                                                                         \
-        hipLaunchKernelGGL((conv3x3_bf16_hsmall_kernel<CIN, PIPNET_EPI_BIAS_RELU>), grid, dim3(256), 0, s, p); \
-        break;                                                                                           \
-      case PIPNET_EPI_BIAS_RESID_RELU:                                                                   \
-        hipLaunchKernelGGL((conv3x3_bf16_hsmall_kernel<CIN, PIPNET_EPI_BIAS_RESID_RELU>), grid, dim3(256), 0, s, p); \
-        break;                                                                                           \
-      default: return PIPNET_ERR_ARG;                                                                    \
-    }
-    if (p.N == 64) {
-      PIPNET_HSM(64)
-    } else {
-      PIPNET_HSM(128)
-    }
-#undef PIPNET_HSM
-    PIPNET_CHECK_LAUNCH();
-    return PIPNET_OK;
-  }
-  if (v == 9) {                                  // persistent 256 x 256 ping-pong (1x1, N % 256 == 0)
-    p.nt = p.N / 256;
-    p.mt = (p.M + 32 * PP_RB - 1) / (32 * PP_RB);
-    p.group_m = choose_group_m(p.K);
-    const int ntiles = p.mt * p.nt;
-    const dim3 grid(ntiles < num_cus() ? ntiles : num_cus());
-#define PIPNET_PPP(E)                                                                                  \
-  case E:                                                                                               \
-    hipLaunchKernelGGL((conv_bf16_ppp_kernel<E, PP_RB>), grid, dim3(512), 0, s, p);                   \
-    break;
-    switch (epi) {
-      PIPNET_PPP(PIPNET_EPI_NONE)
-      PIPNET_PPP(PIPNET_EPI_BIAS)
-      PIPNET_PPP(PIPNET_EPI_BIAS_RELU)
-      PIPNET_PPP(PIPNET_EPI_BIAS_RESID_RELU)
-      PIPNET_PPP(PIPNET_EPI_DUAL_BIAS_RELU)
-      default: return PIPNET_ERR_ARG;
-    }
-#undef PIPNET_PPP
-    PIPNET_CHECK_LAUNCH();
-    return PIPNET_OK;
-  }
-  if (epi == PIPNET_EPI_DUAL_BIAS_RELU) return PIPNET_ERR_ARG;   // persistent 1x1 tile only
-  if (v == 8) {                                  // ping-pong with the LDS input halo, 256 x 64 NB
-    const int nb = halo_nb(p.N);
-    p.nt = (p.N + 64 * nb - 1) / (64 * nb);
-    p.mt = (p.M + 32 * PP_RB - 1) / (32 * PP_RB);
-    p.group_m = choose_group_m(p.K);
-    const dim3 grid(p.mt * p.nt);
-#define PIPNET_HALO(E)                                                                                \
-  case E:                                                                                              \
-    if (nb == 4) hipLaunchKernelGGL((conv3x3_bf16_halo_kernel<E, 4, PP_RB>), grid, dim3(512), 0, s, p); \
-    else return PIPNET_ERR_ARG;                                                                        \
-    break;
-    switch (epi) {
-      PIPNET_HALO(PIPNET_EPI_NONE)
-      PIPNET_HALO(PIPNET_EPI_BIAS)
-      PIPNET_HALO(PIPNET_EPI_BIAS_RELU)
-      PIPNET_HALO(PIPNET_EPI_BIAS_RESID_RELU)
-      default: return PIPNET_ERR_ARG;
-    }
-#undef PIPNET_HALO
-    PIPNET_CHECK_LAUNCH();
-    return PIPNET_OK;
-  }
-  if (v == 7) {                                  // 256 x 192 ping-pong (split epilogues only)
-    p.nt = (p.N + 191) / 192;
-    p.mt = (p.M + 255) / 256;
-    p.group_m = choose_group_m(p.K);
-    const dim3 grid(p.mt * p.nt);
-    switch (epi) {
-      case PIPNET_EPI_S3_GELU:
-        hipLaunchKernelGGL((conv_bf16_pp_kernel<PIPNET_EPI_S3_GELU, ALOAD, 3>), grid, dim3(512), 0, s, p);
-        break;
-      case PIPNET_EPI_F32_BIAS:
-        hipLaunchKernelGGL((conv_bf16_pp_kernel<PIPNET_EPI_F32_BIAS, ALOAD, 3>), grid, dim3(512), 0, s, p);
-        break;
-      case PIPNET_EPI_F32_RESID:
-        hipLaunchKernelGGL((conv_bf16_pp_kernel<PIPNET_EPI_F32_RESID, ALOAD, 3>), grid, dim3(512), 0, s, p);
-        break;
-      default: return PIPNET_ERR_ARG;
-    }
-    PIPNET_CHECK_LAUNCH();
-    return PIPNET_OK;
-  }
-  if (v == 5) {
-    p.nt = (p.N + 255) / 256;
-    p.mt = (p.M + 255) / 256;
-    p.group_m = choose_group_m(p.K);
-    const dim3 grid(p.mt * p.nt);
-    switch (epi) {
-      case PIPNET_EPI_NONE: hipLaunchKernelGGL((conv_bf16_pp_kernel<PIPNET_EPI_NONE, ALOAD>), grid, dim3(512), 0, s, p); break;
-      case PIPNET_EPI_BIAS: hipLaunchKernelGGL((conv_bf16_pp_kernel<PIPNET_EPI_BIAS, ALOAD>), grid, dim3(512), 0, s, p); break;
-      case PIPNET_EPI_BIAS_RELU:
-        hipLaunchKernelGGL((conv_bf16_pp_kernel<PIPNET_EPI_BIAS_RELU, ALOAD>), grid, dim3(512), 0, s, p);
-        break;
-      case PIPNET_EPI_BIAS_RESID_RELU:
-        hipLaunchKernelGGL((conv_bf16_pp_kernel<PIPNET_EPI_BIAS_RESID_RELU, ALOAD>), grid, dim3(512), 0, s, p);
-        break;
-      case PIPNET_EPI_S3_GELU:
-        hipLaunchKernelGGL((conv_bf16_pp_kernel<PIPNET_EPI_S3_GELU, ALOAD>), grid, dim3(512), 0, s, p);
-        break;
-      case PIPNET_EPI_F32_BIAS:
-        hipLaunchKernelGGL((conv_bf16_pp_kernel<PIPNET_EPI_F32_BIAS, ALOAD>), grid, dim3(512), 0, s, p);
-        break;
-      case PIPNET_EPI_F32_RESID:
-        hipLaunchKernelGGL((conv_bf16_pp_kernel<PIPNET_EPI_F32_RESID, ALOAD>), grid, dim3(512), 0, s, p);
-        break;
-      default: return PIPNET_ERR_ARG;
-    }
-    PIPNET_CHECK_LAUNCH();
-    return PIPNET_OK;
-  }
-  const int bm = (v == 2 || v == 3 || v == 6) ? 256 : (v == 0 ? 64 : 128),
-            bn = (v == 2 || v == 3) ? 256 : (v == 6 ? 64 : 128);
-  p.nt = (p.N + bn - 1) / bn;
-  p.mt = (p.M + bm - 1) / bm;
+  const ConvRef k = select_conv<ALOAD>(p, epi, v);
+  if (!k.fn) return PIPNET_ERR_ARG;
+  const TileGeo g = tile_geo(p, v);
+  p.nt = (p.N + g.bn - 1) / g.bn;
+  p.mt = (p.M + g.bm - 1) / g.bm;
   p.group_m = choose_group_m(p.K);
-  const dim3 grid(p.mt * p.nt);
-#define PIPNET_BF_CASE(E)                                                                            \
-  case E:                                                                                           \
-    if (v == 2) hipLaunchKernelGGL((conv_bf16_kernel<CfgL, E, ALOAD, 1>), grid, dim3(512), 0, s, p);  \
-    else if (v == 3) hipLaunchKernelGGL((conv_bf16_kernel<CfgL4, E, ALOAD, 1>), grid, dim3(512), 0, s, p); \
-    else if (v == 4) hipLaunchKernelGGL((conv_bf16_kernel<CfgM4, E, ALOAD, 2>), grid, dim3(256), 0, s, p); \
-    else if (v == 6) hipLaunchKernelGGL((conv_bf16_kernel<CfgN64, E, ALOAD, 2>), grid, dim3(256), 0, s, p); \
-    else if (v == 1) hipLaunchKernelGGL((conv_bf16_kernel<CfgM, E, ALOAD, 2>), grid, dim3(256), 0, s, p); \
-    else hipLaunchKernelGGL((conv_bf16_kernel<CfgS, E, ALOAD, 3>), grid, dim3(256), 0, s, p);        \
-    break;
-  // split-bf16 epilogues: only the tiles the automatic choice picks for N < 256 (0 and 4)
-#define PIPNET_S3_CASE(E)                                                                            \
-  case E:                                                                                           \
-    if (v == 4 && p.N % 128) hipLaunchKernelGGL((conv_bf16_kernel<CfgM4, E, ALOAD, 2, true>), grid, dim3(256), 0, s, p); \
-    else if (v == 4) hipLaunchKernelGGL((conv_bf16_kernel<CfgM4, E, ALOAD, 2>), grid, dim3(256), 0, s, p); \
-    else if (v == 0) hipLaunchKernelGGL((conv_bf16_kernel<CfgS, E, ALOAD, 3>), grid, dim3(256), 0, s, p); \
-    else return PIPNET_ERR_ARG;                                                                     \
-    break;
-  switch (epi) {
-    PIPNET_S3_CASE(PIPNET_EPI_S3_GELU)
-    PIPNET_S3_CASE(PIPNET_EPI_F32_BIAS)
-    PIPNET_S3_CASE(PIPNET_EPI_F32_RESID)
-    PIPNET_BF_CASE(PIPNET_EPI_NONE)
-    PIPNET_BF_CASE(PIPNET_EPI_BIAS)
-    PIPNET_BF_CASE(PIPNET_EPI_BIAS_RELU)
-    PIPNET_BF_CASE(PIPNET_EPI_BIAS_RESID_RELU)
-    default: return PIPNET_ERR_ARG;
-  }
-#undef PIPNET_BF_CASE
-#undef PIPNET_S3_CASE
+  int wgs = p.mt * p.nt;
+  if (v == 9 && wgs > num_cus()) wgs = num_cus();     // persistent: at most one workgroup per CU
+  hipLaunchKernelGGL(k.fn, dim3(wgs), dim3(g.threads), 0, s, p);
   PIPNET_CHECK_LAUNCH();
   return PIPNET_OK;
 }
@@ -393,6 +317,45 @@ int conv_bf16_shape(ConvParams& p, bool& dense, int B, int H, int W, int Cin, in
   return PIPNET_OK;
 }
 
+// The same for pipnet_conv1x1_bf16_dual: M pixels, N1 + N2 columns on the persistent tile (9).
+int conv_dual_shape(ConvParams& p, int64_t M, int Cin, int N1, int N2) {
+  if (M < 0 || M >= ((int64_t)1 << 31) || Cin <= 0 || (Cin & 7) || N1 <= 0 || N2 <= 0 || (N1 % 256) || (N2 % 256))
+    return PIPNET_ERR_ARG;
+  p.lda = Cin;
+  p.ldc = N1;
+  p.ldc2 = N2;
+  p.nsplit = N1;
+  p.M = (int)M; p.N = N1 + N2;
+  p.Kv = Cin;
+  p.K = (Cin + KPAD - 1) / KPAD * KPAD;
+  p.H = (int)M; p.Wd = 1; p.Cin = Cin; p.OH = (int)M; p.OW = 1; p.stride = 1; p.KW = 1; p.pad = 0;
+  p.Cinp = Cin;
+  return PIPNET_OK;
+}
+
+// The same for pipnet_conv2d_nhwc_s3 (Cin = the fp32 channels; ldc is the caller's: it depends on the output form).
+int conv_s3_shape(ConvParams& p, bool& dense, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
+                  int pad, int epilogue, int tile) {
+  if (B < 0 || H <= 0 || W <= 0 || Cin <= 0 || (Cin % 32) || Cout <= 0 || (Cout & 7) || KH <= 0 || KW <= 0 ||
+      stride <= 0 || pad < 0)
+    return PIPNET_ERR_ARG;
+  if (!is_s3_epi(epilogue)) return PIPNET_ERR_ARG;
+  if (tile != -1 && tile != 0 && tile != 4 && tile != 5 && tile != 7) return PIPNET_ERR_ARG;
+  const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
+  if (OH <= 0 || OW <= 0) return PIPNET_ERR_ARG;
+  if ((int64_t)B * OH * OW >= (int64_t)1 << 31) return PIPNET_ERR_ARG;
+  p.ldr = Cout;
+  p.M = B * OH * OW; p.N = Cout;
+  p.Kv = KH * KW * 3 * Cin;
+  p.K = (p.Kv + 31) / 32 * 32;                 // the split tiles (0, 4, 5) all walk K in 32-deep steps
+  p.H = H; p.Wd = W; p.Cin = 3 * Cin; p.OH = OH; p.OW = OW; p.stride = stride; p.KW = KW; p.pad = pad;
+  p.Cinp = 2 * Cin;
+  p.seg = Cin;
+  dense = KH == 1 && KW == 1 && stride == 1 && pad == 0;
+  if (dense) p.lda = 2 * Cin;
+  return PIPNET_OK;
+}
+
 }  // namespace
 
 extern "C" int pipnet_conv2d_nhwc_bf16_tile(const void* x, int B, int H, int W, int Cin, const void* w_packed,
@@ -424,6 +387,15 @@ extern "C" int pipnet_conv2d_nhwc_bf16_plan(int B, int H, int W, int Cin, int Co
   return v < 0 ? -PIPNET_ERR_ARG : v;
 }
 
+extern "C" int pipnet_conv2d_nhwc_bf16_label(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
+                                             int pad, int epilogue, int tile, char* buf, int cap) {
+  ConvParams p{};
+  bool dense = false;
+  if (conv_bf16_shape(p, dense, B, H, W, Cin, Cout, KH, KW, stride, pad, epilogue)) return -PIPNET_ERR_ARG;
+  return pipnet::write_label(dense ? select_conv<ALOAD_DENSE>(p, epilogue, tile)
+                                   : select_conv<ALOAD_CONV>(p, epilogue, tile), buf, cap);
+}
+
 extern "C" int pipnet_conv2d_nhwc_bf16(const void* x, int B, int H, int W, int Cin, const void* w_packed,
                                        const float* bias, int Cout, int KH, int KW, int stride, int pad,
                                        const void* R, int epilogue, void* y, void* stream) {
@@ -433,28 +405,24 @@ extern "C" int pipnet_conv2d_nhwc_bf16(const void* x, int B, int H, int W, int C
 
 extern "C" int pipnet_conv1x1_bf16_dual(const void* x, int64_t M, int Cin, const void* w_packed, const float* bias,
                                         int N1, void* y1, int N2, void* y2, void* stream) {
-  if (M < 0 || M >= ((int64_t)1 << 31) || Cin <= 0 || (Cin & 7) || N1 <= 0 || N2 <= 0 || (N1 % 256) || (N2 % 256) ||
-      !x || !w_packed || !y1 || !y2)
-    return PIPNET_ERR_ARG;
+  ConvParams p{};
+  if (conv_dual_shape(p, M, Cin, N1, N2) || !x || !w_packed || !y1 || !y2) return PIPNET_ERR_ARG;
   if (!aligned16(x) || !aligned16(w_packed) || !aligned16(y1) || !aligned16(y2) || (bias && !aligned16(bias)))
     return PIPNET_ERR_ALIGN;
   if (M == 0) return PIPNET_OK;
-  ConvParams p{};
   p.A = reinterpret_cast<const bf16*>(x);
-  p.lda = Cin;
   p.W = reinterpret_cast<const bf16*>(w_packed);
   p.bias = bias;
   p.C = reinterpret_cast<bf16*>(y1);
-  p.ldc = N1;
   p.C2 = reinterpret_cast<bf16*>(y2);
-  p.ldc2 = N2;
-  p.nsplit = N1;
-  p.M = (int)M; p.N = N1 + N2;
-  p.Kv = Cin;
-  p.K = (Cin + KPAD - 1) / KPAD * KPAD;
-  p.H = (int)M; p.Wd = 1; p.Cin = Cin; p.OH = (int)M; p.OW = 1; p.stride = 1; p.KW = 1; p.pad = 0;
-  p.Cinp = Cin;
   return launch_conv<ALOAD_DENSE>(p, PIPNET_EPI_DUAL_BIAS_RELU, 9, (hipStream_t)stream);
+}
+
+extern "C" int pipnet_conv1x1_bf16_dual_label(int64_t M, int Cin, int N1, int N2, char* buf, int cap) {
+  ConvParams p{};
+  int tile = 9;
+  if (conv_dual_shape(p, M, Cin, N1, N2)) return -PIPNET_ERR_ARG;
+  return pipnet::write_label(select_conv<ALOAD_DENSE>(p, PIPNET_EPI_DUAL_BIAS_RELU, tile), buf, cap);
 }
 
 extern "C" int pipnet_nchw_to_nhwc_bf16(const float* x, int B, int C, int H, int W, int Cpad, void* y,
@@ -519,27 +487,20 @@ extern "C" int pipnet_maxpool2d_nhwc_bf16(const void* x, int B, int H, int W, in
 extern "C" int pipnet_conv2d_nhwc_s3(const void* x, int B, int H, int W, int Cin, const void* w_packed,
                                      const float* bias, const float* scale, const float* R, int Cout, int KH, int KW,
                                      int stride, int pad, int epilogue, void* y, int tile, void* stream) {
-  if (B < 0 || H <= 0 || W <= 0 || Cin <= 0 || (Cin % 32) || Cout <= 0 || (Cout & 7) || KH <= 0 || KW <= 0 ||
-      stride <= 0 || pad < 0)
-    return PIPNET_ERR_ARG;
-  if (!is_s3_epi(epilogue)) return PIPNET_ERR_ARG;
+  ConvParams p{};
+  bool dense = false;
+  if (const int st = conv_s3_shape(p, dense, B, H, W, Cin, Cout, KH, KW, stride, pad, epilogue, tile)) return st;
   if (epilogue == PIPNET_EPI_F32_RESID && (!R || !scale)) return PIPNET_ERR_ARG;
-  if (tile != -1 && tile != 0 && tile != 4 && tile != 5 && tile != 7) return PIPNET_ERR_ARG;
   if (!x || !w_packed || !y) return PIPNET_ERR_ARG;
   if (!aligned16(x) || !aligned16(w_packed) || !aligned16(y) || (R && !aligned16(R)) || (bias && !aligned16(bias)) ||
       (scale && !aligned16(scale)))
     return PIPNET_ERR_ALIGN;
-  const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
-  if (OH <= 0 || OW <= 0) return PIPNET_ERR_ARG;
-  if ((int64_t)B * OH * OW >= (int64_t)1 << 31) return PIPNET_ERR_ARG;
   if (B == 0) return PIPNET_OK;
-  ConvParams p{};
   p.A = reinterpret_cast<const bf16*>(x);
   p.W = reinterpret_cast<const bf16*>(w_packed);
   p.bias = bias;
   p.scale = scale;
   p.R32 = R;
-  p.ldr = Cout;
   if (epilogue == PIPNET_EPI_S3_GELU) {
     p.C = reinterpret_cast<bf16*>(y);
     p.ldc = 2 * (int64_t)Cout;
@@ -547,15 +508,15 @@ extern "C" int pipnet_conv2d_nhwc_s3(const void* x, int B, int H, int W, int Cin
     p.Cf = reinterpret_cast<float*>(y);
     p.ldc = Cout;
   }
-  p.M = B * OH * OW; p.N = Cout;
-  p.Kv = KH * KW * 3 * Cin;
-  p.K = (p.Kv + 31) / 32 * 32;                 // the split tiles (0, 4, 5) all walk K in 32-deep steps
-  p.H = H; p.Wd = W; p.Cin = 3 * Cin; p.OH = OH; p.OW = OW; p.stride = stride; p.KW = KW; p.pad = pad;
-  p.Cinp = 2 * Cin;
-  p.seg = Cin;
-  if (KH == 1 && KW == 1 && stride == 1 && pad == 0) {
-    p.lda = 2 * Cin;
-    return launch_conv<ALOAD_DENSE>(p, epilogue, tile, (hipStream_t)stream);
-  }
-  return launch_conv<ALOAD_CONV>(p, epilogue, tile, (hipStream_t)stream);
+  return dense ? launch_conv<ALOAD_DENSE>(p, epilogue, tile, (hipStream_t)stream)
+               : launch_conv<ALOAD_CONV>(p, epilogue, tile, (hipStream_t)stream);
+}
+
+extern "C" int pipnet_conv2d_nhwc_s3_label(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                           int epilogue, int tile, char* buf, int cap) {
+  ConvParams p{};
+  bool dense = false;
+  if (conv_s3_shape(p, dense, B, H, W, Cin, Cout, KH, KW, stride, pad, epilogue, tile)) return -PIPNET_ERR_ARG;
+  return pipnet::write_label(dense ? select_conv<ALOAD_DENSE>(p, epilogue, tile)
+                                   : select_conv<ALOAD_CONV>(p, epilogue, tile), buf, cap);
 }

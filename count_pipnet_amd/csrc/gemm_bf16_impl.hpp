@@ -18,6 +18,7 @@
 // Requires Cin % 8 == 0 (a 16-B chunk never straddles two taps).
 #pragma once
 #include "common.hpp"
+#include "kernel_ref.hpp"
 
 namespace pipnet_bf16 {
 
@@ -144,6 +145,7 @@ struct Cfg {
   static_assert(KPAD % BK == 0, "packed K must be a multiple of BK");
   static_assert(A_DMA * ROWS_PER_DMA * NWAVES == BMT && B_DMA * ROWS_PER_DMA * NWAVES == BNT, "DMA split");
   static PIPNET_DEV int swz(int row, int c) { return BK == 64 ? (c ^ ((row >> 1) & 7)) : (c ^ ((row >> 2) & 3)); }
+  static std::string label() { return pipnet::kernel_label("pipnet_bf16::Cfg", {WGM, WGN, TM, TN, BK, NS}); }   // PIPNET_KREF_T
 };
 
 template <class C>

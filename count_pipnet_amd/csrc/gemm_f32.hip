@@ -1,5 +1,6 @@
 // Product instantiation of the fp32 MFMA GEMM (templates + design notes: gemm_f32_impl.hpp).
 #include "gemm_f32_impl.hpp"
+#include "kernel_ref.hpp"
 
 using namespace pipnet_gemm;
 
@@ -25,7 +26,7 @@ int choose_group_m(const GemmParams& p) {
 //   N = 384, K >= 768         BK=32, 192 x 384 tiles, 12 waves        (stage-3 fc2, round 6)
 // 0 = register-staged K-tail kernel, 1 = BK16x128 rows x3 stages, 2 = BK32x64 rows,
 // 3 = BK32x128 rows, 5 = BK32 192 x 384 wide tile on 12 waves (exported by pipnet_linear_f32_plan;
-// the profiling labels of count_pipnet_amd/kernels.py:gemm_kernel_name come from it).  An 8-wave 256 x 128 workgroup
+// select_gemm turns it into the kernel and its profiling label).  An 8-wave 256 x 128 workgroup
 // (gemm_f32_impl.hpp gemm_f32_tn8_kernel, tools/gemm_lab.hip 60+) beat variant 3 by 4-8 % on the
 // stage-4 shapes in the lab but not inside C2 (profiles/r06/gemm_tn8_ab.txt): not dispatched.
 // (PIPNET_AB_GEMM_RULE: build-time A/B hook for tools/ab_build.py, 0 in the product)
@@ -117,6 +118,38 @@ __global__ __launch_bounds__(256) void gelu_rows_kernel(float* C, int64_t ldc, i
   }
 }
 
+using GemmRef = pipnet::KernelRef<GemmParams>;
+
+// The instantiation of variant v (gemm_variant) for epilogue epi, and whether a gelu_rows_kernel pass
+// follows it.  BIAS_GELU on the scalar epilogue (the K-tail kernel, or N / ldc / a pointer not 16-byte
+// friendly): the fp32 evaluation of gelu_fast there was up to 1.4x outside the 1.4e-8 + 1.2e-7 |gelu| its
+// comment states (those are the fit's errors in exact arithmetic; tests/test_gpu_gemm_matrix.py
+// test_bias_gelu_exact_argument), so this fallback path stores A W^T + b and takes the GELU in a
+// second pass, in double.  The float4 epilogue (gelu_pk16) is untouched.
+template <int ALOAD>
+GemmRef select_gemm(const GemmParams& p, int epi, int v, bool* gelu_pass = nullptr) {
+  const bool second = epi == PIPNET_EPI_BIAS_GELU && (v == 0 || !p.vec_epi);
+  if (second) epi = PIPNET_EPI_BIAS;
+  if (gelu_pass) *gelu_pass = second;
+  return pipnet::for_value<GemmRef, PIPNET_EPI_NONE, PIPNET_EPI_BIAS, PIPNET_EPI_BIAS_GELU, PIPNET_EPI_RESID,
+                           PIPNET_EPI_MUL, PIPNET_EPI_BIAS_RELU, PIPNET_EPI_BIAS_RESID_RELU, PIPNET_EPI_RESID_ROWSCALE,
+                           PIPNET_EPI_GELU_BWD>(epi, [&](auto e) -> GemmRef {
+    constexpr int E = decltype(e)::value;
+    if constexpr (ALOAD != ALOAD_CONV && E != PIPNET_EPI_GELU_BWD)
+      if (v == 5) return PIPNET_KREF(pipnet_gemm::gemm_f32_tnw_kernel, E, ALOAD, 0);
+    if (v == 1) return PIPNET_KREF(pipnet_gemm::gemm_f32_tn_kernel, 16, 2, E, ALOAD, 2, 3, 0, false);
+    if (v == 2 && p.N % BN) return PIPNET_KREF(pipnet_gemm::gemm_f32_tn_kernel, 32, 1, E, ALOAD, 3, 2, 0, true);
+    if (v == 2) return PIPNET_KREF(pipnet_gemm::gemm_f32_tn_kernel, 32, 1, E, ALOAD, 3, 2, 0, false);
+    if (v == 3) return PIPNET_KREF(pipnet_gemm::gemm_f32_tn_kernel, 32, 2, E, ALOAD, 2, 2, 0, false);
+    return PIPNET_KREF(pipnet_gemm::gemm_f32_tn_ktail_kernel, E, ALOAD);
+  });
+}
+
+// the main kernel of both split-K entries: 64-row tiles, one K slab per blockIdx.y, raw sums to the workspace
+GemmRef select_splitk() {
+  return PIPNET_KREF(pipnet_gemm::gemm_f32_tn_kernel, 32, 1, PIPNET_EPI_NONE, ALOAD_DENSE, 3, 2, 0, false);
+}
+
 template <int ALOAD>
 int launch_gemm(GemmParams& p, int epi, hipStream_t s) {
   p.nt = (p.N + BN - 1) / BN;
@@ -126,13 +159,9 @@ int launch_gemm(GemmParams& p, int epi, hipStream_t s) {
               (!p.scale || aligned16(p.scale));
   const bool vec = aligned16(p.A) && aligned16(p.W) && (ALOAD != ALOAD_DENSE || (p.lda & 3) == 0);
   const int v = gemm_variant(p.M, p.N, p.K, vec, epi, ALOAD, p.vec_epi);
-  // BIAS_GELU on the scalar epilogue (the K-tail kernel, or N / ldc / a pointer not 16-byte friendly):
-  // the fp32 evaluation of gelu_fast there was up to 1.4x outside the 1.4e-8 + 1.2e-7 |gelu| its comment
-  // states (those are the fit's errors in exact arithmetic; tests/test_gpu_gemm_matrix.py
-  // test_bias_gelu_exact_argument), so this fallback path stores A W^T + b and takes the GELU in a
-  // second pass, in double.  The float4 epilogue (gelu_pk16) is untouched.
-  const bool gelu_pass = epi == PIPNET_EPI_BIAS_GELU && (v == 0 || !p.vec_epi);
-  if (gelu_pass) epi = PIPNET_EPI_BIAS;
+  bool gelu_pass = false;
+  const GemmRef k = select_gemm<ALOAD>(p, epi, v, &gelu_pass);
+  if (!k.fn) return PIPNET_ERR_ARG;
   if (v == 5) {
     p.nt = p.N / 384;
     p.mt = (p.M + 191) / 192;
@@ -140,34 +169,7 @@ int launch_gemm(GemmParams& p, int epi, hipStream_t s) {
     p.mt = (p.M + (v == 2 ? 63 : 127)) / (v == 2 ? 64 : 128);
   }
   const dim3 grid(p.mt * p.nt), block(v == 5 ? 768 : NTHREADS);
-#define PIPNET_EPI_CASE(E)                                                                                 \
-  case E:                                                                                                 \
-    if constexpr (ALOAD != ALOAD_CONV && E != PIPNET_EPI_GELU_BWD) {                                      \
-      if (v == 5) {                                                                                       \
-        hipLaunchKernelGGL((gemm_f32_tnw_kernel<E, ALOAD>), grid, block, 0, s, p);                        \
-        break;                                                                                            \
-      }                                                                                                   \
-    }                                                                                                     \
-    if (v == 1) hipLaunchKernelGGL((gemm_f32_tn_kernel<16, 2, E, ALOAD, 2, 3>), grid, block, 0, s, p);    \
-    else if (v == 2 && p.N % BN) hipLaunchKernelGGL((gemm_f32_tn_kernel<32, 1, E, ALOAD, 3, 2, 0, true>), grid, \
-                                                   block, 0, s, p);                                         \
-    else if (v == 2) hipLaunchKernelGGL((gemm_f32_tn_kernel<32, 1, E, ALOAD, 3, 2>), grid, block, 0, s, p); \
-    else if (v == 3) hipLaunchKernelGGL((gemm_f32_tn_kernel<32, 2, E, ALOAD, 2, 2>), grid, block, 0, s, p); \
-    else hipLaunchKernelGGL((gemm_f32_tn_ktail_kernel<E, ALOAD>), grid, block, 0, s, p);                   \
-    break;
-  switch (epi) {
-    PIPNET_EPI_CASE(PIPNET_EPI_NONE)
-    PIPNET_EPI_CASE(PIPNET_EPI_BIAS)
-    PIPNET_EPI_CASE(PIPNET_EPI_BIAS_GELU)
-    PIPNET_EPI_CASE(PIPNET_EPI_RESID)
-    PIPNET_EPI_CASE(PIPNET_EPI_MUL)
-    PIPNET_EPI_CASE(PIPNET_EPI_BIAS_RELU)
-    PIPNET_EPI_CASE(PIPNET_EPI_BIAS_RESID_RELU)
-    PIPNET_EPI_CASE(PIPNET_EPI_RESID_ROWSCALE)
-    PIPNET_EPI_CASE(PIPNET_EPI_GELU_BWD)
-    default: return PIPNET_ERR_ARG;
-  }
-#undef PIPNET_EPI_CASE
+  hipLaunchKernelGGL(k.fn, grid, block, 0, s, p);
   PIPNET_CHECK_LAUNCH();
   if (gelu_pass) {
     const int64_t work = (int64_t)p.M * p.N;
@@ -186,6 +188,19 @@ extern "C" int pipnet_linear_f32_plan(int M, int N, int K, int epilogue, int alo
   if (M < 0 || N < 0 || K <= 0 || aload < ALOAD_DENSE || aload > ALOAD_CONV) return -PIPNET_ERR_ARG;
   if (epilogue < PIPNET_EPI_NONE || epilogue > PIPNET_EPI_GELU_BWD) return -PIPNET_ERR_ARG;
   return gemm_variant(M, N, K, true, epilogue, aload, N % 4 == 0);
+}
+
+// The label of the kernel that plan launches (select_gemm on the same assumptions); splits > 1: the main
+// kernel of pipnet_linear_splitk_f32 / pipnet_linear_pair_mul_f32.
+extern "C" int pipnet_linear_f32_label(int M, int N, int K, int epilogue, int aload, int splits, char* buf, int cap) {
+  const int v = pipnet_linear_f32_plan(M, N, K, epilogue, aload);
+  if (v < 0) return v;
+  if (splits > 1) return pipnet::write_label(select_splitk(), buf, cap);
+  GemmParams p{};
+  p.M = M; p.N = N; p.K = K;
+  p.vec_epi = N % 4 == 0;
+  return pipnet::write_label(pipnet::for_value<GemmRef, ALOAD_DENSE, ALOAD_CONV2X2, ALOAD_CONV>(aload, [&](auto a) {
+    return select_gemm<decltype(a)::value>(p, epilogue, v); }), buf, cap);
 }
 
 extern "C" int pipnet_linear_f32(const float* A, int64_t lda, const float* W, const float* bias,
@@ -283,7 +298,7 @@ extern "C" int pipnet_linear_pair_mul_f32(const float* A, int64_t lda, const flo
   p.vec_epi = 1;
   p.split_stride = (int64_t)M * p.N;
   const dim3 grid(p.mt * p.nt, splits);
-  hipLaunchKernelGGL((gemm_f32_tn_kernel<32, 1, PIPNET_EPI_NONE, ALOAD_DENSE, 3, 2>), grid, dim3(NTHREADS), 0, s, p);
+  hipLaunchKernelGGL(select_splitk().fn, grid, dim3(NTHREADS), 0, s, p);
   PIPNET_CHECK_LAUNCH();
   const int64_t work = (int64_t)M * (Nh / 4);
   const int blocks = (int)((work + 255) / 256 < 4096 ? (work + 255) / 256 : 4096);
@@ -320,7 +335,7 @@ extern "C" int pipnet_linear_splitk_f32(const float* A, int64_t lda, const float
   p.vec_epi = 1;
   p.split_stride = (int64_t)M * N;
   const dim3 grid(p.mt * p.nt, splits);
-  hipLaunchKernelGGL((gemm_f32_tn_kernel<32, 1, PIPNET_EPI_NONE, ALOAD_DENSE, 3, 2>), grid, dim3(NTHREADS), 0, s, p);
+  hipLaunchKernelGGL(select_splitk().fn, grid, dim3(NTHREADS), 0, s, p);
   PIPNET_CHECK_LAUNCH();
   const int64_t work = (int64_t)M * (N / 4);
   const int blocks = (int)((work + 255) / 256 < 4096 ? (work + 255) / 256 : 4096);

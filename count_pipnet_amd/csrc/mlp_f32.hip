@@ -26,6 +26,7 @@
 // as two chains over even / odd g summed at the end -- a different (equally exact) fp32 summation
 // order than the unfused GEMMs.
 #include "common.hpp"
+#include "kernel_ref.hpp"
 
 namespace {
 
@@ -362,31 +363,41 @@ constexpr int MLP_HS2_MAX_HW = 256;
 // 101 KiB of LDS, one 4-wave workgroup (one wave per SIMD) per CU: C2's 25,088-pixel stage-2
 // half batch 198.6 -> 162.2 us on (16, 8), C5-sized 16,384 px 101.6 -> 99.4 on (16, 4).  Small M
 // (C1: 16 images of 64^2) gets smaller workgroups so that the grid still covers the CUs.
-// Plan code = HC * 100 + NW * 10 + HS (the instantiation cnblock_mlp_kernel<C, HC, NW, 1, HS>).
-int mlp_plan(int m, int C, int hw) {
+// One row per case: the instantiation cnblock_mlp_kernel<C, HC, NW, 1, HS>, its label and its launch shape.
+namespace {
+struct MlpSel {
+  pipnet::KernelRef<const float*, const float*, const float*, const float*, const float*, const float*, float*, int> k;
+  int px, threads;      // pixels per workgroup, threads per workgroup
+};
+#define PIPNET_MLP(C, HC, NW, HS) MlpSel{PIPNET_KREF(cnblock_mlp_kernel, C, HC, NW, 1, HS), 16 * (NW) / (HS), 64 * (NW)}
+MlpSel select_mlp(int64_t M, int C, int hw) {
+  if (M < 0 || M >= ((int64_t)1 << 31) || (C != 96 && C != 192) || hw < 0) return {};
+  const int m = (int)M;
   if (C == 96) {
-    if (m >= 98304) return 3241;       // C2 stage 1
-    if (m >= 65536) return 3281;       // C5 stage 1
-    if (m >= 16384) return 3241;
-    if (m >= 8192) return 3221;
-    return 3211;
+    if (m >= 98304) return PIPNET_MLP(96, 32, 4, 1);       // C2 stage 1
+    if (m >= 65536) return PIPNET_MLP(96, 32, 8, 1);       // C5 stage 1
+    if (m >= 16384) return PIPNET_MLP(96, 32, 4, 1);
+    if (m >= 8192) return PIPNET_MLP(96, 32, 2, 1);
+    return PIPNET_MLP(96, 32, 1, 1);
   }
-  if (hw > 0 && hw <= MLP_HS2_MAX_HW) return 1682;   // C5 stage 2
-  if (m >= 24576) return 1681;         // C2 stage 2
-  if (m >= 8192) return 1641;
-  if (m >= 4096) return 3221;
-  return 3211;
+  if (hw > 0 && hw <= MLP_HS2_MAX_HW) return PIPNET_MLP(192, 16, 8, 2);   // C5 stage 2
+  if (m >= 24576) return PIPNET_MLP(192, 16, 8, 1);        // C2 stage 2
+  if (m >= 8192) return PIPNET_MLP(192, 16, 4, 1);
+  if (m >= 4096) return PIPNET_MLP(192, 32, 2, 1);
+  return PIPNET_MLP(192, 32, 1, 1);
 }
+#undef PIPNET_MLP
+}  // namespace
 
-extern "C" int pipnet_cnblock_mlp_plan(int64_t M, int C, int hw) {
-  if (M < 0 || M >= ((int64_t)1 << 31) || (C != 96 && C != 192) || hw < 0) return -PIPNET_ERR_ARG;
-  return mlp_plan((int)M, C, hw);
+extern "C" int pipnet_cnblock_mlp_label(int64_t M, int C, int hw, char* buf, int cap) {
+  return pipnet::write_label(select_mlp(M, C, hw).k, buf, cap);
 }
 
 extern "C" int pipnet_cnblock_mlp_hw_f32(const float* t, const float* W1, const float* b1, const float* W2,
                                          const float* b2, const float* gamma, float* x, int64_t M, int C, int hw,
                                          void* stream) {
-  if (M < 0 || M >= ((int64_t)1 << 31) || (C != 96 && C != 192) || hw < 0) return PIPNET_ERR_ARG;
+  const MlpSel sel = select_mlp(M, C, hw);
+  if (!sel.k.fn) return PIPNET_ERR_ARG;
   if (!t || !W1 || !b1 || !W2 || !b2 || !gamma || !x) return PIPNET_ERR_ARG;
   if (!aligned16(t) || !aligned16(W1) || !aligned16(b1) || !aligned16(W2) || !aligned16(b2) || !aligned16(gamma) ||
       !aligned16(x))
@@ -397,18 +408,9 @@ extern "C" int pipnet_cnblock_mlp_hw_f32(const float* t, const float* W1, const 
   if (pipnet_mlp_lab_variant(C, t, W1, b1, W2, b2, gamma, x, (int)M, s)) return PIPNET_OK;
 #endif
   const int m = (int)M;
-  switch (C * 10000 + mlp_plan(m, C, hw)) {
-    case 963241: return launch_mlp<96, 32, 4, 1>(t, W1, b1, W2, b2, gamma, x, m, s);
-    case 963281: return launch_mlp<96, 32, 8, 1>(t, W1, b1, W2, b2, gamma, x, m, s);
-    case 963221: return launch_mlp<96, 32, 2, 1>(t, W1, b1, W2, b2, gamma, x, m, s);
-    case 963211: return launch_mlp<96, 32, 1, 1>(t, W1, b1, W2, b2, gamma, x, m, s);
-    case 1921682: return launch_mlp<192, 16, 8, 1, 2>(t, W1, b1, W2, b2, gamma, x, m, s);
-    case 1921681: return launch_mlp<192, 16, 8, 1>(t, W1, b1, W2, b2, gamma, x, m, s);
-    case 1921641: return launch_mlp<192, 16, 4, 1>(t, W1, b1, W2, b2, gamma, x, m, s);
-    case 1923221: return launch_mlp<192, 32, 2, 1>(t, W1, b1, W2, b2, gamma, x, m, s);
-    case 1923211: return launch_mlp<192, 32, 1, 1>(t, W1, b1, W2, b2, gamma, x, m, s);
-    default: return PIPNET_ERR_ARG;
-  }
+  hipLaunchKernelGGL(sel.k.fn, dim3((m + sel.px - 1) / sel.px), dim3(sel.threads), 0, s, t, W1, b1, W2, b2, gamma, x, m);
+  PIPNET_CHECK_LAUNCH();
+  return PIPNET_OK;
 }
 
 // map size unknown: the HS = 1 instantiations only

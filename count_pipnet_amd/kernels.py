@@ -48,22 +48,11 @@ def gemm_variant(m: int, n: int, k: int, epilogue: int = _lib.EPI_NONE, aload: i
     return v
 
 
-def gemm_kernel_name(m: int, n: int, k: int, epilogue: int, aload: int) -> str:
-    """The rocprof name of the GEMM instantiation the library picks (dense, unit-stride, 16-B
-    aligned torch operands -- so ``vec_epi`` holds whenever N % 4 == 0)."""
-    v = gemm_variant(m, n, k, epilogue, aload)
-    if epilogue == _lib.EPI_BIAS_GELU and (v == 0 or n % 4):
-        epilogue = _lib.EPI_BIAS        # scalar epilogue: bias in the GEMM, GELU in a second pass (gelu_rows_kernel)
-    if v == 1:
-        return f"pipnet_gemm::gemm_f32_tn_kernel<16, 2, {epilogue}, {aload}, 2, 3, 0, false>"
-    if v == 0:
-        return f"pipnet_gemm::gemm_f32_tn_ktail_kernel<{epilogue}, {aload}>"
-    if v == 5:
-        return f"pipnet_gemm::gemm_f32_tnw_kernel<{epilogue}, {aload}, 0>"
-    if v == 3:
-        return f"pipnet_gemm::gemm_f32_tn_kernel<32, 2, {epilogue}, {aload}, 2, 2, 0, false>"
-    npad = "true" if n % 128 else "false"      # padded-column MFMA blocks skipped
-    return f"pipnet_gemm::gemm_f32_tn_kernel<32, 1, {epilogue}, {aload}, 3, 2, 0, {npad}>"
+@functools.lru_cache(maxsize=4096)
+def gemm_kernel_name(m: int, n: int, k: int, epilogue: int, aload: int, splits: int = 1) -> str:
+    """The rocprof name of the GEMM instantiation the library launches (pipnet_linear_f32_label: dense,
+    unit-stride, 16-B aligned torch operands); ``splits`` > 1: the split-K main kernel."""
+    return _lib.label("pipnet_linear_f32_label", m, n, k, epilogue, aload, splits)
 
 
 _CUS = {}
@@ -227,7 +216,7 @@ def linear(a: Tensor, w: Tensor, bias: Optional[Tensor] = None, epilogue: int = 
     splits = splitk_factor(_plan_rows(m), n, k)
     if splits > 1:
         ws = torch.empty((splits, m, n), device=a.device, dtype=torch.float32)
-        _launch(f"pipnet_gemm::gemm_f32_tn_kernel<32, 1, 0, 0, 3, 2, 0, false>", 2.0 * m * n * k,
+        _launch(gemm_kernel_name(m, n, k, epilogue, 0, splits), 2.0 * m * n * k,
                 lambda: _lib.call("pipnet_linear_splitk_f32", a.data_ptr(), a.stride(0), w.data_ptr(), _ptr(bias),
                                   _ptr(scale), _ptr(r), ldr, out.data_ptr(), out.stride(0), m, n, k, epilogue, splits,
                                   ws.data_ptr(), _stream(a)))
@@ -252,7 +241,7 @@ def linear_pair_mul(a: Tensor, w_pair: Tensor) -> Tensor:
     splits = max(1, splitk_factor(m, n2, k))
     out = torch.empty((m, nh), device=a.device, dtype=torch.float32)
     ws = torch.empty((splits, m, n2), device=a.device, dtype=torch.float32)
-    _launch("pipnet_gemm::gemm_f32_tn_kernel<32, 1, 0, 0, 3, 2, 0, false>", 2.0 * m * n2 * k,
+    _launch(gemm_kernel_name(m, n2, k, _lib.EPI_NONE, 0, 2), 2.0 * m * n2 * k,      # always the split-K main kernel
             lambda: _lib.call("pipnet_linear_pair_mul_f32", a.data_ptr(), a.stride(0), w_pair.data_ptr(),
                               out.data_ptr(), out.stride(0), m, nh, k, splits, ws.data_ptr(), _stream(a)))
     return out
@@ -390,45 +379,14 @@ def bf16_conv_plan(b: int, h: int, w: int, cin: int, cout: int, kh: int, kw: int
     return v
 
 
-def s3_conv_tile(m: int, n: int, pp_ok: bool = True, kv: int = 0) -> int:
-    """Tile of a split-bf16 GEMM (csrc/conv_bf16.hip conv_variant's s3 branch; tiles 0 / 4 / 5 / 7).
-    The split path's labels only -- the ResNet bf16 convs ask the library (bf16_conv_plan)."""
-    m128 = 4 if -(-m // 128) * -(-n // 128) >= 512 else 0
-    if not pp_ok:
-        return m128
-    if n == 192:
-        return 7
-    if n == 384:
-        return 7 if kv >= 3 * 1024 else m128
-    return 5 if n >= 256 else m128
-
-
-_BF16_CFG = {0: ("pipnet_bf16::Cfg<2, 2, 1, 2, 32, 4>", 3), 1: ("pipnet_bf16::Cfg<2, 2, 2, 2, 64, 2>", 2),
-             2: ("pipnet_bf16::Cfg<2, 4, 4, 2, 64, 2>", 1), 3: ("pipnet_bf16::Cfg<2, 4, 4, 2, 32, 4>", 1),
-             4: ("pipnet_bf16::Cfg<2, 2, 2, 2, 32, 4>", 2), 6: ("pipnet_bf16::Cfg<4, 1, 2, 2, 32, 4>", 2)}
-
-
-PP_RB = 8     # row blocks of the 256-wide ping-pong tiles (csrc/conv_bf16.hip PP_RB): 256-row tiles
-
-
-def bf16_conv_kernel_name(m: int, n: int, epilogue: int, aload: int, tile: int, s3: bool = False,
-                          kv: int = 0) -> str:
-    """rocprof name of the bf16 conv instantiation of ``tile`` (bf16_conv_plan / s3_conv_tile)."""
-    t = tile
-    if t == 11:
-        return f"pipnet_bf16::conv3x3_bf16_hsmall_kernel<{kv // 9}, {epilogue}>"
-    if t == 9:
-        return f"pipnet_bf16::conv_bf16_ppp_kernel<{epilogue}, {PP_RB}>"
-    if t == 8:
-        nb = 4 if n >= 256 else (2 if n >= 128 else 1)
-        return f"pipnet_bf16::conv3x3_bf16_halo_kernel<{epilogue}, {nb}, {PP_RB}>"
-    if t == 5:
-        return f"pipnet_bf16::conv_bf16_pp_kernel<{epilogue}, {aload}, 4, 0, 2>"
-    if t == 7:
-        return f"pipnet_bf16::conv_bf16_pp_kernel<{epilogue}, {aload}, 3, 0, 2>"
-    cfg, minb = _BF16_CFG[t]
-    npad = "true" if s3 and t == 4 and n % 128 else "false"     # padded-column MFMA blocks skipped
-    return f"pipnet_bf16::conv_bf16_kernel<{cfg}, {epilogue}, {aload}, {minb}, {npad}>"
+@functools.lru_cache(maxsize=4096)
+def bf16_conv_kernel_name(b: int, h: int, w: int, cin: int, cout: int, kh: int, kw: int, stride: int, pad: int,
+                          epilogue: int, tile: int = -1, s3: bool = False) -> str:
+    """rocprof name of the instantiation conv2d_nhwc_bf16 (``s3``: conv_s3, ``cin`` its fp32 channels)
+    launches for this conv and requested ``tile`` (pipnet_conv2d_nhwc_bf16_label / _s3_label);
+    RuntimeError when the library has none, as the launch would answer."""
+    return _lib.label("pipnet_conv2d_nhwc_s3_label" if s3 else "pipnet_conv2d_nhwc_bf16_label",
+                      b, h, w, cin, cout, kh, kw, stride, pad, epilogue, tile)
 
 
 def pack_conv_weight_bf16(w_ohwi: Tensor) -> Tensor:
@@ -467,11 +425,9 @@ def conv2d_nhwc_bf16(x: Tensor, w_packed: Tensor, kh: int, kw: int, bias: Option
     oh, ow = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
     y = torch.empty((b, oh, ow, cout), device=x.device, dtype=torch.bfloat16)
     m = b * oh * ow
-    aload = 0 if (kh == 1 and kw == 1 and stride == 1 and pad == 0) else 2
     if tile < 0 and not CONV3X3_N64_HALO and bf16_conv_plan(b, h, w, cin, cout, kh, kw, stride, pad, epilogue) == 11:
         tile = 6 if cout == 64 else 4       # the same arithmetic on the generic tile (A/B arm)
-    t = bf16_conv_plan(b, h, w, cin, cout, kh, kw, stride, pad, epilogue, tile)
-    _launch(bf16_conv_kernel_name(m, cout, epilogue, aload, t, kv=k),
+    _launch(bf16_conv_kernel_name(b, h, w, cin, cout, kh, kw, stride, pad, epilogue, tile),
             2.0 * m * cout * k,
             lambda: _lib.call("pipnet_conv2d_nhwc_bf16_tile", x.data_ptr(), b, h, w, cin, w_packed.data_ptr(),
                               _ptr(bias), cout, kh, kw, stride, pad, _ptr(r), epilogue, y.data_ptr(), tile,
@@ -514,6 +470,12 @@ def nchw_to_nhwc_bf16(x: Tensor, cpad: int) -> Tensor:
     return y
 
 
+@functools.lru_cache(maxsize=256)
+def conv1x1_bf16_dual_kernel_name(m: int, cin: int, n1: int, n2: int) -> str:
+    """rocprof name of conv1x1_bf16_dual's kernel (pipnet_conv1x1_bf16_dual_label)."""
+    return _lib.label("pipnet_conv1x1_bf16_dual_label", m, cin, n1, n2)
+
+
 def conv1x1_bf16_dual(x: Tensor, w_packed: Tensor, bias: Tensor, n1: int, n2: int) -> Tuple[Tensor, Tensor]:
     """Two 1x1 stride-1 bf16 convs over one NHWC input in one launch (pipnet_conv1x1_bf16_dual):
     w_packed = the two packed weights stacked [n1 + n2, Kp], bias [n1 + n2] fp32 ->
@@ -525,8 +487,7 @@ def conv1x1_bf16_dual(x: Tensor, w_packed: Tensor, bias: Tensor, n1: int, n2: in
     y1 = torch.empty((b, h, w, n1), device=x.device, dtype=torch.bfloat16)
     y2 = torch.empty((b, h, w, n2), device=x.device, dtype=torch.bfloat16)
     m = b * h * w
-    _launch(f"pipnet_bf16::conv_bf16_ppp_kernel<12, {PP_RB}>",
-            2.0 * m * (n1 + n2) * cin,
+    _launch(conv1x1_bf16_dual_kernel_name(m, cin, n1, n2), 2.0 * m * (n1 + n2) * cin,
             lambda: _lib.call("pipnet_conv1x1_bf16_dual", x.data_ptr(), m, cin, w_packed.data_ptr(), bias.data_ptr(),
                               n1, y1.data_ptr(), n2, y2.data_ptr(), _stream(x)))
     return y1, y2
@@ -593,13 +554,8 @@ MLP_FUSED_CHANNELS = (96, 192)
 
 @functools.lru_cache(maxsize=1024)
 def cnblock_mlp_kernel_name(c: int, m: int = 1 << 20, hw: int = 0) -> str:
-    """rocprof name of the fused MLP instantiation the library launches (pipnet_cnblock_mlp_plan:
-    the library's own rule, csrc/mlp_f32.hip mlp_plan -- never mirrored here)."""
-    code = _lib.load().pipnet_cnblock_mlp_plan(m, c, hw)
-    if code < 0:
-        raise RuntimeError(f"cnblock_mlp: no plan for M = {m}, C = {c}, hw = {hw}")
-    hc, nw, hs = code // 100, code // 10 % 10, code % 10
-    return f"cnblock_mlp_kernel<{c}, {hc}, {nw}, 1, {hs}>"
+    """rocprof name of the fused MLP instantiation the library launches (pipnet_cnblock_mlp_label)."""
+    return _lib.label("pipnet_cnblock_mlp_label", m, c, hw)
 
 
 def cnblock_mlp(t: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, gamma: Tensor, x: Tensor,
@@ -686,9 +642,8 @@ def conv_s3(x2: Tensor, w_packed: Tensor, kh: int, kw: int, cout: int, bias: Opt
     elif out.dtype != dt or out.numel() != b * oh * ow * shape[-1] or not out.is_contiguous():
         raise RuntimeError(f"conv_s3: out {tuple(out.shape)} {out.dtype} does not match {shape} {dt}")
     m = b * oh * ow
-    aload = 0 if (kh == 1 and kw == 1 and stride == 1 and pad == 0) else 2
-    t = tile if tile >= 0 else s3_conv_tile(m, cout, kv=k)
-    _launch(bf16_conv_kernel_name(m, cout, epilogue, aload, t, s3=True, kv=k), 2.0 * m * cout * k / 3.0,
+    _launch(bf16_conv_kernel_name(b, h, w, cin, cout, kh, kw, stride, pad, epilogue, tile, s3=True),
+            2.0 * m * cout * k / 3.0,
             lambda: _lib.call("pipnet_conv2d_nhwc_s3", x2.data_ptr(), b, h, w, cin, w_packed.data_ptr(), _ptr(bias),
                               _ptr(scale), _ptr(r), cout, kh, kw, stride, pad, epilogue, out.data_ptr(), tile,
                               _stream(x2)))

@@ -53,12 +53,13 @@ extern "C" {
  * pipnet_linear_agelu_f32 are gone -- kernel selection is a fixed per-shape rule with no
  * mutable library state -- and the one-launch fused head pipnet_softmax_pool_linear_f32 / _bf16
  * (+ _part_floats) and pipnet_matmul2_f64acc_f32 are new (round 5).  A caller built against an older version must not bind this library.
- * Round 6 only ADDS entry points (pipnet_philox_exp1_f32, pipnet_conv2d_nhwc_bf16_plan,
- * pipnet_linear_f32_plan, pipnet_cnblock_mlp_plan); no signature changed.  The prototype
+ * Round 6 only ADDED entry points (pipnet_philox_exp1_f32, pipnet_conv2d_nhwc_bf16_plan,
+ * pipnet_linear_f32_plan); no signature changed.  The prototype
  * explanation entry points (pipnet_softmax_pool_argmax_f32, pipnet_map_argmax_f32,
  * pipnet_topk_update) are additions as well, and so are pipnet_local_explain_f32 and the
- * attribution entry points (pipnet_attr_*). */
-#define PIPNET_AMD_ABI_VERSION 3
+ * attribution entry points (pipnet_attr_*).  4: the fused-MLP plan query is gone (its packed code had to be
+ * decoded by the caller); the label queries (pipnet_*_label) are new. */
+#define PIPNET_AMD_ABI_VERSION 4
 int pipnet_amd_abi_version(void);
 const char* pipnet_amd_status_string(int status);
 /* sha256 (hex) of the sources this library was compiled from (build provenance). */
@@ -405,20 +406,28 @@ int pipnet_philox_exp1_f32(uint64_t seed, uint64_t offset, int64_t n, int log_e,
 /* fp32 GEMM variant plan: the variant pipnet_linear_f32 (and the conv / rowscale forms) launch for an
  * M x N x K product with dense 16-B aligned operands, PIPNET_EPI_* epilogue and A-operand gather
  * (0 dense / linear, 1 the 2x2 patch conv, 2 the general NHWC conv) -- 0 K-tail kernel, 1 BK16
- * 128-row, 2 BK32 64-row, 3 BK32 128-row, 5 BK32 192 x 384 on 12 waves -- or -PIPNET_ERR_ARG
- * (profiling labels). */
+ * 128-row, 2 BK32 64-row, 3 BK32 128-row, 5 BK32 192 x 384 on 12 waves -- or -PIPNET_ERR_ARG. */
 int pipnet_linear_f32_plan(int M, int N, int K, int epilogue, int aload);
 
-/* fused CNBlock MLP plan: the instantiation pipnet_cnblock_mlp_hw_f32 launches for M pixels of C
- * channels on maps of hw pixels per image (0 = unknown), as HC * 100 + NW * 10 + HS
- * (cnblock_mlp_kernel<C, HC, NW, 1, HS>), or -PIPNET_ERR_ARG (profiling labels). */
-int pipnet_cnblock_mlp_plan(int64_t M, int C, int hw);
-
 /* bf16 conv tile plan: the tile id pipnet_conv2d_nhwc_bf16_tile takes for this shape / epilogue
- * (tile -1 = the automatic choice, >= 0 validated), or -PIPNET_ERR_ARG.  The library's own rule,
- * exported so that profiling labels never mirror it (kernels.bf16_conv_kernel_name). */
+ * (tile -1 = the automatic choice, >= 0 validated), or -PIPNET_ERR_ARG.  The library's own rule. */
 int pipnet_conv2d_nhwc_bf16_plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
                                  int epilogue, int tile);
+
+/* Profiling labels: the name of the kernel a launch with these shape arguments runs, as rocprof and nm -C
+ * print it (e.g. "pipnet_bf16::conv_bf16_pp_kernel<5, 0, 4, 0, 2>").  Each query runs the selection of its
+ * launch (pipnet_linear_f32 and its rowscale / conv forms, splits > 1: the main kernel of the split-K
+ * entries; pipnet_conv2d_nhwc_bf16_tile; pipnet_conv2d_nhwc_s3; pipnet_conv1x1_bf16_dual;
+ * pipnet_cnblock_mlp_hw_f32) on dense 16-B aligned operands, as the plan queries do, without a HIP call.
+ * Writes the NUL-terminated label into buf[cap] and returns its length, or -PIPNET_ERR_ARG when the launch
+ * would be refused or the label does not fit. */
+int pipnet_linear_f32_label(int M, int N, int K, int epilogue, int aload, int splits, char* buf, int cap);
+int pipnet_conv2d_nhwc_bf16_label(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                  int epilogue, int tile, char* buf, int cap);
+int pipnet_conv2d_nhwc_s3_label(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                int epilogue, int tile, char* buf, int cap);
+int pipnet_conv1x1_bf16_dual_label(int64_t M, int Cin, int N1, int N2, char* buf, int cap);
+int pipnet_cnblock_mlp_label(int64_t M, int C, int hw, char* buf, int cap);
 
 /* Count finish (count_pipnet.py:88-97): counts_raw = float(hist) (or sums when hist is
  * NULL), clamped = clamp(round?(counts), 0, max_count) -- round when do_round.

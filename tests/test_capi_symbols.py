@@ -25,7 +25,7 @@ def test_library_loads_and_exports_all_symbols():
     lib = _lib.load()
     for s in declared_symbols():
         assert hasattr(lib, s), s
-    assert lib.pipnet_amd_abi_version() == 3
+    assert lib.pipnet_amd_abi_version() == 4
     assert lib.pipnet_amd_status_string(1).decode().startswith("invalid argument")
 
 
@@ -111,7 +111,7 @@ def test_roofline_kernel_names_exist_in_library():
                  (192, 1024)]:                                 # fused narrow-stage MLP (csrc/mlp_f32.hip)
         assert K.cnblock_mlp_kernel_name(c, m) in out, (c, m)
     assert K.cnblock_mlp_kernel_name(192, 16384, hw=256) in out          # hidden split (C5 stage 2)
-    # the labels are the library's plan (pipnet_cnblock_mlp_plan), not a Python mirror
+    # the labels are the library's own (pipnet_cnblock_mlp_label), not a Python mirror
     assert K.cnblock_mlp_kernel_name(96, 200704) == "cnblock_mlp_kernel<96, 32, 4, 1, 1>"      # C2 stage 1
     assert K.cnblock_mlp_kernel_name(96, 65536) == "cnblock_mlp_kernel<96, 32, 8, 1, 1>"       # C5 stage 1
     assert K.cnblock_mlp_kernel_name(192, 25088) == "cnblock_mlp_kernel<192, 16, 8, 1, 1>"     # C2 stage 2 (half)
@@ -121,7 +121,7 @@ def test_roofline_kernel_names_exist_in_library():
     assert "pipnet_bf16::stem_pool_bf16_kernel" in out                     # fused stem + max-pool
     for m, n, epi in [(200704, 96, _lib.EPI_F32_RESID), (200704, 384, _lib.EPI_S3_GELU),
                       (50176, 192, _lib.EPI_F32_RESID)]:                      # split-bf16 GEMMs
-        name = K.bf16_conv_kernel_name(m, n, epi, 0, K.s3_conv_tile(m, n, kv=3 * 4 * n), s3=True)
+        name = K.bf16_conv_kernel_name(m // 3136, 56, 56, 4 * n, n, 1, 1, 1, 0, epi, s3=True)
         assert name in syms, (m, n, epi, name)
 
 
@@ -150,8 +150,7 @@ def test_bf16_labels_come_from_the_library_plan():
     for name, h, cin, cout, k, s, pad, epi, want in C3_LAYERS:
         t = K.bf16_conv_plan(64, h, h, cin, cout, k, k, s, pad, epi)
         assert t == want, (name, t, want)
-        oh = (h + 2 * pad - k) // s + 1
-        label = K.bf16_conv_kernel_name(64 * oh * oh, cout, epi, 0 if k == 1 and s == 1 else 2, t, kv=k * k * cin)
+        label = K.bf16_conv_kernel_name(64, h, h, cin, cout, k, k, s, pad, epi)
         assert label in out, (name, label)
     # a requested tile is validated, not chosen: tile 8 needs a 3x3 stride-1 halo shape
     import pytest
