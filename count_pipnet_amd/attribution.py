@@ -292,27 +292,6 @@ class _Chunk:
                  "hw")
 
 
-def _count_tail(m: nn.Module, clamped: Tensor):
-    """Intermediate layer and classifier of a CountPIPNet on the clamped counts: (activations the
-    bilinear backward needs, logits) -- train._count_train_forward's tail."""
-    from . import _lib
-    from .count_pipnet import intermediate_hip
-    from .count_pipnet_utils import BilinearIntermediate
-    layer = m._intermediate
-    saved = {}
-    if isinstance(layer, BilinearIntermediate):
-        e = K.linear(clamped, layer.embed.weight)
-        u = K.linear(e, layer.W.weight)
-        v = K.linear(e, layer.V.weight)
-        inter = torch.empty_like(u)
-        K.linear(e, layer.V.weight, epilogue=_lib.EPI_MUL, r=u, out=inter)
-        saved.update(e=e, u=u, v=v)
-    else:
-        inter = intermediate_hip(layer, clamped)
-    _, out = K.nonneg_linear(inter, m._classification.weight, m._classification.bias, None)
-    return saved, out
-
-
 def _gumbel_heads(logits: Tensor, tau: float, noise: Optional[Tensor], seed: int, block0: int):
     """Hard histogram and soft map of one chunk on the same noise: (hist int32 [B,P], soft [B,h,w,P]).
     The chunk's first step starts at Philox block ``block0`` and step b at block0 + b h w P / 4; where
@@ -336,7 +315,7 @@ def _chunk_forward(m, x, baseline, alpha: Tensor, noise: Optional[Tensor], seed:
     from .count_pipnet_utils import GumbelSoftmax
     from .local import _map_is_small, _note_map
     from .pipnet import add_on_activation, add_on_logits_hip
-    from .train import _forward_saving
+    from .train import _count_tail, _forward_saving
     ck = _Chunk()
     b = alpha.numel()
     images = K.attr_path_images(x, baseline, alpha)
@@ -369,7 +348,7 @@ def _chunk_forward(m, x, baseline, alpha: Tensor, noise: Optional[Tensor], seed:
         ck.counts, ck.clamped = K.count_finish(None, sums, m._max_count, bool(m._use_ste))
     ck.pooled = ck.counts
     with K.per_image_gemm_plan(b):             # one row per image: the logits do not see the chunk size
-        ck.inter_saved, ck.out = _count_tail(m, ck.clamped)
+        ck.inter_saved, _, ck.out = _count_tail(m, ck.clamped)
     return ck
 
 

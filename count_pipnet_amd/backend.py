@@ -89,3 +89,23 @@ def packed_ready() -> None:
     readers already and nothing waits."""
     if getattr(_CROSS, "depth", 0) and torch.cuda.is_available() and not torch.cuda.is_current_stream_capturing():
         torch.cuda.current_stream().synchronize()
+
+
+def packed(cache: dict, key: str, t: torch.Tensor, fn) -> torch.Tensor:
+    """Device-layout copy of a parameter, rebuilt whenever the parameter changes
+    (storage pointer or in-place version counter: callers mutate weights, test.py:73)."""
+    stamp = (t.data_ptr(), t._version, tuple(t.shape))
+    key = (key, str(t.device))          # replicas on several devices share one module dict
+    ent = cache.get(key)
+    if ent is None or ent[0] != stamp:
+        with torch.no_grad():
+            ent = (stamp, fn(t.detach()).contiguous())
+        cache[key] = ent
+        packed_ready()
+    return ent[1]
+
+
+def _set_grad(p: torch.Tensor, g: torch.Tensor) -> None:
+    """.grad of a parameter a HIP backward computed (in whatever layout), if it trains."""
+    if p.requires_grad:
+        p.grad = g.reshape(p.shape).contiguous()

@@ -23,7 +23,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import kernels as K
-from .backend import use_hip, packed_ready
+from .backend import packed, use_hip
 
 Tensor = torch.Tensor
 
@@ -229,20 +229,6 @@ def as_nhwc(x: Tensor) -> Tensor:
     """[B,C,h,w] -> contiguous [B,h,w,C] (free when x is channels_last, e.g. our own output)."""
     y = x.permute(0, 2, 3, 1)
     return y if y.is_contiguous() else y.contiguous()
-
-
-def packed(cache: Dict, key: str, t: Tensor, fn) -> Tensor:
-    """Device-layout copy of a parameter, rebuilt whenever the parameter changes
-    (storage pointer or in-place version counter: callers mutate weights, test.py:73)."""
-    stamp = (t.data_ptr(), t._version, tuple(t.shape))
-    key = (key, str(t.device))          # replicas on several devices share one module dict
-    ent = cache.get(key)
-    if ent is None or ent[0] != stamp:
-        with torch.no_grad():
-            ent = (stamp, fn(t.detach()).contiguous())
-        cache[key] = ent
-        packed_ready()
-    return ent[1]
 
 
 FUSED_MLP = True      # tools / A-B runs may switch the fused narrow-stage MLP off

@@ -32,6 +32,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import kernels as K
+from .backend import _set_grad, packed
 
 Tensor = torch.Tensor
 
@@ -66,16 +67,6 @@ def trainable_start(model) -> int:
     return len(blocks)
 
 
-def _packed(cache: Dict, key: str, w: Tensor, fn):
-    stamp = (w.data_ptr(), w._version)
-    ent = cache.get(key)
-    if ent is None or ent[0] != stamp:
-        with torch.no_grad():
-            ent = (stamp, fn(w.detach()).contiguous())
-        cache[key] = ent
-    return ent[1]
-
-
 def _conv(cache: Dict, key: str, conv: nn.Conv2d, x: Tensor, cpad: Optional[int] = None) -> Tensor:
     """Raw (bias-free) conv of NHWC x."""
     if conv.groups != 1 or conv.dilation != (1, 1) or conv.bias is not None or \
@@ -84,9 +75,9 @@ def _conv(cache: Dict, key: str, conv: nn.Conv2d, x: Tensor, cpad: Optional[int]
     k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
     b, h, w, cin = x.shape
     if k == 1 and s == 1 and p == 0:
-        wt = _packed(cache, key + ".w11", conv.weight, lambda t: t.view(t.shape[0], t.shape[1]))
+        wt = packed(cache, key + ".w11", conv.weight, lambda t: t.view(t.shape[0], t.shape[1]))
         return K.linear(x.view(-1, cin), wt).view(b, h, w, wt.shape[0])
-    wp = _packed(cache, key + ".wohwi", conv.weight,
+    wp = packed(cache, key + ".wohwi", conv.weight,
                  lambda t: torch.nn.functional.pad(t.permute(0, 2, 3, 1), (0, (cpad or t.shape[1]) - t.shape[1])))
     return K.conv2d_nhwc(x, wp, None, s, p, _lib.EPI_NONE)
 
@@ -150,11 +141,6 @@ def train_forward(model, xs: Tensor, start: Optional[int]) -> Tuple[Tensor, list
     return h, saved
 
 
-def _set_grad(p: Tensor, g: Tensor) -> None:
-    if p.requires_grad:
-        p.grad = g.reshape(p.shape).contiguous()
-
-
 def _bn_grads(bn: nn.BatchNorm2d, dg: Tensor, db: Tensor) -> None:
     _set_grad(bn.weight, dg)
     _set_grad(bn.bias, db)
@@ -179,7 +165,7 @@ def _conv_dgrad(cache: Dict, key: str, conv: nn.Conv2d, dy: Tensor, x_shape, int
     b, h, w, cin = x_shape
     cout = conv.out_channels
     if k == 1:
-        wt = _packed(cache, key + ".w11t", conv.weight, lambda t: t.view(cout, cin).t())
+        wt = packed(cache, key + ".w11t", conv.weight, lambda t: t.view(cout, cin).t())
         if s == 1:
             if into is None:
                 return K.linear(dy.reshape(-1, cout), wt).view(b, h, w, cin)
@@ -190,7 +176,7 @@ def _conv_dgrad(cache: Dict, key: str, conv: nn.Conv2d, dy: Tensor, x_shape, int
         return K.stride_scatter(g, h, w, s, out=into, accumulate=into is not None)
     if p != (k - 1) // 2:
         raise RuntimeError(f"ResNet HIP training: unsupported conv padding {conv}")
-    wf = _packed(cache, key + ".wflip", conv.weight, lambda t: t.flip(2, 3).permute(1, 2, 3, 0))
+    wf = packed(cache, key + ".wflip", conv.weight, lambda t: t.flip(2, 3).permute(1, 2, 3, 0))
     src = dy if s == 1 else K.stride_scatter(dy, h, w, s)
     d = K.conv2d_nhwc(src, wf, None, 1, p, _lib.EPI_NONE)
     if tuple(d.shape) != (b, h, w, cin):

@@ -28,16 +28,20 @@ suffix on the same kernels: ConvNeXt CNBlocks / downsamples / stem (``_forward_s
 ``_block_backward``) and the ResNet-50 Bottlenecks with train-mode BatchNorm
 (``resnet_train``; every BN of the backbone, frozen ones included, normalises with batch
 statistics and updates its running statistics, as under the reference's ``net.train()``).
+
+Every phase of both models is the one ``_train_step``; the four public ``hip_*_step`` functions
+choose its phase and loss weights, the two heads (``_pipnet_head``, ``_count_head``) its middle.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
 from torch import Tensor
 
 from . import kernels as K
+from .backend import _set_grad, packed
 from .convnext_features import CNBlock, ConvNeXt, MidLayerConvNeXt, convnext_features_hip
 
 # (align, tanh, class) loss weights of the non-pretrain phases (train.py:56-61)
@@ -92,19 +96,78 @@ def stochastic_depth_masks(features: nn.Sequential, batch: int,
     return masks
 
 
+def _supported(net: nn.Module, count: bool, finetune: bool) -> bool:
+    """True when the iteration runs on the HIP kernels: a PIP-Net (``count``: a CountPIPNet whose
+    intermediate layer has a HIP backward) on a backbone with a HIP train-mode forward, fp32 on a
+    ROCm device, whose trainable set fits the phase -- ``finetune``: within the classifier (and the
+    intermediate layer); otherwise a backbone suffix features[j:] (j = 0: the stem too)."""
+    m = _inner(net)
+    if hasattr(m, "_max_count") != count or not hasattr(m, "_classification") or not _backbone_ok(m):
+        return False
+    if count:
+        from .count_pipnet_utils import (BilinearIntermediate, IdentityIntermediate, LinearFull, LinearIntermediate,
+                                         OneHotEncoder)
+        if not isinstance(m._intermediate, (IdentityIntermediate, OneHotEncoder, LinearFull, LinearIntermediate,
+                                           BilinearIntermediate)):
+            return False
+    if not all(p.is_cuda and p.dtype == torch.float32 for p in m.parameters()):
+        return False
+    if not finetune:
+        return trainable_suffix_start(m) < _backbone_units(m)
+    cls = m._classification
+    allowed = list(cls.parameters()) + list(m._intermediate.parameters()) if count else [cls.weight, cls.bias]
+    return {id(p) for p in m.parameters() if p.requires_grad} <= {id(p) for p in allowed}
+
+
 def hip_finetune_supported(net: nn.Module) -> bool:
     """True when the finetune iteration runs on the HIP kernels: a PIP-Net (not Count)
     with a ConvNeXt backbone, fp32 on a ROCm device, only classifier parameters trainable."""
-    m = _inner(net)
-    if hasattr(m, "_max_count") or not hasattr(m, "_classification"):
-        return False
-    if not _backbone_ok(m):
-        return False
-    if not all(p.is_cuda and p.dtype == torch.float32 for p in m.parameters()):
-        return False
-    cls = m._classification
-    allowed = {id(cls.weight)} | ({id(cls.bias)} if cls.bias is not None else set())
-    return {id(p) for p in m.parameters() if p.requires_grad} <= allowed
+    return _supported(net, count=False, finetune=True)
+
+
+def hip_count_finetune_supported(net: nn.Module) -> bool:
+    """A ConvNeXt CountPIPNet (fp32, ROCm) whose trainable parameters are within the
+    classifier and an intermediate layer with a HIP backward (identity, one-hot, linear_full,
+    bilinear)."""
+    return _supported(net, count=True, finetune=True)
+
+
+def hip_train_supported(net: nn.Module) -> bool:
+    """A ConvNeXt PIP-Net (fp32, ROCm) whose trainable backbone part is a suffix features[j:]
+    (the reference's pretrain / "train + freeze params" phases; j = 0, the stem included: the
+    "train everything" epochs after freeze_epochs, main.py:362-373)."""
+    return _supported(net, count=False, finetune=False)
+
+
+def hip_count_train_supported(net: nn.Module) -> bool:
+    """A ConvNeXt CountPIPNet (fp32, ROCm) whose trainable backbone part is a suffix
+    features[j:] (j = 0: the stem too), with an intermediate layer that has a HIP backward
+    (the reference's pretrain, "train + freeze params" and "train everything" phases for
+    CountPIPNet, main.py:238-256, 360-390)."""
+    return _supported(net, count=True, finetune=False)
+
+
+class _Head(NamedTuple):
+    """What a head's train-mode forward leaves for the loss and the backward."""
+    proto: Tensor                 # prototype map, NHWC
+    pooled: Tensor                # max-pooled presence scores (PIP-Net) / raw counts (CountPIPNet)
+    cls_in: Tensor                # the classifier's input
+    out: Tensor
+    saved: dict                   # CountPIPNet: tau, the clamped counts, the bilinear layer's activations
+
+
+def _pipnet_head(m: nn.Module, feats: Tensor) -> _Head:
+    """PIPNet.forward(inference=False) after the backbone: add-on softmax, max-pool, classifier."""
+    from .pipnet import add_on_logits_hip
+    proto, pooled = K.softmax_pool(add_on_logits_hip(m._add_on, feats), pool_mode=0)
+    _, out = K.nonneg_linear(pooled, m._classification.weight, m._classification.bias, None)
+    return _Head(proto, pooled, pooled, out, {})
+
+
+def _pipnet_head_backward(m: nn.Module, hd: _Head, d_out: Optional[Tensor], w_align: float, w_tanh: float,
+                          tanh_loss_coeff: float, to_logits: bool) -> Optional[Tensor]:
+    """d loss / d add-on logits (``to_logits``); a PIP-Net head has no parameter of its own."""
+    return K.head_backward(hd.proto, hd.pooled, d_out, m._classification.weight, w_align, w_tanh) if to_logits else None
 
 
 def train_forward_hip(net: nn.Module, xs: Tensor, sd_keep: Optional[Dict[int, Tensor]],
@@ -114,7 +177,6 @@ def train_forward_hip(net: nn.Module, xs: Tensor, sd_keep: Optional[Dict[int, Te
     under ``net.train()``, a ResNet backbone's BatchNorms normalise with batch statistics and
     take the running-statistics update; ``update_bn_stats=False`` restores every running
     statistic and counter afterwards (an observer forward that must not advance them)."""
-    from .pipnet import add_on_logits_hip
     m = _inner(net)
     saved = None
     if not update_bn_stats:
@@ -125,9 +187,8 @@ def train_forward_hip(net: nn.Module, xs: Tensor, sd_keep: Optional[Dict[int, Te
         finally:
             for b, v in saved or ():
                 b.copy_(v)
-        proto, pooled = K.softmax_pool(add_on_logits_hip(m._add_on, feats), pool_mode=0)
-        _, out = K.nonneg_linear(pooled, m._classification.weight, m._classification.bias, None)
-    return proto, pooled, out
+        hd = _pipnet_head(m, feats)
+    return hd.proto, hd.pooled, hd.out
 
 
 def _group_of(optimizer: torch.optim.Optimizer, param: Tensor) -> Optional[dict]:
@@ -161,79 +222,37 @@ def hip_adamw_step(optimizer: torch.optim.Optimizer, param: Tensor, grad: Tensor
     return True
 
 
-def hip_finetune_step(net: nn.Module, xs1: Tensor, xs2: Tensor, ys: Tensor,
-                      optimizer_classifier: torch.optim.Optimizer, enforce_weight_sparsity: bool = True,
-                      sd_keep: Optional[Dict[int, Tensor]] = None,
-                      generator: Optional[torch.Generator] = None) -> Tensor:
-    """One finetune iteration on the device (no host sync).  Returns ``kernels.train_loss``'s
-    stats: [align, tanh, class, loss, correct, w_align, w_tanh, w_class]."""
-    m = _inner(net)
-    cls = m._classification
-    xs = torch.cat([xs1, xs2])
-    if sd_keep is None:
-        sd_keep = _sd_masks(m, xs.shape[0], generator)
-    proto, pooled, out = train_forward_hip(m, xs, sd_keep)
-    w_align, w_tanh, w_class = FINETUNE_LOSS_WEIGHTS
-    with torch.no_grad():
-        stats, d_out = K.train_loss(proto, pooled, out, ys, cls.normalization_multiplier, enforce_weight_sparsity,
-                                    1.0, w_align, w_tanh, w_class, "finetune")
-        train_b = cls.bias is not None and cls.bias.requires_grad
-        dw, db = K.nonneg_linear_backward(d_out, pooled, cls.weight, train_b)
-        clamp_w = (SPARSITY_DELTA, 0.0) if enforce_weight_sparsity else None
-        clamp_b = (0.0, 0.0) if enforce_weight_sparsity else None
-        stepped_w = stepped_b = False
-        if cls.weight.requires_grad:
-            cls.weight.grad = dw
-            stepped_w = hip_adamw_step(optimizer_classifier, cls.weight, dw, clamp_w)
-        if train_b:
-            cls.bias.grad = db
-            stepped_b = hip_adamw_step(optimizer_classifier, cls.bias, db, clamp_b)
-        if enforce_weight_sparsity:          # the clamps of parameters the optimizer did not touch
-            if not stepped_w:
-                K.weight_sparsify_(cls.weight.detach(), SPARSITY_DELTA)
-            if cls.bias is not None and not stepped_b:
-                K.clamp_min_(cls.bias.detach(), 0.0)
-            K.clamp_min_(cls.normalization_multiplier.detach(), 1.0)
-    return stats
-
-
 # ------------------------------------------------------------------------------------------
-# CountPIPNet finetune phase (main.py:333-343): classifier + intermediate layer train
+# CountPIPNet head (count_pipnet.py:70-110) and its backward
 # ------------------------------------------------------------------------------------------
-def hip_count_finetune_supported(net: nn.Module) -> bool:
-    """A ConvNeXt CountPIPNet (fp32, ROCm) whose trainable parameters are within the
-    classifier and an intermediate layer with a HIP backward (identity, one-hot, linear_full,
-    bilinear)."""
-    from .count_pipnet_utils import (BilinearIntermediate, IdentityIntermediate, LinearFull, LinearIntermediate,
-                                     OneHotEncoder)
-    m = _inner(net)
-    if not hasattr(m, "_max_count") or not _backbone_ok(m):
-        return False
-    if not isinstance(m._intermediate, (IdentityIntermediate, OneHotEncoder, LinearFull, LinearIntermediate,
-                                       BilinearIntermediate)):
-        return False
-    if not all(p.is_cuda and p.dtype == torch.float32 for p in m.parameters()):
-        return False
-    allowed = {id(p) for p in m._classification.parameters()} | {id(p) for p in m._intermediate.parameters()}
-    return {id(p) for p in m.parameters() if p.requires_grad} <= allowed
-
-
-def _count_train_forward(m: nn.Module, xs: Tensor, sd_keep: Dict[int, Tensor], j: Optional[int] = None):
-    """CountPIPNet.forward(xs) in train mode (count_pipnet.py:70-110) on the HIP kernels, keeping
-    what the backward needs: (proto NHWC, raw counts, clamped counts, intermediate activations
-    dict, classifier input, out).  With ``j`` the backbone suffix features[j:] runs with its
-    activations kept (``_forward_saving``); they and the features are added to the dict
-    (``feats``, ``suffix``) together with the head's temperature (``tau``)."""
+def _count_tail(m: nn.Module, clamped: Tensor):
+    """Intermediate layer and classifier of a CountPIPNet on the clamped counts: (activations the
+    bilinear backward needs, classifier input, logits)."""
     from . import _lib
-    from .count_pipnet_utils import BilinearIntermediate, GumbelSoftmax
+    from .count_pipnet import intermediate_hip
+    from .count_pipnet_utils import BilinearIntermediate
+    layer = m._intermediate
+    saved = {}
+    if isinstance(layer, BilinearIntermediate):
+        e = K.linear(clamped, layer.embed.weight)
+        u = K.linear(e, layer.W.weight)
+        v = K.linear(e, layer.V.weight)
+        inter = torch.empty_like(u)
+        K.linear(e, layer.V.weight, epilogue=_lib.EPI_MUL, r=u, out=inter)
+        saved.update(e=e, u=u, v=v)
+    else:
+        inter = intermediate_hip(layer, clamped)
+    _, out = K.nonneg_linear(inter, m._classification.weight, m._classification.bias, None)
+    return saved, inter, out
+
+
+def _count_head(m: nn.Module, feats: Tensor) -> _Head:
+    """CountPIPNet.forward in train mode after the backbone: soft Gumbel-softmax / softmax map,
+    spatial sums = raw counts, STE round and clamp, intermediate layer, classifier.  ``saved``
+    keeps the head's temperature (``tau``) and the clamped counts with the tail's activations."""
+    from .count_pipnet_utils import GumbelSoftmax
     from .count_pipnet import _fresh_seed
     from .pipnet import add_on_activation, add_on_logits_hip
-    saved = {}
-    if j is None:
-        feats = _backbone_train_forward(m, xs, sd_keep)
-    else:
-        feats, saved["suffix"] = _backbone_forward_saving(m, xs, j, sd_keep)
-        saved["feats"] = feats
     act = add_on_activation(m._add_on)
     if isinstance(act, GumbelSoftmax):
         logits = add_on_logits_hip(m._add_on, feats, activation=GumbelSoftmax)
@@ -243,27 +262,24 @@ def _count_train_forward(m: nn.Module, xs: Tensor, sd_keep: Dict[int, Tensor], j
                                                                         dtype=torch.float32).contiguous(), 0)
         else:
             proto, sums = K.count_gumbel_soft(logits, act.tau, None, _fresh_seed())   # fresh noise per call
-        saved["tau"] = float(act.tau)
+        tau = float(act.tau)
     else:
         logits = add_on_logits_hip(m._add_on, feats, activation=nn.Softmax)
         proto, sums = K.softmax_pool(logits, pool_mode=1)
-        saved["tau"] = 1.0
+        tau = 1.0
     del logits
     # train mode: STE round in the forward only with use_ste (count_pipnet.py:90-97)
     counts, clamped = K.count_finish(None, sums, m._max_count, bool(m._use_ste))
-    layer = m._intermediate
-    if isinstance(layer, BilinearIntermediate):
-        e = K.linear(clamped, layer.embed.weight)
-        u = K.linear(e, layer.W.weight)
-        v = K.linear(e, layer.V.weight)
-        inter = torch.empty_like(u)
-        K.linear(e, layer.V.weight, epilogue=_lib.EPI_MUL, r=u, out=inter)
-        saved.update(e=e, u=u, v=v)
-    else:
-        from .count_pipnet import intermediate_hip
-        inter = intermediate_hip(layer, clamped)
-    _, out = K.nonneg_linear(inter, m._classification.weight, m._classification.bias, None)
-    return proto, counts, clamped, saved, inter, out
+    saved, inter, out = _count_tail(m, clamped)
+    saved.update(tau=tau, clamped=clamped)
+    return _Head(proto, counts, inter, out, saved)
+
+
+def _count_train_forward(m: nn.Module, xs: Tensor, sd_keep: Dict[int, Tensor]):
+    """CountPIPNet.forward(xs) in train mode on the HIP kernels: (proto NHWC, raw counts, clamped
+    counts, the head's saved dict, classifier input, out)."""
+    hd = _count_head(m, _backbone_train_forward(m, xs, sd_keep))
+    return hd.proto, hd.pooled, hd.saved["clamped"], hd.saved, hd.cls_in, hd.out
 
 
 def _intermediate_backward(layer: nn.Module, x: Tensor, saved: dict, d_inter: Tensor,
@@ -314,52 +330,23 @@ def _intermediate_backward(layer: nn.Module, x: Tensor, saved: dict, d_inter: Te
     raise NotImplementedError(f"HIP count training: no backward for {type(layer).__name__}")
 
 
-def hip_count_finetune_step(net: nn.Module, xs1: Tensor, xs2: Tensor, ys: Tensor,
-                            optimizer_classifier: torch.optim.Optimizer, enforce_weight_sparsity: bool = True,
-                            tanh_loss_coeff: float = 1.0, sd_keep: Optional[Dict[int, Tensor]] = None,
-                            generator: Optional[torch.Generator] = None) -> Tensor:
-    """One CountPIPNet finetune iteration (train.py:75-140 with finetune=True,
-    is_count_pipnet=True): train-mode forward (soft Gumbel head, stochastic depth), the loss
-    kernel (loss = 2 * class; align / tanh over C * raw counts for logging), backward into the
-    classifier and the intermediate layer, AdamW for every parameter the classifier optimizer
-    holds (intermediate included when ``train_intermediate`` put it there), the sparsity clamps.
-    Returns the loss-kernel stats without synchronising."""
-    m = _inner(net)
-    cls = m._classification
-    xs = torch.cat([xs1, xs2])
-    if sd_keep is None:
-        sd_keep = _sd_masks(m, xs.shape[0], generator)
-    w_align, w_tanh, w_class = FINETUNE_LOSS_WEIGHTS
-    with torch.no_grad():
-        proto, counts, clamped, saved, inter, out = _count_train_forward(m, xs, sd_keep)
-        stats, d_out = K.train_loss(proto, counts, out, ys, cls.normalization_multiplier, enforce_weight_sparsity,
-                                    tanh_loss_coeff, w_align, w_tanh, w_class, "finetune")
-        train_b = cls.bias is not None and cls.bias.requires_grad
-        dw, db = K.nonneg_linear_backward(d_out, inter, cls.weight, train_b)
-        if cls.weight.requires_grad:
-            cls.weight.grad = dw
-        if train_b:
-            cls.bias.grad = db
-        layer = m._intermediate
-        if any(p.requires_grad for p in layer.parameters()):
-            _intermediate_backward(layer, clamped, saved, K.nonneg_linear_dx(d_out, cls.weight.detach()))
-        stepped = set()
-        for g in optimizer_classifier.param_groups:
-            for p in g["params"]:
-                if p.grad is None:
-                    continue
-                post = None
-                if enforce_weight_sparsity:
-                    post = (SPARSITY_DELTA, 0.0) if p is cls.weight else (0.0, 0.0) if p is cls.bias else None
-                if hip_adamw_step(optimizer_classifier, p, p.grad, post):
-                    stepped.add(id(p))
-        if enforce_weight_sparsity:          # the clamps of parameters the optimizer did not touch
-            if id(cls.weight) not in stepped:
-                K.weight_sparsify_(cls.weight.detach(), SPARSITY_DELTA)
-            if cls.bias is not None and id(cls.bias) not in stepped:
-                K.clamp_min_(cls.bias.detach(), 0.0)
-            K.clamp_min_(cls.normalization_multiplier.detach(), 1.0)
-    return stats
+def _count_head_backward(m: nn.Module, hd: _Head, d_out: Optional[Tensor], w_align: float, w_tanh: float,
+                         tanh_loss_coeff: float, to_logits: bool) -> Optional[Tensor]:
+    """Backward below the classifier: intermediate layer (parameter gradients; ModifiedSTE for a
+    one-hot encoder) and, with ``to_logits``, on through ClampSTE / STE_Round -> d counts (+ the
+    tanh term) -> d proto (+ the align term) -> soft-max backward scaled by 1 / tau.  Without it
+    the intermediate layer runs only when one of its parameters trains, and nothing comes back."""
+    layer = m._intermediate
+    d_counts = None
+    if d_out is not None and (to_logits or any(p.requires_grad for p in layer.parameters())):
+        d_inter = K.nonneg_linear_dx(d_out, m._classification.weight.detach())
+        d_clamped = _intermediate_backward(layer, hd.saved["clamped"], hd.saved, d_inter, need_dx=to_logits)
+        if d_clamped is not None:
+            d_counts = K.count_ste_backward(hd.pooled, d_clamped, m._max_count, bool(m._use_ste),
+                                            not m._is_clamp_backward_identity or not m._use_ste)
+    if not to_logits:
+        return None
+    return K.count_head_backward(hd.proto, hd.pooled, d_counts, w_align, w_tanh, tanh_loss_coeff, hd.saved["tau"])
 
 
 # ------------------------------------------------------------------------------------------
@@ -400,18 +387,6 @@ def _backbone_forward_saving(m: nn.Module, xs: Tensor, j: int, sd_keep: Dict[int
     return _forward_saving(m, xs, j, sd_keep)
 
 
-def hip_train_supported(net: nn.Module) -> bool:
-    """A ConvNeXt PIP-Net (fp32, ROCm) whose trainable backbone part is a suffix features[j:]
-    (the reference's pretrain / "train + freeze params" phases; j = 0, the stem included: the
-    "train everything" epochs after freeze_epochs, main.py:362-373)."""
-    m = _inner(net)
-    if hasattr(m, "_max_count") or not _backbone_ok(m):
-        return False
-    if not all(p.is_cuda and p.dtype == torch.float32 for p in m.parameters()):
-        return False
-    return trainable_suffix_start(m) < _backbone_units(m)
-
-
 def _forward_saving(m: nn.Module, xs: Tensor, j: int, sd_keep: Dict[int, Tensor], eval_mode: bool = False,
                     nhwc4: Optional[Tensor] = None):
     """Train-mode forward; features[:j] on the inference executor, features[j:] with plain
@@ -422,7 +397,7 @@ def _forward_saving(m: nn.Module, xs: Tensor, j: int, sd_keep: Dict[int, Tensor]
     runs with rs = None), as under ``net.eval()``.  ``nhwc4`` (j = 0 only): the input already in
     the stem conv's 4-channel NHWC form, in place of ``xs``."""
     from . import _lib
-    from .convnext_features import LayerNorm2d, packed, stochastic_depth_row_scales
+    from .convnext_features import LayerNorm2d, stochastic_depth_row_scales
     feats, cache = m._net.features, m._net._hip_pack
     saved = []
     if j == 0:       # trainable stem (the "train everything" epochs): conv k4 s4 and LN unfused
@@ -471,18 +446,12 @@ def _forward_saving(m: nn.Module, xs: Tensor, j: int, sd_keep: Dict[int, Tensor]
     return h, saved
 
 
-def _set_grad(p: Tensor, g: Tensor) -> None:
-    if p.requires_grad:
-        p.grad = g.reshape(p.shape).contiguous()
-
-
 def _block_backward(blk: CNBlock, sv: dict, dy: Tensor, param_grads: bool = True, cache: Optional[dict] = None) -> Tensor:
     """Gradients of one CNBlock (written to the parameters' .grad); returns d input [B,H,W,C].
     ``param_grads=False``: the input gradient only -- no weight-gradient kernel runs, no .grad is
     touched, the reductions the kernels must write (d_ls, d_gamma, ...) go to scratch and the saved
     activations are left as they are; ``cache`` then keeps the transposed / flipped weights."""
     from . import _lib
-    from .convnext_features import packed
     dw, ln, l1, l2 = blk.block[0], blk.block[2], blk.block[3], blk.block[5]
     x = sv["x"]
     b, hh, ww, c = x.shape
@@ -629,12 +598,23 @@ def _addon_suffix_backward(m: nn.Module, feats: Tensor, saved: list, d_logits: T
     return None
 
 
-def _step_train_optimizers(m: nn.Module, optimizer_net, optimizer_classifier, pretrain: bool,
-                           enforce_weight_sparsity: bool) -> None:
-    """optimizer_classifier (not in pretrain; train.py:117-120) and optimizer_net (train.py:122-124)
-    as device AdamW steps, then the sparsity clamps (train.py:131-140)."""
+# ------------------------------------------------------------------------------------------
+# the iteration: one step for both models and every phase
+# ------------------------------------------------------------------------------------------
+def _loss_weights(pretrain: bool, epoch: int = 0, nr_epochs: int = 1) -> Tuple[float, float, float]:
+    """(align, tanh, class) loss weights of an iteration (train.py:45-61)."""
+    return (epoch / nr_epochs, 5.0, 0.0) if pretrain else FINETUNE_LOSS_WEIGHTS
+
+
+def _step_optimizers(m: nn.Module, optimizer_classifier, optimizer_net, enforce_weight_sparsity: bool) -> None:
+    """Device AdamW for every parameter with a .grad in optimizer_classifier (train.py:117-120)
+    and in optimizer_net (train.py:122-124) -- None: the phase does not step that one -- then the
+    sparsity clamps (train.py:131-140; not in pretrain, where the classifier optimizer rests).
+    The classifier weight's and bias's clamps ride on their AdamW launch; one that no such
+    launch clamped is clamped on its own, as the reference clamps whatever the optimizers did."""
     cls = m._classification
-    if not pretrain:
+    clamped = set()
+    if optimizer_classifier is not None:
         for g in optimizer_classifier.param_groups:
             for p in g["params"]:
                 if p.grad is not None:
@@ -642,16 +622,87 @@ def _step_train_optimizers(m: nn.Module, optimizer_net, optimizer_classifier, pr
                     if enforce_weight_sparsity:
                         post = (SPARSITY_DELTA, 0.0) if p is cls.weight else (0.0, 0.0) if p is cls.bias else None
                     hip_adamw_step(optimizer_classifier, p, p.grad, post)
-    for g in optimizer_net.param_groups:
-        for p in g["params"]:
-            if p.grad is not None:
-                hip_adamw_step(optimizer_net, p, p.grad)
-    if not pretrain and enforce_weight_sparsity:
-        if not cls.weight.requires_grad:
+                    clamped.add(id(p))
+    if optimizer_net is not None:
+        for g in optimizer_net.param_groups:
+            for p in g["params"]:
+                if p.grad is not None:
+                    hip_adamw_step(optimizer_net, p, p.grad)
+    if optimizer_classifier is not None and enforce_weight_sparsity:
+        if id(cls.weight) not in clamped:
             K.weight_sparsify_(cls.weight.detach(), SPARSITY_DELTA)
-        if cls.bias is not None and not cls.bias.requires_grad:
+        if cls.bias is not None and id(cls.bias) not in clamped:
             K.clamp_min_(cls.bias.detach(), 0.0)
         K.clamp_min_(cls.normalization_multiplier.detach(), 1.0)
+
+
+def _train_step(m: nn.Module, xs1: Tensor, xs2: Tensor, ys: Tensor, *, phase: str, optimizer_classifier,
+                optimizer_net=None, w: Tuple[float, float, float], enforce_weight_sparsity: bool,
+                tanh_loss_coeff: float = 1.0, sd_keep: Optional[Dict[int, Tensor]], generator, step_optimizers=True):
+    """One iteration of ``phase`` ("pretrain" | "train" | "finetune", also the loss kernel's mode):
+    concatenate the views and draw the stochastic-depth masks; backbone, head and loss; classifier
+    gradients; outside finetune the backward through head, add-on and the trainable suffix (whose
+    activations the forward then kept); AdamW on the device and the sparsity clamps."""
+    head, head_backward = (_count_head, _count_head_backward) if hasattr(m, "_max_count") else \
+        (_pipnet_head, _pipnet_head_backward)
+    finetune = phase == "finetune"
+    cls = m._classification
+    xs = torch.cat([xs1, xs2])
+    if sd_keep is None:
+        sd_keep = _sd_masks(m, xs.shape[0], generator)
+    w_align, w_tanh, w_class = w
+    with torch.no_grad():
+        if finetune:
+            feats, suffix = _backbone_train_forward(m, xs, sd_keep), None
+        else:
+            feats, suffix = _backbone_forward_saving(m, xs, trainable_suffix_start(m), sd_keep)
+        hd = head(m, feats)
+        stats, d_out = K.train_loss(hd.proto, hd.pooled, hd.out, ys, cls.normalization_multiplier,
+                                    enforce_weight_sparsity, tanh_loss_coeff, w_align, w_tanh, w_class, phase)
+        has_bias = cls.bias is not None
+        if d_out is not None and (finetune or cls.weight.requires_grad or (has_bias and cls.bias.requires_grad)):
+            # db is only ever kept under requires_grad (_set_grad), so asking for it is a matter of cost alone:
+            # the finetune steps have always skipped a frozen bias's column sum, the other phases compute it
+            # whenever there is a bias; each phase goes on launching what it did
+            want_bias = has_bias and (cls.bias.requires_grad or not finetune)
+            dw, db = K.nonneg_linear_backward(d_out, hd.cls_in, cls.weight, want_bias)
+            _set_grad(cls.weight, dw)
+            if want_bias:
+                _set_grad(cls.bias, db)
+        d_logits = head_backward(m, hd, d_out, w_align, w_tanh, tanh_loss_coeff, to_logits=not finetune)
+        del hd
+        if not finetune:
+            _addon_suffix_backward(m, feats, suffix, d_logits)
+        if step_optimizers:
+            _step_optimizers(m, None if phase == "pretrain" else optimizer_classifier,
+                             None if finetune else optimizer_net, enforce_weight_sparsity)
+    return stats
+
+
+def hip_finetune_step(net: nn.Module, xs1: Tensor, xs2: Tensor, ys: Tensor,
+                      optimizer_classifier: torch.optim.Optimizer, enforce_weight_sparsity: bool = True,
+                      sd_keep: Optional[Dict[int, Tensor]] = None,
+                      generator: Optional[torch.Generator] = None) -> Tensor:
+    """One finetune iteration on the device (no host sync).  Returns ``kernels.train_loss``'s
+    stats: [align, tanh, class, loss, correct, w_align, w_tanh, w_class]."""
+    return _train_step(_inner(net), xs1, xs2, ys, phase="finetune", optimizer_classifier=optimizer_classifier,
+                       w=_loss_weights(False), enforce_weight_sparsity=enforce_weight_sparsity, sd_keep=sd_keep,
+                       generator=generator)
+
+
+def hip_count_finetune_step(net: nn.Module, xs1: Tensor, xs2: Tensor, ys: Tensor,
+                            optimizer_classifier: torch.optim.Optimizer, enforce_weight_sparsity: bool = True,
+                            tanh_loss_coeff: float = 1.0, sd_keep: Optional[Dict[int, Tensor]] = None,
+                            generator: Optional[torch.Generator] = None) -> Tensor:
+    """One CountPIPNet finetune iteration (train.py:75-140 with finetune=True,
+    is_count_pipnet=True): train-mode forward (soft Gumbel head, stochastic depth), the loss
+    kernel (loss = 2 * class; align / tanh over C * raw counts for logging), backward into the
+    classifier and the intermediate layer, AdamW for every parameter the classifier optimizer
+    holds (intermediate included when ``train_intermediate`` put it there), the sparsity clamps.
+    Returns the loss-kernel stats without synchronising."""
+    return _train_step(_inner(net), xs1, xs2, ys, phase="finetune", optimizer_classifier=optimizer_classifier,
+                       w=_loss_weights(False), enforce_weight_sparsity=enforce_weight_sparsity,
+                       tanh_loss_coeff=tanh_loss_coeff, sd_keep=sd_keep, generator=generator)
 
 
 def hip_train_step(net: nn.Module, xs1: Tensor, xs2: Tensor, ys: Tensor, optimizer_net, optimizer_classifier,
@@ -664,51 +715,13 @@ def hip_train_step(net: nn.Module, xs1: Tensor, xs2: Tensor, ys: Tensor, optimiz
     parameter with requires_grad gets its .grad), then optimizer_classifier (joint only)
     and optimizer_net steps (AdamW on the device) and the sparsity clamps.  Returns the
     loss-kernel stats without synchronising."""
-    from .pipnet import add_on_logits_hip
     m = _inner(net)
-    j = trainable_suffix_start(m)
-    if j >= _backbone_units(m):
+    if trainable_suffix_start(m) >= _backbone_units(m):
         raise NotImplementedError("HIP training step: no trainable backbone parameter (use the finetune step)")
-    xs = torch.cat([xs1, xs2])
-    if sd_keep is None:
-        sd_keep = _sd_masks(m, xs.shape[0], generator)
-    cls = m._classification
-    w_align, w_tanh, w_class = (epoch / nr_epochs, 5.0, 0.0) if pretrain else FINETUNE_LOSS_WEIGHTS
-    with torch.no_grad():
-        feats, saved = _backbone_forward_saving(m, xs, j, sd_keep)
-        logits = add_on_logits_hip(m._add_on, feats)
-        proto, pooled = K.softmax_pool(logits, pool_mode=0)
-        _, out = K.nonneg_linear(pooled, cls.weight, cls.bias, None)
-        stats, d_out = K.train_loss(proto, pooled, out, ys, cls.normalization_multiplier, enforce_weight_sparsity,
-                                    1.0, w_align, w_tanh, w_class, "pretrain" if pretrain else "train")
-        if d_out is not None and (cls.weight.requires_grad or (cls.bias is not None and cls.bias.requires_grad)):
-            dw, db = K.nonneg_linear_backward(d_out, pooled, cls.weight, cls.bias is not None)
-            _set_grad(cls.weight, dw)
-            if cls.bias is not None:
-                _set_grad(cls.bias, db)
-        d_logits = K.head_backward(proto, pooled, d_out, cls.weight, w_align, w_tanh)
-        _addon_suffix_backward(m, feats, saved, d_logits)
-        if step_optimizers:
-            _step_train_optimizers(m, optimizer_net, optimizer_classifier, pretrain, enforce_weight_sparsity)
-    return stats
-
-
-def hip_count_train_supported(net: nn.Module) -> bool:
-    """A ConvNeXt CountPIPNet (fp32, ROCm) whose trainable backbone part is a suffix
-    features[j:] (j = 0: the stem too), with an intermediate layer that has a HIP backward
-    (the reference's pretrain, "train + freeze params" and "train everything" phases for
-    CountPIPNet, main.py:238-256, 360-390)."""
-    from .count_pipnet_utils import (BilinearIntermediate, IdentityIntermediate, LinearFull, LinearIntermediate,
-                                     OneHotEncoder)
-    m = _inner(net)
-    if not hasattr(m, "_max_count") or not _backbone_ok(m):
-        return False
-    if not isinstance(m._intermediate, (IdentityIntermediate, OneHotEncoder, LinearFull, LinearIntermediate,
-                                       BilinearIntermediate)):
-        return False
-    if not all(p.is_cuda and p.dtype == torch.float32 for p in m.parameters()):
-        return False
-    return trainable_suffix_start(m) < _backbone_units(m)
+    return _train_step(m, xs1, xs2, ys, phase="pretrain" if pretrain else "train", optimizer_net=optimizer_net,
+                       optimizer_classifier=optimizer_classifier, w=_loss_weights(pretrain, epoch, nr_epochs),
+                       enforce_weight_sparsity=enforce_weight_sparsity, sd_keep=sd_keep, generator=generator,
+                       step_optimizers=step_optimizers)
 
 
 def hip_count_train_step(net: nn.Module, xs1: Tensor, xs2: Tensor, ys: Tensor, optimizer_net, optimizer_classifier,
@@ -724,36 +737,12 @@ def hip_count_train_step(net: nn.Module, xs1: Tensor, xs2: Tensor, ys: Tensor, o
     (+ the align term) -> soft-max backward scaled by 1/tau -> add-on -> suffix; AdamW steps
     and the sparsity clamps as ``hip_train_step``.  Returns the loss-kernel stats."""
     m = _inner(net)
-    j = trainable_suffix_start(m)
-    if j >= _backbone_units(m):
+    if trainable_suffix_start(m) >= _backbone_units(m):
         raise NotImplementedError("HIP count training step: no trainable backbone parameter (use the finetune step)")
-    xs = torch.cat([xs1, xs2])
-    if sd_keep is None:
-        sd_keep = _sd_masks(m, xs.shape[0], generator)
-    cls = m._classification
-    w_align, w_tanh, w_class = (epoch / nr_epochs, 5.0, 0.0) if pretrain else FINETUNE_LOSS_WEIGHTS
-    with torch.no_grad():
-        proto, counts, clamped, saved, inter, out = _count_train_forward(m, xs, sd_keep, j)
-        stats, d_out = K.train_loss(proto, counts, out, ys, cls.normalization_multiplier, enforce_weight_sparsity,
-                                    tanh_loss_coeff, w_align, w_tanh, w_class, "pretrain" if pretrain else "train")
-        d_counts = None
-        if d_out is not None:
-            if cls.weight.requires_grad or (cls.bias is not None and cls.bias.requires_grad):
-                dw, db = K.nonneg_linear_backward(d_out, inter, cls.weight, cls.bias is not None)
-                _set_grad(cls.weight, dw)
-                if cls.bias is not None:
-                    _set_grad(cls.bias, db)
-            d_inter = K.nonneg_linear_dx(d_out, cls.weight.detach())
-            d_clamped = _intermediate_backward(m._intermediate, clamped, saved, d_inter, need_dx=True)
-            if d_clamped is not None:
-                d_counts = K.count_ste_backward(counts, d_clamped, m._max_count, bool(m._use_ste),
-                                                not m._is_clamp_backward_identity or not m._use_ste)
-        d_logits = K.count_head_backward(proto, counts, d_counts, w_align, w_tanh, tanh_loss_coeff, saved["tau"])
-        del proto
-        _addon_suffix_backward(m, saved["feats"], saved["suffix"], d_logits)
-        if step_optimizers:
-            _step_train_optimizers(m, optimizer_net, optimizer_classifier, pretrain, enforce_weight_sparsity)
-    return stats
+    return _train_step(m, xs1, xs2, ys, phase="pretrain" if pretrain else "train", optimizer_net=optimizer_net,
+                       optimizer_classifier=optimizer_classifier, w=_loss_weights(pretrain, epoch, nr_epochs),
+                       enforce_weight_sparsity=enforce_weight_sparsity, tanh_loss_coeff=tanh_loss_coeff,
+                       sd_keep=sd_keep, generator=generator, step_optimizers=step_optimizers)
 
 
 # ------------------------------------------------------------------------------------------
@@ -811,6 +800,21 @@ class HipEpoch:
         return info
 
 
+_NO_HIP_STEP = ("count_pipnet_amd.train_pipnet: this configuration (phase / trainable parameters / device) has no HIP "
+                "step; use the reference train_pipnet with these modules (torch autograd path)")
+# (is_count_pipnet, finetune) -> the step, its predicate, what train_pipnet says where the predicate fails
+_STEPS = {
+    (False, True): (hip_finetune_step, hip_finetune_supported, _NO_HIP_STEP),
+    (False, False): (hip_train_step, hip_train_supported, _NO_HIP_STEP),
+    (True, True): (hip_count_finetune_step, hip_count_finetune_supported,
+                   "count_pipnet_amd.train_pipnet: this CountPIPNet finetune setup has no HIP "
+                   "step; run the reference train_pipnet with these modules"),
+    (True, False): (hip_count_train_step, hip_count_train_supported,
+                    "count_pipnet_amd.train_pipnet: this CountPIPNet training setup (ResNet "
+                    "backbone or non-fp32 parameters) runs on the torch path"),
+}
+
+
 def train_pipnet(net, train_loader, optimizer_net, optimizer_classifier, scheduler_net, scheduler_classifier,
                  criterion, epoch, nr_epochs, device, is_count_pipnet=False, pretrain=False, finetune=False,
                  progress_prefix: str = "Train Epoch", enforce_weight_sparsity=True, tanh_loss_coeff=1.0,
@@ -824,40 +828,18 @@ def train_pipnet(net, train_loader, optimizer_net, optimizer_classifier, schedul
     reference's own loop on these modules (torch autograd path)."""
     if pretrain and finetune:
         raise NotImplementedError("count_pipnet_amd.train_pipnet: pretrain and finetune are exclusive")
-    if is_count_pipnet and finetune:
-        if not hip_count_finetune_supported(net):
-            raise NotImplementedError("count_pipnet_amd.train_pipnet: this CountPIPNet finetune setup has no HIP "
-                                      "step; run the reference train_pipnet with these modules")
-        weights = FINETUNE_LOSS_WEIGHTS
+    count, finetune = bool(is_count_pipnet), bool(finetune)
+    hip_step, supported, refusal = _STEPS[count, finetune]
+    if not supported(net):
+        raise NotImplementedError(refusal)
+    weights = _loss_weights(pretrain, epoch, nr_epochs)
+    args = (optimizer_classifier,) if finetune else (optimizer_net, optimizer_classifier, pretrain, epoch, nr_epochs)
+    kwargs = dict(tanh_loss_coeff=tanh_loss_coeff) if count else {}
 
-        def step(a, b, labels):
-            return hip_count_finetune_step(net, a, b, labels, optimizer_classifier, enforce_weight_sparsity,
-                                           tanh_loss_coeff, generator=generator)
-    elif is_count_pipnet:
-        if not hip_count_train_supported(net):
-            raise NotImplementedError("count_pipnet_amd.train_pipnet: this CountPIPNet training setup (ResNet "
-                                      "backbone or non-fp32 parameters) runs on the torch path")
-        weights = (epoch / nr_epochs, 5.0, 0.0) if pretrain else FINETUNE_LOSS_WEIGHTS
+    def step(a, b, labels):
+        return hip_step(net, a, b, labels, *args, enforce_weight_sparsity=enforce_weight_sparsity,
+                        generator=generator, **kwargs)
 
-        def step(a, b, labels):
-            return hip_count_train_step(net, a, b, labels, optimizer_net, optimizer_classifier, pretrain, epoch,
-                                        nr_epochs, enforce_weight_sparsity, tanh_loss_coeff, generator=generator)
-    elif finetune and hip_finetune_supported(net):
-        weights = FINETUNE_LOSS_WEIGHTS
-
-        def step(a, b, labels):
-            return hip_finetune_step(net, a, b, labels, optimizer_classifier, enforce_weight_sparsity,
-                                     generator=generator)
-    elif not finetune and hip_train_supported(net):
-        weights = (epoch / nr_epochs, 5.0, 0.0) if pretrain else FINETUNE_LOSS_WEIGHTS
-
-        def step(a, b, labels):
-            return hip_train_step(net, a, b, labels, optimizer_net, optimizer_classifier, pretrain, epoch,
-                                  nr_epochs, enforce_weight_sparsity, generator=generator)
-    else:
-        raise NotImplementedError(
-            "count_pipnet_amd.train_pipnet: this configuration (phase / trainable parameters / device) has no HIP "
-            "step; use the reference train_pipnet with these modules (torch autograd path)")
     net.train()
     _inner(net)._classification.requires_grad = not pretrain
     runner = HipEpoch(step, weights, track_acc=not pretrain)

@@ -20,10 +20,11 @@ import torch
 
 from count_pipnet_amd import kernels as K
 from count_pipnet_amd import train as T
-from count_pipnet_amd.convnext_features import CNBlock
 from golden_util import load_train_golden, train_golden_names, train_loader_batches, train_step_lrs
 from model_util import build_model
 from oracle import ref_cpu, train_ref
+from train_trace_cases import (_count_setup, _count_suffix_setup, _finetune_setup, _inject_noise,
+                               _optimizers_like_reference, _sd_keep)
 
 pytestmark = pytest.mark.gpu
 NAMES = [n for n in train_golden_names() if n.startswith("train_finetune_")]
@@ -137,37 +138,6 @@ def test_adamw_kernel_matches_torch(gpu, post):
         torch.testing.assert_close(q, p.detach(), rtol=1e-6, atol=3e-7)
         torch.testing.assert_close(m, opt.state[p]["exp_avg"], rtol=1e-6, atol=1e-6 * ms)
         torch.testing.assert_close(v, opt.state[p]["exp_avg_sq"], rtol=1e-6, atol=1e-6 * vs)
-
-
-def _finetune_setup(name, gpu):
-    meta, rec, fwd_meta = load_train_golden(name)
-    net = build_model(fwd_meta).to(gpu).train()
-    for prm in net.parameters():
-        prm.requires_grad = False
-    for prm in net._classification.parameters():
-        prm.requires_grad = True
-    net._classification.normalization_multiplier.requires_grad = False
-    cls = net._classification
-    groups = [{"params": [cls.weight], "lr": meta["lr"], "weight_decay": meta["weight_decay"]}]
-    if cls.bias is not None:
-        groups.append({"params": [cls.bias], "lr": meta["lr"], "weight_decay": 0.0})
-    opt = torch.optim.AdamW(groups, lr=meta["lr"], weight_decay=0.0)
-    sched = torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(opt, T_0=10, eta_min=0.001, T_mult=1)
-    c = fwd_meta["case"]
-    batches = train_loader_batches(c["size"], c["num_classes"], meta["iterations"], meta["batch_per_view"],
-                                   meta["seed"])
-    return meta, rec, fwd_meta, net, opt, sched, batches
-
-
-def _sd_keep(net, masks):
-    """Recorded masks (forward order of the blocks with p > 0) -> {block id: bool mask}."""
-    if not hasattr(net._net, "features"):         # ResNet: no stochastic depth
-        assert masks.shape[0] == 0
-        return {}
-    blocks = [m for m in net._net.features.modules() if isinstance(m, CNBlock)]
-    ids = [bid for bid, b in enumerate(blocks) if b.stochastic_depth.p > 0.0]
-    assert len(ids) == masks.shape[0]
-    return {bid: _t(masks[j]) > 0.5 for j, bid in enumerate(ids)}
 
 
 # Per-element AdamW trajectory tolerance from the reference's own per-iteration gradients
@@ -322,50 +292,6 @@ def test_train_forward_stochastic_depth_matches_oracle(gpu):
     torch.testing.assert_close(pooled.cpu(), rpool, rtol=1e-3, atol=2e-4)
     torch.testing.assert_close(out.cpu(), rout, rtol=1e-3, atol=2e-3)
     torch.testing.assert_close(proto.cpu().permute(0, 3, 1, 2), rp, rtol=1e-3, atol=2e-4)
-
-
-# ---- pretrain / joint phases: trainable backbone suffix + add-on (+ classifier) ------------
-def _optimizers_like_reference(net, meta, fwd_meta):
-    """AdamW groups of util/args.py:get_optimizer_nn (restated for the test) + the phase's
-    requires_grad pattern (main.py:238-256 pretrain, 377-390 joint) + its schedulers."""
-    case = fwd_meta["case"]
-    train, freeze, backbone = [], [], []
-    for name, prm in net._net.named_parameters():
-        parts = name.split(".")
-        if case["net"].startswith("resnet"):     # util/args.py:280-290
-            if "layer4.2" in name:
-                train.append(prm)
-            elif "layer4" in name or "layer3" in name:
-                freeze.append(prm)
-            elif "layer2" in name:
-                backbone.append(prm)
-        elif case.get("use_mid_layers"):
-            st = int(parts[1])
-            (train if st == case["num_stages"] else freeze if st == case["num_stages"] - 1 else backbone).append(prm)
-        else:
-            (train if "features.7.2" in name else freeze if ("features.7" in name or "features.6" in name)
-             else backbone).append(prm)
-    lr_net, lr_block = meta["lr_net"], meta["lr_block"]
-    opt_net = torch.optim.AdamW([{"params": backbone, "lr": lr_net, "weight_decay": 0.0},
-                                 {"params": freeze, "lr": lr_block, "weight_decay": 0.0},
-                                 {"params": train, "lr": lr_block, "weight_decay": 0.0},
-                                 {"params": list(net._add_on.parameters()), "lr": lr_block * 10.0, "weight_decay": 0.0}],
-                                lr=meta["lr"], weight_decay=0.0)
-    cls = net._classification
-    groups = [{"params": [cls.weight], "lr": meta["lr"], "weight_decay": meta["weight_decay"]}]
-    if cls.bias is not None:
-        groups.append({"params": [cls.bias], "lr": meta["lr"], "weight_decay": 0.0})
-    opt_cls = torch.optim.AdamW(groups, lr=meta["lr"], weight_decay=0.0)
-    for prm in net.parameters():
-        prm.requires_grad = False
-    for prm in train + freeze + list(net._add_on.parameters()) + (backbone if meta["phase"] == "full" else []):
-        prm.requires_grad = True
-    for prm in cls.parameters():
-        prm.requires_grad = meta["phase"] != "pretrain"
-    cls.normalization_multiplier.requires_grad = False
-    sched_net = torch.optim.lr_scheduler.CosineAnnealingLR(opt_net, T_max=10, eta_min=5e-6)
-    sched_cls = torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(opt_cls, T_0=10, eta_min=0.001, T_mult=1)
-    return opt_net, opt_cls, sched_net, sched_cls
 
 
 def _resnet_first_grads_close(net, rec):
@@ -608,31 +534,6 @@ def _resnet_grads_vs_f64(net, xs1, xs2, ys, hip, ref32, weights, gpu):
     assert eh[worst] < 0.25, (worst, eh[worst])
 
 
-# ---- CountPIPNet finetune phase: classifier + intermediate layer (main.py:333-343) -----------
-def _count_setup(name, gpu):
-    """The reference run's setup: finetune freeze (classifier + intermediate train), the
-    classifier optimizer of util/args.py:get_optimizer_nn with train_intermediate=True
-    (restated for the test), CosineAnnealingWarmRestarts as main.py:314."""
-    meta, rec, fwd_meta = load_train_golden(name)
-    net = build_model(fwd_meta).to(gpu).train()
-    cls = net._classification
-    for prm in net.parameters():
-        prm.requires_grad = False
-    for prm in list(cls.parameters()) + list(net._intermediate.parameters()):
-        prm.requires_grad = True
-    cls.normalization_multiplier.requires_grad = False
-    groups = [{"params": [cls.weight], "lr": meta["lr"], "weight_decay": meta["weight_decay"]},
-              {"params": [] if cls.bias is None else [cls.bias], "lr": meta["lr"], "weight_decay": 0.0},
-              {"params": list(net._intermediate.parameters()), "lr": meta["lr"],
-               "weight_decay": meta["weight_decay"]}]
-    opt = torch.optim.AdamW(groups, lr=meta["lr"], weight_decay=0.0)
-    sched = torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(opt, T_0=10, eta_min=0.001, T_mult=1)
-    c = fwd_meta["case"]
-    batches = train_loader_batches(c["size"], c["num_classes"], meta["iterations"], meta["batch_per_view"],
-                                   meta["seed"])
-    return meta, rec, fwd_meta, net, opt, sched, batches
-
-
 @pytest.mark.parametrize("name", COUNT)
 def test_count_finetune_iterations_match_reference(gpu, name):
     """The reference's own train_pipnet(finetune=True, is_count_pipnet=True) run, replayed on
@@ -691,33 +592,6 @@ def test_count_train_pipnet_epoch(gpu):
                               finetune=True)
     assert len(info["lrs_class"]) == len(batches)
     assert np.isfinite(info["loss"]) and info["loss"] > 0
-
-
-# ---- CountPIPNet pretrain / joint: backbone suffix + add-on (+ classifier + intermediate) ----
-def _count_suffix_setup(name, gpu):
-    meta, rec, fwd_meta = load_train_golden(name)
-    net = build_model(fwd_meta).to(gpu).train()
-    pmeta = dict(meta, phase=meta["phase"][len("count_"):])
-    opt_net, opt_cls, sched_net, sched_cls = _optimizers_like_reference(net, pmeta, fwd_meta)
-    pretrain = pmeta["phase"] == "pretrain"
-    inter = list(net._intermediate.parameters())
-    if inter:                    # train_intermediate=True (util/args.py:318-321); main.py:251-253, 386-388
-        opt_cls.add_param_group({"params": inter, "lr": meta["lr"], "weight_decay": meta["weight_decay"]})
-        for prm in inter:
-            prm.requires_grad = not pretrain
-        sched_cls = torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(opt_cls, T_0=10, eta_min=0.001, T_mult=1)
-    c = fwd_meta["case"]
-    batches = train_loader_batches(c["size"], c["num_classes"], meta["iterations"], meta["batch_per_view"],
-                                   meta["seed"])
-    return meta, rec, fwd_meta, net, opt_net, opt_cls, sched_net, sched_cls, pretrain, batches
-
-
-def _inject_noise(net, meta, rec, i, gpu):
-    from count_pipnet_amd.count_pipnet_utils import GumbelSoftmax
-    from count_pipnet_amd.synthetic import synth_exponential
-    act = list(net._add_on)[-1]
-    if isinstance(act, GumbelSoftmax):
-        act.exp_noise = synth_exponential(tuple(rec[f"s{i}_proto"].shape), meta["noise_seed"] + i).to(gpu)
 
 
 @pytest.mark.parametrize("name", COUNT_SUFFIX)
