@@ -118,6 +118,8 @@ SIGNATURES = {
     "pipnet_attr_stem_dx_f32": [P, P, I32, I32, I32, I32, I64, P, P],
     "pipnet_attr_path_weights_f32": [P, P, P, I32, I32, F32, P, P, P],
     "pipnet_attr_path_reduce_f32": [P, I64, P, P, P, F32, I32, I64, P, P],
+    "pipnet_proto_stats_update_f32": [P, I64, P, I32, I32, I32, F32, P, I32, P, P, P, P, P, P, P, P, P],
+    "pipnet_colsum_accum_f64": [P, I64, I32, I32, P, P],
 }
 _RESTYPE_EXTRA = {"pipnet_wgrad_workspace_bytes": ctypes.c_int64, "pipnet_train_partials_floats": ctypes.c_int64,
                   "pipnet_bn_workspace_floats": ctypes.c_int64,

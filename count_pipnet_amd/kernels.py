@@ -774,6 +774,79 @@ def topk_update(state: TopkState, score: Tensor, loc: Tensor, i0: int, group: Op
     return state
 
 
+PROTO_STATS_MAX_BINS = 1024      # include/pipnet_amd.h PIPNET_PROTO_STATS_MAX_BINS
+
+
+class ProtoStatsState:
+    """Device state of the streaming class-conditional statistics (pipnet_proto_stats_update_f32):
+    per (class, prototype) the counters, fp64 sums, maximum and histogram so far, the images per
+    class and the count of labels outside [0, classes).  ``edges``: ascending fp32 [NB + 1], or
+    None for no histogram."""
+
+    def __init__(self, classes: int, prototypes: int, threshold: float, edges: Optional[Tensor], device):
+        if classes < 1 or prototypes < 1:
+            raise ValueError("prototype statistics: need at least one class and one prototype")
+        if edges is not None:
+            edges = torch.as_tensor(edges, dtype=torch.float32).to(device).contiguous()
+            if edges.dim() != 1 or not 2 <= edges.numel() <= PROTO_STATS_MAX_BINS + 1:
+                raise ValueError(f"prototype statistics: edges must be 1-D with 2..{PROTO_STATS_MAX_BINS + 1} "
+                                 f"entries, got {tuple(edges.shape)}")
+        self.classes, self.prototypes, self.edges = classes, prototypes, edges
+        self.bins = 0 if edges is None else edges.numel() - 1
+        self.threshold = float(torch.tensor(threshold, dtype=torch.float32))     # the fp32 value compared against
+        kp = (classes, prototypes)
+        self.n_class = torch.zeros((classes,), device=device, dtype=torch.int64)
+        self.n_ge = torch.zeros(kp, device=device, dtype=torch.int64)
+        self.n_gt = torch.zeros(kp, device=device, dtype=torch.int64)
+        self.total = torch.zeros(kp, device=device, dtype=torch.float64)
+        self.total_gt = torch.zeros(kp, device=device, dtype=torch.float64)
+        self.vmax = torch.full(kp, float("-inf"), device=device, dtype=torch.float32)
+        self.hist = torch.zeros(kp + (self.bins,), device=device, dtype=torch.int32)
+        self.bad = torch.zeros((1,), device=device, dtype=torch.int64)
+
+    def tensors(self):
+        return (self.n_class, self.n_ge, self.n_gt, self.total, self.total_gt, self.vmax, self.hist, self.bad)
+
+
+def proto_stats_update(state: ProtoStatsState, act: Tensor, labels: Tensor) -> ProtoStatsState:
+    """Merge one batch into ``state``: act [B,P] float32 (any row stride, unit column stride), labels
+    [B] int64 on the device; a label outside [0, classes) only raises ``state.bad``.  Every entry is
+    accumulated in image order by one owner thread, so the state does not depend on the batching.
+    Enqueues one kernel, no host sync."""
+    require_device(act, "prototype activations")
+    if act.dim() != 2 or act.shape[1] != state.prototypes or (act.stride(1) != 1 and act.shape[1] > 1):
+        raise RuntimeError(f"proto_stats_update: act {tuple(act.shape)} (strides {act.stride()}) must be "
+                           f"[B, {state.prototypes}] with unit column stride")
+    b, p = act.shape
+    if tuple(labels.shape) != (b,) or labels.dtype != torch.int64 or labels.device != act.device \
+            or not labels.is_contiguous():
+        raise RuntimeError("proto_stats_update: labels must be a contiguous int64 tensor [B] on act's device")
+    if state.n_ge.device != act.device:
+        raise RuntimeError("proto_stats_update: state and activations are on different devices")
+    if b == 0:
+        return state
+    lda = act.stride(0) if b > 1 else max(act.stride(0), p)
+    _lib.call("pipnet_proto_stats_update_f32", act.data_ptr(), lda, labels.data_ptr(), b, p, state.classes,
+              state.threshold, _ptr(state.edges), state.bins, *[t.data_ptr() for t in state.tensors()], _stream(act))
+    return state
+
+
+def colsum_accum_f64(acc: Tensor, x: Tensor) -> Tensor:
+    """acc [D] float64 += the column sums of x [B,D] float32 (any row stride), the rows added in
+    order by one owner thread per column (pipnet_colsum_accum_f64).  One kernel, no host sync."""
+    require_device(x, "colsum_accum_f64 input")
+    if x.dim() != 2 or (x.stride(1) != 1 and x.shape[1] > 1):
+        raise RuntimeError(f"colsum_accum_f64: x {tuple(x.shape)} must be 2-D with unit column stride")
+    b, d = x.shape
+    if tuple(acc.shape) != (d,) or acc.dtype != torch.float64 or acc.device != x.device or not acc.is_contiguous():
+        raise RuntimeError(f"colsum_accum_f64: acc must be a contiguous float64 tensor [{d}] on x's device")
+    if b == 0:
+        return acc
+    _lib.call("pipnet_colsum_accum_f64", x.data_ptr(), x.stride(0) if b > 1 else max(x.stride(0), d), b, d,
+              acc.data_ptr(), _stream(x))
+    return acc
+
+
 LOCAL_EXPLAIN_MAX = 2048         # prototypes / classes per image (csrc/explain.hip LX_MAX)
 
 

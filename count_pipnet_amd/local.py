@@ -54,12 +54,17 @@ class LocalExplanation:
                                             else getattr(self, f.name)) for f in fields(self)})
 
 
-def count_importance_matrix(net) -> Tensor:
-    """[K, P] with column p = ``net.get_prototype_importance_per_class(p)``: what one unit of
-    prototype p's classifier inputs adds to each class.  ``vis_pred`` indexes
+def count_importance_matrix(net, classifier_input_scalars: Optional[Tensor] = None) -> Tensor:
+    """[K, P] with column p = ``net.get_prototype_importance_per_class(p, classifier_input_scalars)``:
+    what one unit of prototype p's classifier inputs adds to each class.  ``vis_pred`` indexes
     ``_classification.weight[c, p]``, which means that only while the classifier's input width is
-    P; for the identity intermediate layer the two are equal."""
-    return torch.stack([net.get_prototype_importance_per_class(p) for p in range(net._num_prototypes)], dim=1)
+    P; for the identity intermediate layer the two are equal.  With scalars (the dataset's mean
+    intermediate features) it is the virtual classification matrix of count_pipnet.py:312-321."""
+    if classifier_input_scalars is not None:      # the layer builds its input weights where it likes (one-hot: host)
+        classifier_input_scalars = classifier_input_scalars.to(
+            net._intermediate.prototype_to_classifier_input_weights(0).device)
+    return torch.stack([net.get_prototype_importance_per_class(p, classifier_input_scalars)
+                        for p in range(net._num_prototypes)], dim=1)
 
 
 def _map_is_small(net, xs: Tensor) -> Optional[bool]:

@@ -706,6 +706,36 @@ int pipnet_attr_path_reduce_f32(const float* grads, int64_t ldg, const float* we
                                 const float* baseline, float baseline_value, int S, int64_t N, float* out,
                                 void* stream);
 
+/* ---- class-conditional prototype activation statistics (util/histograms.py:206-209, 320,
+ * 521-522, 590-591, 617-661, 687-707, 1031-1065; pipnet/count_pipnet.py:272-276: the dataset
+ * mean behind the virtual weights; csrc/proto_stats.hip) -------------------------------------
+ * pipnet_proto_stats_update_f32: one batch merged into the running per-(class, prototype)
+ *   statistics.  act [B,P] fp32 with row stride lda >= P, labels [B] int64, thr the near-zero
+ *   threshold, edges [NB+1] ascending fp32 (NB == 0: no histogram, edges / hist not read).
+ *   State (caller-owned, device, zeroed before the first call; vmax starts at -inf):
+ *     n_class [K] int64 images of class k;  n_ge / n_gt [K,P] int64 act >= thr / act > thr;
+ *     total [K,P] fp64 sum of act;  total_gt [K,P] fp64 sum of act over act > thr;
+ *     vmax [K,P] fp32 largest act (NaN passed over);
+ *     hist [K,P,NB] int32 over the values with act > thr: bin i holds edges[i] <= act < edges[i+1],
+ *       the last bin also act == edges[NB], values outside [edges[0], edges[NB]] (and NaN) are
+ *       not counted -- np.histogram(values, bins=edges);
+ *     bad [1] int64 labels outside [0, K): such an image changes nothing else.
+ *   Every (k, p) entry of the state is owned by one thread, which walks the batch's images in
+ *   order and updates with plain loads and stores (no floating-point atomic, no cross-thread
+ *   sum): counters and both fp64 sums are accumulated in dataset order and are bitwise
+ *   independent of how the dataset is cut into batches.
+ *   1 <= B, P, K; lda >= P; 0 <= NB <= PIPNET_PROTO_STATS_MAX_BINS; a violation or a NULL pointer
+ *   returns PIPNET_ERR_ARG before any HIP call.
+ * pipnet_colsum_accum_f64: acc[d] += sum_b x[b][d] for x [B,D] fp32 (row stride ldx >= D) and
+ *   acc [D] fp64, the images added in order by the one thread that owns column d (the streaming
+ *   form of intermediate_features.mean(dim=0)).  1 <= B, D; same argument rule. */
+#define PIPNET_PROTO_STATS_MAX_BINS 1024
+int pipnet_proto_stats_update_f32(const float* act, int64_t lda, const int64_t* labels, int B, int P, int K, float thr,
+                                  const float* edges, int NB, int64_t* n_class, int64_t* n_ge, int64_t* n_gt,
+                                  double* total, double* total_gt, float* vmax, int32_t* hist, int64_t* bad,
+                                  void* stream);
+int pipnet_colsum_accum_f64(const float* x, int64_t ldx, int B, int D, double* acc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
