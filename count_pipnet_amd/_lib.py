@@ -120,6 +120,11 @@ SIGNATURES = {
     "pipnet_attr_path_reduce_f32": [P, I64, P, P, P, F32, I32, I64, P, P],
     "pipnet_proto_stats_update_f32": [P, I64, P, I32, I32, I32, F32, P, I32, P, P, P, P, P, P, P, P, P],
     "pipnet_colsum_accum_f64": [P, I64, I32, I32, P, P],
+    "pipnet_part_purity_update": [P, I64, P, P, I32, I32, I64, F64, I32, I32, I32, I32, I32, P, P, P, I64, P, P, P, I32,
+                                  I32, P, P, P, P, P, P],
+    "pipnet_part_purity_rows": [P, P, P, I32, I32, I32, I32, I32, I32, I32, P, P, P, I64, P, P, P, I32, I32, P, P, P, P,
+                                P, P],
+    "pipnet_part_purity_finish": [P, P, P, P, I32, I32, P, P, P, P, P, P, P, P, P],
 }
 _RESTYPE_EXTRA = {"pipnet_wgrad_workspace_bytes": ctypes.c_int64, "pipnet_train_partials_floats": ctypes.c_int64,
                   "pipnet_bn_workspace_floats": ctypes.c_int64,

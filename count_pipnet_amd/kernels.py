@@ -847,6 +847,116 @@ def colsum_accum_f64(acc: Tensor, x: Tensor) -> Tensor:
     return acc
 
 
+PART_PURITY_MAX_PARTS = 32       # include/pipnet_amd.h PIPNET_PART_PURITY_MAX_PARTS
+
+
+class PartPurityState:
+    """Device state of the part-purity evaluation (pipnet_part_purity_update / _rows): per
+    (prototype, merged part) the rows in which the part is visible, those in which it lies in the
+    patch and the key of its first appearance; the rows per prototype; the count of dataset indices
+    outside the annotation table.  All integer."""
+
+    def __init__(self, prototypes: int, merged_parts: int, device):
+        if prototypes < 1 or not 1 <= merged_parts <= PART_PURITY_MAX_PARTS:
+            raise ValueError(f"part purity: needs at least one prototype and 1..{PART_PURITY_MAX_PARTS} merged parts")
+        self.prototypes, self.merged_parts = prototypes, merged_parts
+        pm = (prototypes, merged_parts)
+        self.n = torch.zeros(pm, device=device, dtype=torch.int64)
+        self.hits = torch.zeros(pm, device=device, dtype=torch.int64)
+        self.first_key = torch.full(pm, -1, device=device, dtype=torch.int64)      # the bits of uint64 all ones
+        self.rows = torch.zeros((prototypes,), device=device, dtype=torch.int64)
+        self.bad = torch.zeros((1,), device=device, dtype=torch.int64)
+
+    def tensors(self):
+        return (self.n, self.hits, self.first_key, self.rows, self.bad)
+
+
+def _part_table_args(state: PartPurityState, table, relevant: Tensor, geometry, what: str):
+    """Checked (geometry + annotation table + state) argument tail shared by the two row kernels.
+    ``table``: (xy [N,Q,2] float64, vis [N,Q] uint8, size [N,2] int32, merged [Q] int32, is_left [Q]
+    uint8, pair_index [Q] int32); ``geometry``: (H, W, image_size, skip, small_map)."""
+    xy, vis, size, merged, is_left, pair_index = table
+    dev = state.n.device
+    n_img, q = vis.shape
+    want = ((xy, (n_img, q, 2), torch.float64), (vis, (n_img, q), torch.uint8), (size, (n_img, 2), torch.int32),
+            (merged, (q,), torch.int32), (is_left, (q,), torch.uint8), (pair_index, (q,), torch.int32),
+            (relevant, (state.prototypes,), torch.uint8))
+    for t, shape, dtype in want:
+        if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous() or not t.is_cuda:
+            raise RuntimeError(f"{what}: expected a contiguous {dtype} device tensor {shape} on {dev}, got "
+                               f"{tuple(t.shape)} {t.dtype} on {t.device}")
+    h, w, image_size, skip, small_map = geometry
+    return (int(h), int(w), int(image_size), int(skip), 1 if small_map else 0, xy.data_ptr(), vis.data_ptr(),
+            size.data_ptr(), n_img, merged.data_ptr(), is_left.data_ptr(), pair_index.data_ptr(), q,
+            state.merged_parts, *[t.data_ptr() for t in state.tensors()])
+
+
+def part_purity_update(state: PartPurityState, pooled: Tensor, loc: Tensor, relevant: Tensor, i0: int,
+                       threshold: float, geometry, table) -> PartPurityState:
+    """Merge the rows of one batch (mode "all"): image b is dataset index ``i0 + b``; prototype p
+    with ``relevant[p]`` and ``pooled[b, p] > threshold`` gives a row whose patch follows from
+    ``loc[b, p]``.  pooled [B,P] float32 (any row stride, unit column stride), loc [B,P] int32.
+    One owner thread per prototype walks the images in order: the state does not depend on the
+    batching.  Enqueues one kernel, no host sync."""
+    require_device(pooled, "pooled scores")
+    if pooled.dim() != 2 or pooled.shape[1] != state.prototypes or (pooled.stride(1) != 1 and pooled.shape[1] > 1):
+        raise RuntimeError(f"part_purity_update: pooled {tuple(pooled.shape)} (strides {pooled.stride()}) must be "
+                           f"[B, {state.prototypes}] with unit column stride")
+    b, p = pooled.shape
+    if tuple(loc.shape) != (b, p) or loc.dtype != torch.int32 or loc.device != pooled.device or not loc.is_contiguous():
+        raise RuntimeError("part_purity_update: loc must be a contiguous int32 tensor [B, P] on pooled's device")
+    if state.n.device != pooled.device:
+        raise RuntimeError("part_purity_update: state and scores are on different devices")
+    tail = _part_table_args(state, table, relevant, geometry, "part_purity_update")
+    if b == 0:
+        return state
+    lda = pooled.stride(0) if b > 1 else max(pooled.stride(0), p)
+    _launch("part_purity_update_kernel", 0.0,
+            lambda: _lib.call("pipnet_part_purity_update", pooled.data_ptr(), lda, loc.data_ptr(), relevant.data_ptr(),
+                              b, p, int(i0), float(threshold), *tail, _stream(pooled)))
+    return state
+
+
+def part_purity_rows(state: PartPurityState, index: Tensor, loc: Tensor, relevant: Tensor, geometry,
+                     table) -> PartPurityState:
+    """Merge explicit rows (mode "topk"): index [P,k] int64 dataset indices (< 0: empty slot) and loc
+    [P,k] int32 of a top-k state; slot j of a relevant prototype is its j-th row.  One kernel."""
+    if index.dim() != 2 or index.shape[0] != state.prototypes or not 1 <= index.shape[1] <= 32:
+        raise RuntimeError(f"part_purity_rows: index {tuple(index.shape)} must be [{state.prototypes}, k <= 32]")
+    dev = state.n.device
+    for t, dtype in ((index, torch.int64), (loc, torch.int32)):
+        if t.shape != index.shape or t.dtype != dtype or t.device != dev or not t.is_cuda or not t.is_contiguous():
+            raise RuntimeError("part_purity_rows: index (int64) and loc (int32) must be contiguous device tensors "
+                               "of one shape on the state's device")
+    tail = _part_table_args(state, table, relevant, geometry, "part_purity_rows")
+    _launch("part_purity_rows_kernel", 0.0,
+            lambda: _lib.call("pipnet_part_purity_rows", index.data_ptr(), loc.data_ptr(), relevant.data_ptr(),
+                              state.prototypes, index.shape[1], *tail, _stream(index)))
+    return state
+
+
+def part_purity_finish(state: PartPurityState):
+    """The per-prototype results of the reference's evaluation loop from ``state``: (in_csv [P] bool,
+    max_purity [P] float64, max_part [P] int32, max_sum [P] int64, most_part [P] int32 (-1: none),
+    most_sum [P] int64, most_purity [P] float64, purity [P,M] float64 with NaN where the part never
+    was visible).  One kernel, no host sync."""
+    dev = state.n.device
+    if not state.n.is_cuda:
+        raise RuntimeError("part_purity_finish: the state must be on a ROCm device; there is no CPU fallback")
+    p, m = state.prototypes, state.merged_parts
+    in_csv = torch.empty((p,), device=dev, dtype=torch.uint8)
+    f64 = [torch.empty((p,), device=dev, dtype=torch.float64) for _ in range(2)]
+    i32 = [torch.empty((p,), device=dev, dtype=torch.int32) for _ in range(2)]
+    i64 = [torch.empty((p,), device=dev, dtype=torch.int64) for _ in range(2)]
+    purity = torch.empty((p, m), device=dev, dtype=torch.float64)
+    _launch("part_purity_finish_kernel", 0.0,
+            lambda: _lib.call("pipnet_part_purity_finish", state.n.data_ptr(), state.hits.data_ptr(),
+                              state.first_key.data_ptr(), state.rows.data_ptr(), p, m, in_csv.data_ptr(),
+                              f64[0].data_ptr(), i32[0].data_ptr(), i64[0].data_ptr(), i32[1].data_ptr(),
+                              i64[1].data_ptr(), f64[1].data_ptr(), purity.data_ptr(), _stream(state.n)))
+    return in_csv.bool(), f64[0], i32[0], i64[0], i32[1], i64[1], f64[1], purity
+
+
 LOCAL_EXPLAIN_MAX = 2048         # prototypes / classes per image (csrc/explain.hip LX_MAX)
 
 

@@ -110,9 +110,10 @@ def _unwrap(net):
     return net
 
 
-def _pipnet_batch(net, xs: Tensor, small_map: Optional[bool]):
+def _pipnet_batch(net, xs: Tensor, small_map: Optional[bool], with_raw: bool = False):
     """(clamped pooled [B,P], loc [B,P], logits [B,K], (H, W)) of one batch: PIPNet._forward_hip with
     the arg-location head in place of softmax_pool, the proto map not stored (fp32 logits).
+    ``with_raw``: the unclamped pooled values [B,P] (the non-inference forward's) as a fifth item.
 
     Every image gets the bits of its own batch-1 forward, whatever the batch: on maps of more than
     K.SPLITK_MAX_M pixels the forward's kernels never see the batch size (``small_map`` False: the
@@ -140,7 +141,8 @@ def _pipnet_batch(net, xs: Tensor, small_map: Optional[bool]):
     with K.per_image_gemm_plan(b if n == 1 else 1):    # n > 1: the plain forward's concurrent sub-batches
         streams, logits = sub_batch_logits(net, xs, n)
     run_heads(streams, logits, head)
-    return clamped, loc, out, tuple(logits[0].shape[1:3])
+    hw = tuple(logits[0].shape[1:3])
+    return (clamped, loc, out, hw, pooled) if with_raw else (clamped, loc, out, hw)
 
 
 def _count_lut(class_to_count: Dict[Tuple[int, int], int]):

@@ -736,6 +736,54 @@ int pipnet_proto_stats_update_f32(const float* act, int64_t lda, const int64_t* 
                                   void* stream);
 int pipnet_colsum_accum_f64(const float* x, int64_t ldx, int B, int D, double* acc, void* stream);
 
+/* ---- prototype part purity (util/eval_cub_csv.py:16-175 evaluated from the rows of :178-215
+ * "all" and :218-283 "topk"; csrc/part_purity.hip, row function csrc/part_purity_row.hpp) ------
+ * A row is (prototype p, image i, loc = h_idx * W + w_idx of p's maximum in i).  Its patch is
+ * util/vis_pipnet.py get_img_coordinates for the map shape (P, H, W) with patch size 32 and the
+ * given skip (small_map != 0: the 26 x 26 small-stride rule), scaled to the original image in
+ * fp64 as (height / (double)image_size) * h (width for w); a visible part (x, y) is in the patch
+ * iff hmin <= y <= hmax and wmin <= x <= wmax.
+ * Annotation table (device, whole dataset): xy [N,Q,2] fp64 (x, y), vis [N,Q] uint8, size [N,2]
+ *   int32 (width, height); fold table merged [Q] int32 (merged part 0 .. M-1 of each id),
+ *   is_left [Q] uint8 (the id is folded into its right partner), pair_index [Q] int32 (a left
+ *   id's pair, in pair order).
+ * State (caller-owned, device): n / hits [P,M] int64 zeroed (rows in which a member of m is
+ *   visible / in which a visible member lies in the patch); first_key [P,M] uint64 all ones
+ *   (smallest ordinal << 6 | slot over the rows in which m is present, slot = the visible own
+ *   id's index q, or Q + pair_index through the left partner only: the insertion order of the
+ *   reference's dict); rows [P] int64 zeroed; bad [1] int64 zeroed (dataset indices outside
+ *   [0, N): such a row changes nothing else).
+ * pipnet_part_purity_update ("all"): image b of the batch is dataset index i0 + b and gives a row
+ *   for every p with relevant[p] != 0 and (double)pooled[b][p] > threshold (pooled [B,P] fp32, row
+ *   stride lda >= P; loc [B,P] int32), ordinal i0 + b.  One owner thread per prototype walks the
+ *   images in order with plain loads and stores: the state is bitwise independent of the batching.
+ * pipnet_part_purity_rows ("topk"): index / loc [P,k] (a top-k state, k <= 32): slot j of a
+ *   relevant p is a row with ordinal j; index < 0 is an empty slot.
+ * pipnet_part_purity_finish: per prototype, over its present parts in ascending first_key:
+ *   purity = hits / n (fp64); max_purity / max_part / max_sum by the reference's rules (higher
+ *   purity; at equal non-zero purity the strictly larger hits; at purity 0 the last part), most_part
+ *   / most_sum / most_purity of the first part with the strictly largest hits > 0 (-1, 0, 0 when
+ *   none), in_csv = rows > 0, purity [P,M] (NaN where n == 0).
+ * 1 <= B, P, k, N, H, W; B * P <= INT_MAX; 1 <= M <= Q <= PIPNET_PART_PURITY_MAX_PARTS;
+ * image_size >= 32; skip >= 0; a violation or a NULL pointer returns PIPNET_ERR_ARG before any
+ * HIP call. */
+#define PIPNET_PART_PURITY_MAX_PARTS 32
+int pipnet_part_purity_update(const float* pooled, int64_t lda, const int32_t* loc, const uint8_t* relevant, int B,
+                              int P, int64_t i0, double threshold, int H, int W, int image_size, int skip,
+                              int small_map, const double* xy, const uint8_t* vis, const int32_t* size, int64_t N,
+                              const int32_t* merged, const uint8_t* is_left, const int32_t* pair_index, int Q, int M,
+                              int64_t* n, int64_t* hits, uint64_t* first_key, int64_t* rows, int64_t* bad,
+                              void* stream);
+int pipnet_part_purity_rows(const int64_t* index, const int32_t* loc, const uint8_t* relevant, int P, int k, int H,
+                            int W, int image_size, int skip, int small_map, const double* xy, const uint8_t* vis,
+                            const int32_t* size, int64_t N, const int32_t* merged, const uint8_t* is_left,
+                            const int32_t* pair_index, int Q, int M, int64_t* n, int64_t* hits, uint64_t* first_key,
+                            int64_t* rows, int64_t* bad, void* stream);
+int pipnet_part_purity_finish(const int64_t* n, const int64_t* hits, const uint64_t* first_key, const int64_t* rows,
+                              int P, int M, uint8_t* in_csv, double* max_purity, int32_t* max_part, int64_t* max_sum,
+                              int32_t* most_part, int64_t* most_sum, double* most_purity, double* purity,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif
