@@ -9,6 +9,9 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
+
+from .build import REPO, source_digest
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PIPNET_AMD_LIB") or os.path.join(_HERE, "libpipnet_amd.so")    # env: A/B builds (tools)
@@ -20,131 +23,56 @@ U64 = ctypes.c_uint64
 F32 = ctypes.c_float
 F64 = ctypes.c_double
 
-# name -> argtypes (restype is int status unless listed in _RESTYPE)
-SIGNATURES = {
-    "pipnet_amd_abi_version": [],
-    "pipnet_amd_status_string": [I32],
-    "pipnet_amd_source_digest": [],
-    "pipnet_linear_f32": [P, I64, P, P, P, P, I64, P, I64, I32, I32, I32, I32, P],
-    "pipnet_linear_rowscale_f32": [P, I64, P, P, P, P, I64, P, I64, I32, I32, I32, P, I32, P],
-    "pipnet_linear_splitk_f32": [P, I64, P, P, P, P, I64, P, I64, I32, I32, I32, I32, I32, P, P],
-    "pipnet_linear_pair_mul_f32": [P, I64, P, P, I64, I32, I32, I32, I32, P, P],
-    "pipnet_matmul_f64acc_f32": [P, I64, P, I64, P, I64, I32, I32, I32, P],
-    "pipnet_matmul2_f64acc_f32": [P, P, I64, P, I64, P, P, I64, I32, I32, I32, P],
-    "pipnet_conv2x2_f32": [P, I32, I32, I32, I32, P, P, I32, I32, P, P],
-    "pipnet_convnext_stem_f32": [P, I32, I32, I32, P, P, P, P, P, P],
-    "pipnet_conv2d_nhwc_f32": [P, I32, I32, I32, I32, P, P, I32, I32, I32, I32, I32, P, I32, P, P],
-    "pipnet_maxpool2d_nhwc_f32": [P, I32, I32, I32, I32, I32, I32, I32, P, P],
-    "pipnet_nchw_to_nhwc_f32": [P, I32, I32, I32, I32, I32, P, P],
-    "pipnet_conv2d_nhwc_bf16": [P, I32, I32, I32, I32, P, P, I32, I32, I32, I32, I32, P, I32, P, P],
-    "pipnet_conv2d_nhwc_bf16_tile": [P, I32, I32, I32, I32, P, P, I32, I32, I32, I32, I32, P, I32, P, I32, P],
-    "pipnet_conv2d_nhwc_bf16_plan": [I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32],
-    "pipnet_linear_f32_plan": [I32, I32, I32, I32, I32],
-    "pipnet_linear_f32_label": [I32, I32, I32, I32, I32, I32, ctypes.c_char_p, I32],
-    "pipnet_conv2d_nhwc_bf16_label": [I32] * 11 + [ctypes.c_char_p, I32],
-    "pipnet_conv2d_nhwc_s3_label": [I32] * 11 + [ctypes.c_char_p, I32],
-    "pipnet_conv1x1_bf16_dual_label": [I64, I32, I32, I32, ctypes.c_char_p, I32],
-    "pipnet_cnblock_mlp_label": [I64, I32, I32, ctypes.c_char_p, I32],
-    "pipnet_count_gumbel_soft_f32": [P, I32, I32, I32, F32, P, U64, U64, P, P, P],
-    "pipnet_philox_exp1_f32": [U64, U64, I64, I32, P, P],
-    "pipnet_nonneg_linear_dx_f32": [P, P, I32, I32, I32, P, P],
-    "pipnet_bilinear_bwd_prep_f32": [P, P, P, I64, P, P, P],
-    "pipnet_linear_inter_partials_floats": [I32],
-    "pipnet_linear_inter_bwd_f32": [P, I64, I32, P, P, P, P, I32, P, P],
-    "pipnet_count_ste_bwd_f32": [P, I64, I32, I32, I32, P, P, P],
-    "pipnet_onehot_ste_bwd_f32": [P, I64, I32, P, I32, I32, P, P, P],
-    "pipnet_count_head_bwd_f32": [P, P, I32, I32, I32, P, F32, F32, F32, F32, P, P, P],
-    "pipnet_conv2d_nhwc_s3": [P, I32, I32, I32, I32, P, P, P, P, I32, I32, I32, I32, I32, I32, P, I32, P],
-    "pipnet_dwconv7_ln_s3": [P, I32, I32, I32, I32, P, P, P, P, P, P],
-    "pipnet_layernorm_s3": [P, I64, I32, P, P, P, P],
-    "pipnet_maxpool2d_nhwc_bf16": [P, I32, I32, I32, I32, I32, I32, I32, P, P],
-    "pipnet_nchw_to_nhwc_bf16": [P, I32, I32, I32, I32, I32, P, P],
-    "pipnet_nchw_to_s2d_bf16": [P, I32, I32, I32, P, P],
-    "pipnet_stem_pool_bf16": [P, I32, I32, I32, P, P, P, P],
-    "pipnet_conv1x1_bf16_dual": [P, I64, I32, P, P, I32, P, I32, P, P],
-    "pipnet_softmax_pool_bf16": [P, I32, I32, I32, I32, P, P, P],
-    "pipnet_eval_batch_f32": [P, P, P, I32, I32, I32, P, P, F32, P, P, P, P, P, P, P],
-    "pipnet_weight_sparsify_f32": [P, I64, F32, P],
-    "pipnet_dwconv7_ln_f32": [P, I32, I32, I32, I32, P, P, P, P, P, P],
-    "pipnet_layernorm_f32": [P, I64, I32, P, P, P, P],
-    "pipnet_softmax_pool_f32": [P, I32, I32, I32, I32, P, P, P],
-    "pipnet_softmax_pool_argmax_f32": [P, I32, I32, I32, I32, P, P, P, P, P],
-    "pipnet_map_argmax_f32": [P, I32, I32, I32, I32, P, P, P],
-    "pipnet_topk_update": [P, P, I32, I32, I64, P, I32, I32, F32, P, I32, I32, P, P, P, P, P, P],
-    "pipnet_local_explain_f32": [P, P, P, P, I64, I32, I32, I32, I32, I32, F64, P, P, P, P, P, P, P, P, P],
-    "pipnet_softmax_pool_linear_part_floats": [I32, I32, I32],
-    "pipnet_softmax_pool_linear_f32": [P, I32, I32, I32, P, P, P, P, I32, I32, F32, P, P, P, P, P],
-    "pipnet_softmax_pool_linear_bf16": [P, I32, I32, I32, P, P, P, P, I32, I32, F32, P, P, P, P, P],
-    "pipnet_nonneg_linear_f32": [P, I32, I32, P, P, I32, I32, F32, P, P, P],
-    "pipnet_count_gumbel_f32": [P, I32, I32, I32, F32, P, U64, U64, P, P, P],
-    "pipnet_count_gumbel_devseed_f32": [P, I32, I32, I32, F32, P, P, P, P],
-    "pipnet_count_finish_f32": [P, P, I32, I32, I32, I32, P, P, P],
-    "pipnet_count_encode_f32": [P, I32, I32, I32, I32, I32, P, P, P],
-    "pipnet_resize_plan": [P, I32, I32, I32, P, P],
-    "pipnet_resize_normalize_rgb8": [P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P, P],
-    "pipnet_augment_geometry_plan": [P, I32, I32, I32, P, P, P],
-    "pipnet_augment_geometry_rgb8": [P, P, P, P, I32, I32, I32, I32, I32, P, P, P],
-    "pipnet_augment_view_rgb8": [P, P, I32, I32, I32, I32, I32, P, P, F32, U64, P, P, P],
-    "pipnet_train_align_partials": [],
-    "pipnet_train_align_partial_f32": [P, I32, I32, I32, P, P],
-    "pipnet_train_loss_f32": [P, I32, I32, P, P, P, I32, I32, P, I32, F32, F32, F32, F32, I32, P, P, P],
-    "pipnet_nonneg_linear_bwd_f32": [P, P, I32, I32, P, I32, P, P, P],
-    "pipnet_adamw_step_f32": [P, P, P, P, I64, F64, F64, F64, F64, F64, I64, I32, F32, F32, P],
-    "pipnet_clamp_min_f32": [P, I64, F32, P],
-    "pipnet_wgrad_workspace_bytes": [I32, I32, I32],
-    "pipnet_wgrad_f32": [P, I64, P, I64, I32, I32, I32, P, I64, I32, P, P],
-    "pipnet_wgrad_conv2x2_f32": [P, P, I32, I32, I32, I32, I32, I32, P, I32, P, P],
-    "pipnet_wgrad_conv_f32": [P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, P, I32, P, P],
-    "pipnet_colsum_workspace_bytes": [I32],
-    "pipnet_colsum_f32": [P, I64, I32, I32, P, I32, P, P],
-    "pipnet_train_partials_floats": [I32],
-    "pipnet_gelu_fwd_f32": [P, P, I64, P],
-    "pipnet_resid_scale_f32": [P, P, P, P, I32, I64, I32, P, P],
-    "pipnet_ls_bwd_f32": [P, P, P, P, I32, I64, I32, P, P, P, I32, P, P],
-    "pipnet_ln_bwd_f32": [P, P, P, I64, I32, P, P, P, I32, P, P],
-    "pipnet_dwconv7_plain_f32": [P, I32, I32, I32, I32, P, P, I32, P, P],
-    "pipnet_dwconv7_wgrad_f32": [P, P, I32, I32, I32, I32, P, P, I32, P, P],
-    "pipnet_head_bwd_f32": [P, P, I32, I32, I32, P, P, I32, F32, F32, F32, P, P, P, P],
-    "pipnet_cnblock_mlp_f32": [P, P, P, P, P, P, P, I64, I32, P],
-    "pipnet_cnblock_mlp_hw_f32": [P, P, P, P, P, P, P, I64, I32, I32, P],
-    "pipnet_bn_workspace_floats": [I32],
-    "pipnet_bn_slabs": [I64, I32],
-    "pipnet_bn_stats_f32": [P, I64, I32, F32, F32, P, P, P, P, P, P],
-    "pipnet_bn_apply_f32": [P, I64, I32, P, P, P, P, P, I32, P, P],
-    "pipnet_bn_backward_f32": [P, P, P, I64, I32, P, P, P, P, P, P, P, P, P],
-    "pipnet_stride_scatter_f32": [P, I32, I32, I32, I32, I32, I32, I32, I32, P, P],
-    "pipnet_attr_path_images_f32": [P, P, F32, P, I32, I32, I32, P, P],
-    "pipnet_attr_head_bwd_f32": [P, P, P, I32, I32, I32, I32, F32, P, P],
-    "pipnet_attr_stem_dx_f32": [P, P, I32, I32, I32, I32, I64, P, P],
-    "pipnet_attr_path_weights_f32": [P, P, P, I32, I32, F32, P, P, P],
-    "pipnet_attr_path_reduce_f32": [P, I64, P, P, P, F32, I32, I64, P, P],
-    "pipnet_proto_stats_update_f32": [P, I64, P, I32, I32, I32, F32, P, I32, P, P, P, P, P, P, P, P, P],
-    "pipnet_colsum_accum_f64": [P, I64, I32, I32, P, P],
-    "pipnet_part_purity_update": [P, I64, P, P, I32, I32, I64, F64, I32, I32, I32, I32, I32, P, P, P, I64, P, P, P, I32,
-                                  I32, P, P, P, P, P, P],
-    "pipnet_part_purity_rows": [P, P, P, I32, I32, I32, I32, I32, I32, I32, P, P, P, I64, P, P, P, I32, I32, P, P, P, P,
-                                P, P],
-    "pipnet_part_purity_finish": [P, P, P, P, I32, I32, P, P, P, P, P, P, P, P, P],
-}
-_RESTYPE_EXTRA = {"pipnet_wgrad_workspace_bytes": ctypes.c_int64, "pipnet_train_partials_floats": ctypes.c_int64,
-                  "pipnet_bn_workspace_floats": ctypes.c_int64,
-                  "pipnet_softmax_pool_linear_part_floats": ctypes.c_int64}
-_RESTYPE = {"pipnet_amd_status_string": ctypes.c_char_p, "pipnet_amd_source_digest": ctypes.c_char_p,
-            **_RESTYPE_EXTRA}
-
-EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_RESID, EPI_MUL, EPI_BIAS_RELU, EPI_BIAS_RESID_RELU = 0, 1, 2, 3, 4, 5, 6
-EPI_RESID_ROWSCALE = 7
-EPI_GELU_BWD = 8
-EPI_S3_GELU, EPI_F32_BIAS, EPI_F32_RESID = 9, 10, 11      # split-bf16 ("bf16x3") ConvNeXt path
-EPI_DUAL_BIAS_RELU = 12        # pipnet_conv1x1_bf16_dual: downsample + conv1 of a first Bottleneck
-
-ABI_VERSION = 4          # include/pipnet_amd.h PIPNET_AMD_ABI_VERSION
-
-_lib = None
-
 
 class PipnetLibraryError(RuntimeError):
     pass
+
+
+HEADER = os.path.join(REPO, "include", "pipnet_amd.h")
+_SCALARS = {"int": I32, "int64_t": I64, "uint64_t": U64, "float": F32, "double": F64}
+_RETURNS = {"int": I32, "int64_t": I64, "const char *": ctypes.c_char_p}
+
+
+def _argtype(param: str, decl: str):
+    toks = param.replace("*", " * ").split()
+    if "*" in toks:                      # every pointer is opaque, but a writable char* is a label buffer
+        return ctypes.c_char_p if toks[:2] == ["char", "*"] else P
+    ctype = _SCALARS.get(" ".join(toks[:-1]))
+    if ctype is None:
+        raise PipnetLibraryError(f"{HEADER}: no ctypes type for parameter '{param.strip()}' of {decl}")
+    return ctype
+
+
+def parse_header(text: str):
+    """(name -> argtypes, name -> restype, PIPNET_<NAME> -> int) of the C header ``text``: only the shapes
+    include/pipnet_amd.h uses (one-line integer #defines, ``type pipnet_name(params);`` over any lines)."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    consts = {m[1]: int(m[2]) for m in re.finditer(r"^[ \t]*#define[ \t]+PIPNET_(\w+)[ \t]+(-?\d+)[ \t]*$", text,
+                                                   flags=re.M)}
+    argtypes, restypes = {}, {}
+    for m in re.finditer(r"^[ \t]*([\w \t*]+?)(pipnet_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
+        ret, name, params = " ".join(m[1].replace("*", " * ").split()), m[2], m[3].strip()
+        if ret not in _RETURNS:
+            raise PipnetLibraryError(f"{HEADER}: no ctypes type for the return type '{ret}' of {name}")
+        restypes[name] = _RETURNS[ret]
+        argtypes[name] = [] if params == "void" else [_argtype(p, name) for p in params.split(",")]
+    return argtypes, restypes, consts
+
+
+def _read_header() -> str:
+    try:
+        with open(HEADER) as f:
+            return f.read()
+    except OSError as e:
+        raise PipnetLibraryError(f"{HEADER} is missing: the binding of {LIB_PATH} is read from it") from e
+
+
+# name -> argtypes / restype of every entry point, and the header's integer constants without the PIPNET_ prefix
+SIGNATURES, RESTYPES, CONSTANTS = parse_header(_read_header())
+globals().update({k: v for k, v in CONSTANTS.items() if k.startswith("EPI_")})       # _lib.EPI_NONE, ...
+ABI_VERSION = CONSTANTS["AMD_ABI_VERSION"]
+
+_lib = None
 
 
 def load() -> ctypes.CDLL:
@@ -161,7 +89,7 @@ def load() -> ctypes.CDLL:
     for name, args in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError = missing export = loud failure
         fn.argtypes = args
-        fn.restype = _RESTYPE.get(name, ctypes.c_int)
+        fn.restype = RESTYPES[name]
     _check_provenance(lib)
     if lib.pipnet_amd_abi_version() != ABI_VERSION:
         raise PipnetLibraryError(f"{LIB_PATH} exports ABI version {lib.pipnet_amd_abi_version()}, "
@@ -174,7 +102,6 @@ def _check_provenance(lib) -> None:
     """The library must have been compiled from the sources of this tree (sha256 compiled
     in by build.py).  ``PIPNET_AMD_ALLOW_STALE=1`` is the explicit A/B escape hatch (e.g. an
     experimental build loaded through ``PIPNET_AMD_LIB``)."""
-    from .build import source_digest
     built = lib.pipnet_amd_source_digest().decode()
     here = source_digest()
     if built != here and os.environ.get("PIPNET_AMD_ALLOW_STALE") != "1":

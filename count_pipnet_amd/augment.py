@@ -24,7 +24,9 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
-GEOM_PARAMS, VIEW_PARAMS = 13, 8              # include/pipnet_amd.h PIPNET_AUG_*_PARAMS
+from ._lib import CONSTANTS
+
+GEOM_PARAMS, VIEW_PARAMS = CONSTANTS["AUG_GEOM_PARAMS"], CONSTANTS["AUG_VIEW_PARAMS"]
 WARP_NONE, WARP_FIXED, WARP_DOUBLE = 0, 1, 2
 (OP_IDENTITY, OP_BRIGHTNESS, OP_COLOR, OP_CONTRAST, OP_SHARPNESS, OP_POSTERIZE, OP_SOLARIZE, OP_AUTOCONTRAST,
  OP_EQUALIZE) = range(9)

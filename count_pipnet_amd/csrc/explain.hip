@@ -176,7 +176,7 @@ struct TopkArgs {
 // which is fetched with the others at write-back.  The abstain blocks take TOPK_ROWS images each,
 // one wave reading a row of logits 64 columns at a time.
 constexpr int TOPK_THREADS = 64;
-constexpr int TOPK_MAX_K = 32;
+constexpr int TOPK_MAX_K = PIPNET_TOPK_MAX_K;
 constexpr int TOPK_CHUNK = 8;
 constexpr int TOPK_ROWS = 8;
 
@@ -338,7 +338,7 @@ extern "C" int pipnet_topk_update(const float* score, const int32_t* loc, int B,
 namespace {
 
 constexpr int LX_THREADS = 256;
-constexpr int LX_MAX = 2048;        // prototypes / classes per image: the head's largest nj_bucket
+constexpr int LX_MAX = PIPNET_LOCAL_EXPLAIN_MAX;        // prototypes / classes per image: the head's largest nj_bucket
 
 // float -> uint32 whose unsigned order is the float order (-0 made +0 first: equal values must
 // share their bits, the index half of the key breaks the tie); order_value is the inverse.

@@ -1,12 +1,14 @@
 """Tensor-level wrappers over the C-ABI (one function per HIP entry point).
 
-Every wrapper validates device / dtype / contiguity, allocates its outputs on the input's
-device and enqueues on torch's *current* HIP stream, so the calls compose with torch
-streams, events and graph capture.  Nothing here computes on the host.
+Every wrapper holds each tensor operand against ``_operand`` (dtype, device, size, layout) before its
+pointer reaches the library, allocates its outputs on the input's device and enqueues on torch's
+*current* HIP stream, so the calls compose with torch streams, events and graph capture.  Nothing
+here computes on the host.
 """
 from __future__ import annotations
 
 import contextlib
+import ctypes
 import functools
 import threading
 
@@ -53,19 +55,6 @@ def gemm_kernel_name(m: int, n: int, k: int, epilogue: int, aload: int, splits: 
     """The rocprof name of the GEMM instantiation the library launches (pipnet_linear_f32_label: dense,
     unit-stride, 16-B aligned torch operands); ``splits`` > 1: the split-K main kernel."""
     return _lib.label("pipnet_linear_f32_label", m, n, k, epilogue, aload, splits)
-
-
-_CUS = {}
-
-
-def _num_cus() -> int:
-    """CUs of the current device (per device, as the library's launch rule sees it)."""
-    if not torch.cuda.is_available():
-        return 256
-    d = torch.cuda.current_device()
-    if d not in _CUS:
-        _CUS[d] = torch.cuda.get_device_properties(d).multi_processor_count
-    return _CUS[d]
 
 
 SPLITK_WG_PER_CU = int(os.environ.get("PIPNET_SPLITK_WG_PER_CU", "2"))   # env: A/B runs (tools)
@@ -126,10 +115,41 @@ def require_device(t: Tensor, what: str = "input") -> None:
             "inputs to a GPU, or run the autograd path (train mode / grad enabled).")
 
 
+def _operand(fn: str, what: str, t: Optional[Tensor], dtype=torch.float32, shape=None, device=None,
+             layout: Optional[str] = "contiguous", optional: bool = False) -> None:
+    """The one operand test of this file.  The library only sees a pointer: a wrong dtype, device, size or
+    stride would read or write the wrong memory silently, so every tensor handed to it is first held
+    against what the entry point documents (include/pipnet_amd.h): a ``dtype`` ROCm tensor, on ``device``
+    (the primary operand's; None for the primary itself), of ``shape`` (a tuple, or an int: that many
+    elements, or None: any) and ``layout`` ("contiguous"; "rows": 2-D row-major with unit column stride;
+    None: any).  Attribute comparisons only: no host sync, no copy."""
+    if t is None:
+        if optional:
+            return
+        raise RuntimeError(f"{fn}: {what} is missing")
+    if not (t.is_cuda and t.dtype == dtype):           # the label is only built on the way to an error
+        if dtype is not torch.float32:
+            raise RuntimeError(f"count_pipnet_amd: {fn} {what} must be a {dtype} ROCm device tensor "
+                               f"(got device={t.device}, dtype={t.dtype}); there is no CPU fallback")
+        require_device(t, f"{fn} {what}")               # float32: the public check and its message
+    ok = device is None or t.device == device
+    if shape is not None:
+        ok = ok and (t.numel() == shape if isinstance(shape, int) else t.shape == shape)
+    if layout == "contiguous":
+        ok = ok and t.is_contiguous()
+    elif layout == "rows":
+        ok = ok and t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1) and \
+            (t.shape[0] <= 1 or t.stride(0) >= t.shape[1])
+    if not ok:
+        size = f"{shape} elements" if isinstance(shape, int) else f"shape {'any' if shape is None else tuple(shape)}"
+        kind = {"contiguous": "contiguous", "rows": "row-major (unit column stride)", None: "strided"}[layout]
+        raise RuntimeError(f"{fn}: {what} must be a {kind} {dtype} tensor of {size} on {device or t.device} "
+                           f"(got shape {tuple(t.shape)}, stride {t.stride()}, device {t.device})")
+
+
 def _chk(t: Tensor, what: str, contiguous: bool = True) -> None:
-    require_device(t, what)
-    if contiguous and not t.is_contiguous():
-        raise RuntimeError(f"count_pipnet_amd: {what} must be contiguous")
+    """A float32 primary operand (``what`` names the wrapper too)."""
+    _operand("count_pipnet_amd", what, t, layout="contiguous" if contiguous else None)
 
 
 _EPI_READS_R = (_lib.EPI_RESID, _lib.EPI_MUL, _lib.EPI_BIAS_RESID_RELU, _lib.EPI_RESID_ROWSCALE, _lib.EPI_GELU_BWD)
@@ -137,78 +157,49 @@ _EPI_READS_R = (_lib.EPI_RESID, _lib.EPI_MUL, _lib.EPI_BIAS_RESID_RELU, _lib.EPI
 
 def _chk_gemm_operands(fn: str, a: Tensor, m: int, n: int, epilogue: int, bias: Optional[Tensor],
                        scale: Optional[Tensor], r: Optional[Tensor], out: Optional[Tensor]) -> None:
-    """The library takes raw pointers: a wrong dtype, device, shape or stride of an epilogue operand
-    would read or write the wrong memory silently, so every one is checked before any launch."""
-    for t, what in ((bias, "bias"), (scale, "scale")):
-        if t is None:
-            continue
-        require_device(t, f"{fn} {what}")
-        if t.device != a.device or t.numel() != n or not t.is_contiguous():
-            raise RuntimeError(f"{fn}: {what} must be {n} contiguous floats on {a.device} "
-                               f"(got shape {tuple(t.shape)}, stride {t.stride()}, device {t.device})")
-    for t, what in ((r, "r"), (out, "out")):
-        if t is None:
-            continue
-        require_device(t, f"{fn} {what}")
-        if t.device != a.device or t.dim() != 2 or tuple(t.shape) != (m, n) or (n > 1 and t.stride(1) != 1) or \
-                (m > 1 and t.stride(0) < n):
-            raise RuntimeError(f"{fn}: {what} must be a ({m}, {n}) row-major view with unit column stride on "
-                               f"{a.device} (got shape {tuple(t.shape)}, stride {t.stride()}, device {t.device})")
+    """The epilogue operands of a GEMM: bias / scale [n], r / out (m, n) row-major views, on a's device."""
+    _chk_vec(fn, a, n, bias=bias, scale=scale)
+    _operand(fn, "r", r, shape=(m, n), device=a.device, layout="rows", optional=True)
+    _operand(fn, "out", out, shape=(m, n), device=a.device, layout="rows", optional=True)
     if r is None and epilogue in _EPI_READS_R:
         raise RuntimeError(f"{fn}: epilogue {epilogue} reads r, which is missing")
 
 
 def _chk_rows(fn: str, t: Tensor, what: str, ndim: int) -> None:
     """The primary operand of a training kernel: a contiguous float32 device tensor of ``ndim`` dimensions."""
-    require_device(t, f"{fn} {what}")
-    if t.dim() != ndim or not t.is_contiguous():
-        raise RuntimeError(f"{fn}: {what} must be a contiguous {ndim}-D tensor "
-                           f"(got shape {tuple(t.shape)}, stride {t.stride()})")
+    _operand(fn, what, t)
+    if t.dim() != ndim:
+        raise RuntimeError(f"{fn}: {what} must be a contiguous {ndim}-D tensor (got shape {tuple(t.shape)})")
 
 
 def _chk_same(fn: str, ref: Tensor, **operands: Optional[Tensor]) -> None:
     """Optional operands the library indexes exactly as ``ref``: same shape, contiguous, same device."""
     for what, t in operands.items():
-        if t is None:
-            continue
-        require_device(t, f"{fn} {what}")
-        if t.device != ref.device or t.shape != ref.shape or not t.is_contiguous():
-            raise RuntimeError(f"{fn}: {what} must be a contiguous {tuple(ref.shape)} tensor on {ref.device} "
-                               f"(got shape {tuple(t.shape)}, stride {t.stride()}, device {t.device})")
+        _operand(fn, what, t, shape=ref.shape, device=ref.device, optional=True)
 
 
-def _chk_vec(fn: str, ref: Tensor, n: int, at_least: bool = False, **operands: Optional[Tensor]) -> None:
-    """Optional per-channel (or per-row-group) operands: ``n`` contiguous floats (or more, ``at_least``)
-    on ``ref``'s device.  As for the GEMM epilogue operands the library only sees a pointer."""
+def _chk_vec(fn: str, ref: Tensor, n: int, **operands: Optional[Tensor]) -> None:
+    """Optional per-channel operands: ``n`` contiguous floats on ``ref``'s device."""
     for what, t in operands.items():
-        if t is None:
-            continue
-        require_device(t, f"{fn} {what}")
-        ok = t.numel() >= n if at_least else t.numel() == n
-        if t.device != ref.device or not ok or not t.is_contiguous():
-            raise RuntimeError(f"{fn}: {what} must be {'at least ' if at_least else ''}{n} contiguous floats on "
-                               f"{ref.device} (got shape {tuple(t.shape)}, stride {t.stride()}, device {t.device})")
+        _operand(fn, what, t, shape=n, device=ref.device, optional=True)
 
 
 def _chk_row_scale(fn: str, ref: Tensor, m: int, row_scale: Optional[Tensor], rows_per_scale: int) -> None:
-    if row_scale is None:
-        return
-    if rows_per_scale <= 0:
-        raise RuntimeError(f"{fn}: rows_per_scale must be positive with a row_scale (got {rows_per_scale})")
-    _chk_vec(fn, ref, -(-m // rows_per_scale), at_least=True, row_scale=row_scale)
+    _operand(fn, "row_scale", row_scale, device=ref.device, optional=True)
+    if row_scale is not None and (rows_per_scale <= 0 or row_scale.numel() * rows_per_scale < m):
+        raise RuntimeError(f"{fn}: row_scale ({row_scale.numel()} floats, {rows_per_scale} rows each) does not cover "
+                           f"{m} rows")
 
 
 def linear(a: Tensor, w: Tensor, bias: Optional[Tensor] = None, epilogue: int = _lib.EPI_NONE,
            scale: Optional[Tensor] = None, r: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
     """out[M,N] = epi(a[M,K] @ w[N,K]^T).  a, r and out may be any 2-D row-major views with unit col stride."""
-    require_device(a, "linear input")
-    _chk(w, "weight")
-    if a.dim() != 2 or w.dim() != 2 or a.stride(1) != 1 or w.device != a.device:
-        raise RuntimeError("linear: expects 2-D operands with unit column stride on one device")
+    _operand("linear", "input", a, layout="rows")
     m, k = a.shape
-    n = w.shape[0]
-    if w.shape[1] != k:
+    if w.dim() != 2 or w.shape[1] != k:
         raise RuntimeError(f"linear: K mismatch {tuple(a.shape)} x {tuple(w.shape)}")
+    _operand("linear", "weight", w, device=a.device)
+    n = w.shape[0]
     _chk_gemm_operands("linear", a, m, n, epilogue, bias, scale, r, out)
     if out is None:
         out = torch.empty((m, n), device=a.device, dtype=torch.float32)
@@ -231,11 +222,11 @@ def linear_pair_mul(a: Tensor, w_pair: Tensor) -> Tensor:
     """(a @ w_pair[Nh:]^T) * (a @ w_pair[:Nh]^T) for a [M,K] and w_pair [2 Nh, K] (the stacked
     folded BilinearIntermediate weights) as ONE split-K GEMM + one reduction that takes the product
     (include/pipnet_amd.h pipnet_linear_pair_mul_f32)."""
-    require_device(a, "linear input")
-    _chk(w_pair, "paired weight")
+    _operand("linear_pair_mul", "input", a, layout="rows")
     m, k = a.shape
+    _operand("linear_pair_mul", "paired weight", w_pair, device=a.device)
     n2 = w_pair.shape[0]
-    if a.stride(1) != 1 or w_pair.shape[1] != k or n2 % 2:
+    if w_pair.dim() != 2 or w_pair.shape[1] != k or n2 % 2:
         raise RuntimeError(f"linear_pair_mul: shapes {tuple(a.shape)} x {tuple(w_pair.shape)}")
     nh = n2 // 2
     splits = max(1, splitk_factor(m, n2, k))
@@ -250,8 +241,8 @@ def linear_pair_mul(a: Tensor, w_pair: Tensor) -> Tensor:
 def matmul_f64acc(a: Tensor, b: Tensor) -> Tensor:
     """[M,K] @ [K,N] (row-major fp32) with fp64 products and sums, rounded once to fp32
     (include/pipnet_amd.h pipnet_matmul_f64acc_f32): the inference-time weight folds."""
-    _chk(a, "fold operand A")
-    _chk(b, "fold operand B")
+    _operand("matmul_f64acc", "A", a)
+    _operand("matmul_f64acc", "B", b, device=a.device)
     if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[0]:
         raise RuntimeError(f"matmul_f64acc: shapes {tuple(a.shape)} x {tuple(b.shape)}")
     m, k = a.shape
@@ -264,9 +255,10 @@ def matmul_f64acc(a: Tensor, b: Tensor) -> Tensor:
 def matmul2_f64acc(a0: Tensor, a1: Tensor, b: Tensor) -> Tensor:
     """torch.stack((a0 @ b, a1 @ b)) ([2, M, N]) as ``matmul_f64acc`` in ONE launch
     (pipnet_matmul2_f64acc_f32): the bilinear fold's W.E and V.E share the embedding operand."""
-    for t, what in ((a0, "fold operand A0"), (a1, "fold operand A1"), (b, "fold operand B")):
-        _chk(t, what)
-    if a0.dim() != 2 or a0.shape != a1.shape or b.dim() != 2 or a0.shape[1] != b.shape[0]:
+    _operand("matmul2_f64acc", "A0", a0)
+    _operand("matmul2_f64acc", "A1", a1, shape=a0.shape, device=a0.device)
+    _operand("matmul2_f64acc", "B", b, device=a0.device)
+    if a0.dim() != 2 or b.dim() != 2 or a0.shape[1] != b.shape[0]:
         raise RuntimeError(f"matmul2_f64acc: shapes {tuple(a0.shape)}, {tuple(a1.shape)} x {tuple(b.shape)}")
     m, k = a0.shape
     n = b.shape[1]
@@ -280,19 +272,14 @@ def linear_rowscale(a: Tensor, w: Tensor, bias: Optional[Tensor], scale: Tensor,
                     rows_per_scale: int) -> Tensor:
     """In place on ``r`` ([M,N]): r = r + row_scale[m // rows_per_scale] * (scale * (a w^T + bias))
     (CNBlock Linear2 under train-mode stochastic depth)."""
-    require_device(a, "linear input")
-    _chk(w, "weight")
-    _chk(row_scale, "row scale")
-    if a.dim() != 2 or w.dim() != 2 or a.stride(1) != 1 or w.device != a.device or row_scale.device != a.device:
-        raise RuntimeError("linear_rowscale: expects 2-D operands with unit column stride on one device")
+    _operand("linear_rowscale", "input", a, layout="rows")
     m, k = a.shape
+    if w.dim() != 2 or w.shape[1] != k:
+        raise RuntimeError(f"linear_rowscale: K mismatch {tuple(a.shape)} x {tuple(w.shape)}")
+    _operand("linear_rowscale", "weight", w, device=a.device)
     n = w.shape[0]
-    if w.shape[1] != k or r is None or tuple(r.shape) != (m, n):
-        raise RuntimeError(f"linear_rowscale: shapes a {tuple(a.shape)}, w {tuple(w.shape)}, "
-                           f"r {None if r is None else tuple(r.shape)}")
     _chk_gemm_operands("linear_rowscale", a, m, n, _lib.EPI_RESID_ROWSCALE, bias, scale, r, None)
-    if rows_per_scale <= 0 or row_scale.numel() * rows_per_scale < m:
-        raise RuntimeError("linear_rowscale: row_scale does not cover every row")
+    _chk_row_scale("linear_rowscale", a, m, row_scale, rows_per_scale)
     _launch(gemm_kernel_name(m, n, k, _lib.EPI_RESID_ROWSCALE, 0), 2.0 * m * n * k,
             lambda: _lib.call("pipnet_linear_rowscale_f32", a.data_ptr(), a.stride(0), w.data_ptr(), _ptr(bias),
                               _ptr(scale), r.data_ptr(), r.stride(0), r.data_ptr(), r.stride(0), m, n, k,
@@ -301,9 +288,11 @@ def linear_rowscale(a: Tensor, w: Tensor, bias: Optional[Tensor], scale: Tensor,
 
 
 def conv2x2(x_nhwc: Tensor, w_packed: Tensor, bias: Optional[Tensor], stride: int) -> Tensor:
-    _chk(x_nhwc, "conv2x2 input")
+    _chk_rows("conv2x2", x_nhwc, "input", 4)
     b, h, w, cin = x_nhwc.shape
     cout = w_packed.shape[0]
+    _operand("conv2x2", "w_packed", w_packed, shape=cout * 4 * cin, device=x_nhwc.device)
+    _operand("conv2x2", "bias", bias, shape=cout, device=x_nhwc.device, optional=True)
     oh, ow = (h - 2) // stride + 1, (w - 2) // stride + 1
     y = torch.empty((b, oh, ow, cout), device=x_nhwc.device, dtype=torch.float32)
     epi = _lib.EPI_BIAS if bias is not None else _lib.EPI_NONE
@@ -316,13 +305,15 @@ def conv2x2(x_nhwc: Tensor, w_packed: Tensor, bias: Optional[Tensor], stride: in
 def conv2d_nhwc(x: Tensor, w_packed: Tensor, bias: Optional[Tensor], stride: int, pad: int,
                 epilogue: int = _lib.EPI_BIAS, r: Optional[Tensor] = None) -> Tensor:
     """NHWC implicit-GEMM convolution; w_packed [Cout, KH, KW, Cin]; r = residual (NHWC)."""
-    _chk(x, "conv input")
-    _chk(w_packed, "conv weight")
+    _chk_rows("conv2d_nhwc", x, "input", 4)
+    _operand("conv2d_nhwc", "weight", w_packed, device=x.device)
     b, h, w, cin = x.shape
-    cout, kh, kw, wcin = w_packed.shape
-    if wcin != cin:
-        raise RuntimeError(f"conv2d_nhwc: input has {cin} channels, weight {wcin}")
+    if w_packed.dim() != 4 or w_packed.shape[3] != cin:
+        raise RuntimeError(f"conv2d_nhwc: input has {cin} channels, weight shape {tuple(w_packed.shape)}")
+    cout, kh, kw, _ = w_packed.shape
     oh, ow = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
+    _operand("conv2d_nhwc", "bias", bias, shape=cout, device=x.device, optional=True)
+    _operand("conv2d_nhwc", "r", r, shape=(b, oh, ow, cout), device=x.device, optional=True)
     y = torch.empty((b, oh, ow, cout), device=x.device, dtype=torch.float32)
     m, k = b * oh * ow, kh * kw * cin
     aload = 0 if (kh == 1 and kw == 1 and stride == 1 and pad == 0) else 2
@@ -355,11 +346,7 @@ BF16_KTILE = 64
 
 
 def _chk_bf(t: Tensor, what: str) -> None:
-    if not (t.is_cuda and t.dtype == torch.bfloat16):
-        raise RuntimeError(f"count_pipnet_amd: {what} must be a bfloat16 ROCm device tensor "
-                           f"(got device={t.device}, dtype={t.dtype}); there is no CPU fallback")
-    if not t.is_contiguous():
-        raise RuntimeError(f"count_pipnet_amd: {what} must be contiguous")
+    _operand("count_pipnet_amd", what, t, dtype=torch.bfloat16)
 
 
 @functools.lru_cache(maxsize=4096)
@@ -412,17 +399,16 @@ def conv2d_nhwc_bf16(x: Tensor, w_packed: Tensor, kh: int, kw: int, bias: Option
     8 = ping-pong with the LDS input halo (3x3 stride-1 pad-1 only), 9 = persistent ping-pong
     (1x1 stride-1, N % 256 == 0), 11 = 3x3 stride-1 pad-1 N = 64 on an LDS input halo."""
     _chk_bf(x, "conv input")
-    _chk_bf(w_packed, "conv weight")
-    if r is not None:
-        _chk_bf(r, "residual")
-    if bias is not None:
-        _chk(bias, "conv bias")
     b, h, w, cin = x.shape
+    dev, bf = x.device, torch.bfloat16
+    _operand("conv2d_nhwc_bf16", "weight", w_packed, dtype=bf, device=dev)
     cout, kp = w_packed.shape
     k = kh * kw * cin
     if kp != -(-k // BF16_KTILE) * BF16_KTILE:
         raise RuntimeError(f"conv2d_nhwc_bf16: packed weight K {kp} does not match {kh}x{kw}x{cin}")
     oh, ow = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
+    _operand("conv2d_nhwc_bf16", "bias", bias, shape=cout, device=dev, optional=True)
+    _operand("conv2d_nhwc_bf16", "residual", r, dtype=bf, shape=(b, oh, ow, cout), device=dev, optional=True)
     y = torch.empty((b, oh, ow, cout), device=x.device, dtype=torch.bfloat16)
     m = b * oh * ow
     if tile < 0 and not CONV3X3_N64_HALO and bf16_conv_plan(b, h, w, cin, cout, kh, kw, stride, pad, epilogue) == 11:
@@ -439,12 +425,11 @@ def stem_pool_bf16(s2d: Tensor, w_packed: Tensor, bias: Tensor) -> Tensor:
     """ResNet stem over the space-to-depth image (4x4 stride 1, 16 -> 64, + bias + ReLU) fused
     with MaxPool2d(3, 2, 1) (pipnet_stem_pool_bf16): bitwise conv2d_nhwc_bf16 + maxpool2d_nhwc_bf16."""
     _chk_bf(s2d, "stem s2d input")
-    _chk_bf(w_packed, "stem weight")
-    _chk(bias, "stem bias")
     b, sh, sw, c = s2d.shape
-    if c != 16 or tuple(w_packed.shape) != (64, 256):
-        raise RuntimeError(f"stem_pool_bf16: expects a 16-channel s2d image and a [64, 256] weight, got "
-                           f"{tuple(s2d.shape)} / {tuple(w_packed.shape)}")
+    if c != 16:
+        raise RuntimeError(f"stem_pool_bf16: expects a 16-channel s2d image, got {tuple(s2d.shape)}")
+    _operand("stem_pool_bf16", "weight", w_packed, dtype=torch.bfloat16, shape=(64, 256), device=s2d.device)
+    _operand("stem_pool_bf16", "bias", bias, shape=64, device=s2d.device)
     ph, pw = (sh - 4) // 2 + 1, (sw - 4) // 2 + 1
     y = torch.empty((b, ph, pw, 64), device=s2d.device, dtype=torch.bfloat16)
     _launch("pipnet_bf16::stem_pool_bf16_kernel", 2.0 * b * (sh - 3) * (sw - 3) * 64 * 256,
@@ -482,8 +467,11 @@ def conv1x1_bf16_dual(x: Tensor, w_packed: Tensor, bias: Tensor, n1: int, n2: in
     (x W1^T + b1, relu(x W2^T + b2)), each bit-equal to its own pipnet_conv2d_nhwc_bf16."""
     _chk_bf(x, "conv input")
     b, h, w, cin = x.shape
-    if tuple(w_packed.shape[:1]) != (n1 + n2,) or bias.numel() != n1 + n2 or n1 % 256 or n2 % 256:
-        raise RuntimeError(f"conv1x1_bf16_dual: weights {tuple(w_packed.shape)}, n1 {n1}, n2 {n2}")
+    if n1 % 256 or n2 % 256:
+        raise RuntimeError(f"conv1x1_bf16_dual: n1 {n1}, n2 {n2} must be multiples of 256")
+    kp = -(-cin // BF16_KTILE) * BF16_KTILE
+    _operand("conv1x1_bf16_dual", "weight", w_packed, dtype=torch.bfloat16, shape=(n1 + n2, kp), device=x.device)
+    _operand("conv1x1_bf16_dual", "bias", bias, shape=n1 + n2, device=x.device)
     y1 = torch.empty((b, h, w, n1), device=x.device, dtype=torch.bfloat16)
     y2 = torch.empty((b, h, w, n2), device=x.device, dtype=torch.bfloat16)
     m = b * h * w
@@ -520,11 +508,8 @@ def _head_out(out, b, h, w, p, dev):
         return (torch.empty((b, h, w, p), device=dev, dtype=torch.float32),
                 torch.empty((b, p), device=dev, dtype=torch.float32))
     proto, pooled = out
-    if tuple(proto.shape) != (b, h, w, p) or tuple(pooled.shape) != (b, p):
-        raise RuntimeError(f"softmax_pool: out shapes {tuple(proto.shape)}, {tuple(pooled.shape)} do not match "
-                           f"{(b, h, w, p)}, {(b, p)}")
-    _chk(proto, "proto out")
-    _chk(pooled, "pooled out")
+    _operand("softmax_pool", "proto out", proto, shape=(b, h, w, p), device=dev)
+    _operand("softmax_pool", "pooled out", pooled, shape=(b, p), device=dev)
     return proto, pooled
 
 
@@ -539,10 +524,12 @@ def softmax_pool_bf16(feat_nhwc: Tensor, pool_mode: int, out=None) -> Tuple[Tens
 
 
 def convnext_stem(x_nchw: Tensor, w: Tensor, b: Tensor, ln_w: Tensor, ln_b: Tensor) -> Tensor:
-    _chk(x_nchw, "network input (NCHW)")
+    _chk_rows("convnext_stem", x_nchw, "network input (NCHW)", 4)
     n, c, h, wd = x_nchw.shape
     if c != 3:
         raise RuntimeError(f"convnext stem expects 3 input channels, got {c}")
+    for t, what, numel in ((w, "w", 96 * 3 * 4 * 4), (b, "b", 96), (ln_w, "ln_w", 96), (ln_b, "ln_b", 96)):
+        _operand("convnext_stem", what, t, shape=numel, device=x_nchw.device)
     y = torch.empty((n, h // 4, wd // 4, 96), device=x_nchw.device, dtype=torch.float32)
     _lib.call("pipnet_convnext_stem_f32", x_nchw.data_ptr(), n, h, wd, w.data_ptr(), b.data_ptr(), ln_w.data_ptr(),
               ln_b.data_ptr(), y.data_ptr(), _stream(x_nchw))
@@ -564,23 +551,32 @@ def cnblock_mlp(t: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, gamma
     of a narrow stage (C = 96 / 192) in one kernel, the hidden activation kept in registers
     (csrc/mlp_f32.hip).  ``hw`` = the layer's pixels per image (0 = unknown): picks the
     instantiation by map size, never by M."""
-    for v, what in ((t, "mlp input"), (w1, "fc1 weight"), (b1, "fc1 bias"), (w2, "fc2 weight"), (b2, "fc2 bias"),
-                    (gamma, "layer scale"), (x, "residual")):
-        _chk(v, what)
+    _chk_rows("cnblock_mlp", t, "mlp input", 2)
     m, c = t.shape
-    if c not in MLP_FUSED_CHANNELS or tuple(x.shape) != (m, c) or tuple(w1.shape) != (4 * c, c) \
-            or tuple(w2.shape) != (c, 4 * c) or b1.numel() != 4 * c or b2.numel() != c or gamma.numel() != c:
-        raise RuntimeError(f"cnblock_mlp: shapes t {tuple(t.shape)} w1 {tuple(w1.shape)} w2 {tuple(w2.shape)}")
+    if c not in MLP_FUSED_CHANNELS:
+        raise RuntimeError(f"cnblock_mlp: {c} channels, supported {MLP_FUSED_CHANNELS}")
+    for v, what, shape in ((w1, "fc1 weight", (4 * c, c)), (b1, "fc1 bias", 4 * c), (w2, "fc2 weight", (c, 4 * c)),
+                           (b2, "fc2 bias", c), (gamma, "layer scale", c), (x, "residual", (m, c))):
+        _operand("cnblock_mlp", what, v, shape=shape, device=t.device)
     _launch(cnblock_mlp_kernel_name(c, m, hw), 2.0 * 2 * m * 4 * c * c,
             lambda: _lib.call("pipnet_cnblock_mlp_hw_f32", t.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
                               b2.data_ptr(), gamma.data_ptr(), x.data_ptr(), m, c, hw, _stream(t)))
     return x
 
 
+def _chk_dwconv7_ln(fn: str, x_nhwc: Tensor, w_packed: Tensor, bias: Tensor, ln_w: Tensor, ln_b: Tensor):
+    _chk_rows(fn, x_nhwc, "input", 4)
+    c = x_nhwc.shape[3]
+    _operand(fn, "w_packed", w_packed, shape=49 * c, device=x_nhwc.device)
+    for what, t in (("bias", bias), ("ln_w", ln_w), ("ln_b", ln_b)):
+        _operand(fn, what, t, shape=c, device=x_nhwc.device)
+    return x_nhwc.shape
+
+
 def dwconv7_ln(x_nhwc: Tensor, w_packed: Tensor, bias: Tensor, ln_w: Tensor, ln_b: Tensor,
                out: Optional[Tensor] = None) -> Tensor:
-    _chk(x_nhwc, "dwconv input")
-    b, h, w, c = x_nhwc.shape
+    b, h, w, c = _chk_dwconv7_ln("dwconv7_ln", x_nhwc, w_packed, bias, ln_w, ln_b)
+    _chk_same("dwconv7_ln", x_nhwc, out=out)
     y = torch.empty_like(x_nhwc) if out is None else out
     _lib.call("pipnet_dwconv7_ln_f32", x_nhwc.data_ptr(), b, h, w, c, w_packed.data_ptr(), bias.data_ptr(),
               ln_w.data_ptr(), ln_b.data_ptr(), y.data_ptr(), _stream(x_nhwc))
@@ -617,30 +613,27 @@ def conv_s3(x2: Tensor, w_packed: Tensor, kh: int, kw: int, cout: int, bias: Opt
     EPI_S3_GELU -> split planes [B,OH,OW,2Cout] of gelu(conv + b); EPI_F32_BIAS -> fp32
     [B,OH,OW,Cout]; EPI_F32_RESID -> fp32 r + scale * (conv + b) (``out`` may be ``r``)."""
     _chk_bf(x2, "split-plane input")
-    _chk_bf(w_packed, "split-plane weight")
-    if bias is not None:
-        _chk(bias, "bias")
     b, h, w, cin2 = x2.shape
     cin = cin2 // 2
     k = kh * kw * 3 * cin
-    if cin2 % 2 or w_packed.shape[0] != cout or w_packed.shape[1] != -(-k // S3_KTILE) * S3_KTILE:
-        raise RuntimeError(f"conv_s3: packed weight {tuple(w_packed.shape)} does not match {kh}x{kw}x3*{cin} -> {cout}")
+    if cin2 % 2:
+        raise RuntimeError(f"conv_s3: split planes need an even channel count, got {cin2}")
+    _operand("conv_s3", "split-plane weight", w_packed, dtype=torch.bfloat16, device=x2.device,
+             shape=(cout, -(-k // S3_KTILE) * S3_KTILE))
+    _chk_vec("conv_s3", x2, cout, bias=bias, scale=scale)
     oh, ow = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
     if epilogue == _lib.EPI_S3_GELU:
         shape, dt = (b, oh, ow, 2 * cout), torch.bfloat16
     else:
         shape, dt = (b, oh, ow, cout), torch.float32
-    if epilogue == _lib.EPI_F32_RESID:
-        if r is None or scale is None:
-            raise RuntimeError("conv_s3: EPI_F32_RESID needs r and scale")
-        _chk(r, "residual")
-        _chk(scale, "layer scale")
-        if r.numel() != b * oh * ow * cout:
-            raise RuntimeError(f"conv_s3: residual {tuple(r.shape)} does not match {(b, oh, ow, cout)}")
+    if epilogue == _lib.EPI_F32_RESID and scale is None:
+        raise RuntimeError("conv_s3: EPI_F32_RESID needs r and scale")
+    _operand("conv_s3", "residual", r, shape=b * oh * ow * cout, device=x2.device,
+             optional=epilogue != _lib.EPI_F32_RESID)
     if out is None:
         out = torch.empty(shape, device=x2.device, dtype=dt)
-    elif out.dtype != dt or out.numel() != b * oh * ow * shape[-1] or not out.is_contiguous():
-        raise RuntimeError(f"conv_s3: out {tuple(out.shape)} {out.dtype} does not match {shape} {dt}")
+    else:
+        _operand("conv_s3", "out", out, dtype=dt, shape=b * oh * ow * shape[-1], device=x2.device)
     m = b * oh * ow
     _launch(bf16_conv_kernel_name(b, h, w, cin, cout, kh, kw, stride, pad, epilogue, tile, s3=True),
             2.0 * m * cout * k / 3.0,
@@ -652,8 +645,7 @@ def conv_s3(x2: Tensor, w_packed: Tensor, kh: int, kw: int, cout: int, bias: Opt
 
 def dwconv7_ln_s3(x_nhwc: Tensor, w_packed: Tensor, bias: Tensor, ln_w: Tensor, ln_b: Tensor) -> Tensor:
     """pipnet_dwconv7_ln_f32 writing split planes [B,H,W,2C] bf16."""
-    _chk(x_nhwc, "dwconv input")
-    b, h, w, c = x_nhwc.shape
+    b, h, w, c = _chk_dwconv7_ln("dwconv7_ln_s3", x_nhwc, w_packed, bias, ln_w, ln_b)
     y = torch.empty((b, h, w, 2 * c), device=x_nhwc.device, dtype=torch.bfloat16)
     _lib.call("pipnet_dwconv7_ln_s3", x_nhwc.data_ptr(), b, h, w, c, w_packed.data_ptr(), bias.data_ptr(),
               ln_w.data_ptr(), ln_b.data_ptr(), y.data_ptr(), _stream(x_nhwc))
@@ -662,8 +654,9 @@ def dwconv7_ln_s3(x_nhwc: Tensor, w_packed: Tensor, bias: Tensor, ln_w: Tensor, 
 
 def layernorm_s3(x: Tensor, w: Tensor, b: Tensor) -> Tensor:
     """Row LayerNorm writing split planes [..., 2C] bf16."""
-    _chk(x, "layernorm input")
+    _operand("layernorm_s3", "input", x)
     c = x.shape[-1]
+    _chk_vec("layernorm_s3", x, c, w=w, b=b)
     y = torch.empty(tuple(x.shape[:-1]) + (2 * c,), device=x.device, dtype=torch.bfloat16)
     _lib.call("pipnet_layernorm_s3", x.data_ptr(), x.numel() // c, c, w.data_ptr(), b.data_ptr(), y.data_ptr(),
               _stream(x))
@@ -671,8 +664,10 @@ def layernorm_s3(x: Tensor, w: Tensor, b: Tensor) -> Tensor:
 
 
 def layernorm(x: Tensor, w: Tensor, b: Tensor, out: Optional[Tensor] = None) -> Tensor:
-    _chk(x, "layernorm input")
+    _operand("layernorm", "input", x)
     c = x.shape[-1]
+    _chk_vec("layernorm", x, c, w=w, b=b)
+    _chk_same("layernorm", x, out=out)
     y = torch.empty_like(x) if out is None else out
     _lib.call("pipnet_layernorm_f32", x.data_ptr(), x.numel() // c, c, w.data_ptr(), b.data_ptr(), y.data_ptr(),
               _stream(x))
@@ -712,12 +707,8 @@ def _argmax_out(out, b: int, p: int, dev, what: str) -> Tuple[Tensor, Tensor]:
         return (torch.empty((b, p), device=dev, dtype=torch.float32),
                 torch.empty((b, p), device=dev, dtype=torch.int32))
     val, loc = out
-    if tuple(val.shape) != (b, p) or tuple(loc.shape) != (b, p) or loc.dtype != torch.int32:
-        raise RuntimeError(f"{what}: out {tuple(val.shape)}, {tuple(loc.shape)} {loc.dtype} do not match "
-                           f"{(b, p)} float32 / int32")
-    _chk(val, what + " value out")
-    if not (loc.is_cuda and loc.is_contiguous()):
-        raise RuntimeError(f"{what}: loc out must be a contiguous device tensor")
+    _operand(what, "value out", val, shape=(b, p), device=dev)
+    _operand(what, "loc out", loc, dtype=torch.int32, shape=(b, p), device=dev)
     return val, loc
 
 
@@ -733,13 +724,16 @@ def map_argmax(map_nhwc: Tensor, out=None) -> Tuple[Tensor, Tensor]:
     return val, loc
 
 
+TOPK_MAX_K = _lib.CONSTANTS["TOPK_MAX_K"]
+
+
 class TopkState:
     """Device state of the streaming top-k (pipnet_topk_update): per (group, prototype) the k best
     (score, dataset index, loc) so far, the fill counts and the abstain counter."""
 
     def __init__(self, groups: int, prototypes: int, k: int, device):
-        if not 1 <= k <= 32:
-            raise ValueError(f"top-k: k must be in 1..32, got {k}")
+        if not 1 <= k <= TOPK_MAX_K:
+            raise ValueError(f"top-k: k must be in 1..{TOPK_MAX_K}, got {k}")
         if groups < 1 or prototypes < 1:
             raise ValueError("top-k: needs at least one group and one prototype")
         self.groups, self.prototypes, self.k = groups, prototypes, k
@@ -755,16 +749,16 @@ def topk_update(state: TopkState, score: Tensor, loc: Tensor, i0: int, group: Op
     """Merge one batch into ``state``: score / loc [B,P] (image b = dataset index ``i0 + b``),
     ``group`` [B] int32 (None: all in group 0; -1 skips the image), ``min_score`` skips candidates
     below it, ``out`` [B,K] logits feed the abstain counter.  Enqueues one kernel, no host sync."""
-    _chk(score, "top-k scores")
+    _chk_rows("topk_update", score, "scores", 2)
     b, p = score.shape
-    if p != state.prototypes or tuple(loc.shape) != (b, p) or loc.dtype != torch.int32 or not loc.is_contiguous():
-        raise RuntimeError(f"topk_update: score {tuple(score.shape)} / loc {tuple(loc.shape)} {loc.dtype} do not "
-                           f"match {state.prototypes} prototypes")
-    if group is not None and (tuple(group.shape) != (b,) or group.dtype != torch.int32 or not group.is_cuda
-                              or not group.is_contiguous()):
-        raise RuntimeError("topk_update: group must be a contiguous int32 device tensor [B]")
+    dev = score.device
+    if p != state.prototypes or state.score.device != dev:
+        raise RuntimeError(f"topk_update: score {tuple(score.shape)} on {dev} does not match the state's "
+                           f"{state.prototypes} prototypes on {state.score.device}")
+    _operand("topk_update", "loc", loc, dtype=torch.int32, shape=(b, p), device=dev)
+    _operand("topk_update", "group", group, dtype=torch.int32, shape=(b,), device=dev, optional=True)
     if out is not None:
-        _chk(out, "logits")
+        _operand("topk_update", "logits", out, device=dev)
         if out.dim() != 2 or out.shape[0] != b:
             raise RuntimeError(f"topk_update: logits {tuple(out.shape)} vs batch {b}")
     _lib.call("pipnet_topk_update", score.data_ptr(), loc.data_ptr(), b, p, int(i0), _ptr(group), state.groups,
@@ -774,7 +768,7 @@ def topk_update(state: TopkState, score: Tensor, loc: Tensor, i0: int, group: Op
     return state
 
 
-PROTO_STATS_MAX_BINS = 1024      # include/pipnet_amd.h PIPNET_PROTO_STATS_MAX_BINS
+PROTO_STATS_MAX_BINS = _lib.CONSTANTS["PROTO_STATS_MAX_BINS"]
 
 
 class ProtoStatsState:
@@ -813,16 +807,12 @@ def proto_stats_update(state: ProtoStatsState, act: Tensor, labels: Tensor) -> P
     [B] int64 on the device; a label outside [0, classes) only raises ``state.bad``.  Every entry is
     accumulated in image order by one owner thread, so the state does not depend on the batching.
     Enqueues one kernel, no host sync."""
-    require_device(act, "prototype activations")
-    if act.dim() != 2 or act.shape[1] != state.prototypes or (act.stride(1) != 1 and act.shape[1] > 1):
-        raise RuntimeError(f"proto_stats_update: act {tuple(act.shape)} (strides {act.stride()}) must be "
-                           f"[B, {state.prototypes}] with unit column stride")
+    _operand("proto_stats_update", "act", act, layout="rows")
     b, p = act.shape
-    if tuple(labels.shape) != (b,) or labels.dtype != torch.int64 or labels.device != act.device \
-            or not labels.is_contiguous():
-        raise RuntimeError("proto_stats_update: labels must be a contiguous int64 tensor [B] on act's device")
-    if state.n_ge.device != act.device:
-        raise RuntimeError("proto_stats_update: state and activations are on different devices")
+    if p != state.prototypes or state.n_ge.device != act.device:
+        raise RuntimeError(f"proto_stats_update: act {tuple(act.shape)} on {act.device} does not match the state's "
+                           f"{state.prototypes} prototypes on {state.n_ge.device}")
+    _operand("proto_stats_update", "labels", labels, dtype=torch.int64, shape=(b,), device=act.device)
     if b == 0:
         return state
     lda = act.stride(0) if b > 1 else max(act.stride(0), p)
@@ -834,12 +824,9 @@ def proto_stats_update(state: ProtoStatsState, act: Tensor, labels: Tensor) -> P
 def colsum_accum_f64(acc: Tensor, x: Tensor) -> Tensor:
     """acc [D] float64 += the column sums of x [B,D] float32 (any row stride), the rows added in
     order by one owner thread per column (pipnet_colsum_accum_f64).  One kernel, no host sync."""
-    require_device(x, "colsum_accum_f64 input")
-    if x.dim() != 2 or (x.stride(1) != 1 and x.shape[1] > 1):
-        raise RuntimeError(f"colsum_accum_f64: x {tuple(x.shape)} must be 2-D with unit column stride")
+    _operand("colsum_accum_f64", "input", x, layout="rows")
     b, d = x.shape
-    if tuple(acc.shape) != (d,) or acc.dtype != torch.float64 or acc.device != x.device or not acc.is_contiguous():
-        raise RuntimeError(f"colsum_accum_f64: acc must be a contiguous float64 tensor [{d}] on x's device")
+    _operand("colsum_accum_f64", "acc", acc, dtype=torch.float64, shape=(d,), device=x.device)
     if b == 0:
         return acc
     _lib.call("pipnet_colsum_accum_f64", x.data_ptr(), x.stride(0) if b > 1 else max(x.stride(0), d), b, d,
@@ -847,7 +834,7 @@ def colsum_accum_f64(acc: Tensor, x: Tensor) -> Tensor:
     return acc
 
 
-PART_PURITY_MAX_PARTS = 32       # include/pipnet_amd.h PIPNET_PART_PURITY_MAX_PARTS
+PART_PURITY_MAX_PARTS = _lib.CONSTANTS["PART_PURITY_MAX_PARTS"]
 
 
 class PartPurityState:
@@ -881,10 +868,8 @@ def _part_table_args(state: PartPurityState, table, relevant: Tensor, geometry, 
     want = ((xy, (n_img, q, 2), torch.float64), (vis, (n_img, q), torch.uint8), (size, (n_img, 2), torch.int32),
             (merged, (q,), torch.int32), (is_left, (q,), torch.uint8), (pair_index, (q,), torch.int32),
             (relevant, (state.prototypes,), torch.uint8))
-    for t, shape, dtype in want:
-        if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous() or not t.is_cuda:
-            raise RuntimeError(f"{what}: expected a contiguous {dtype} device tensor {shape} on {dev}, got "
-                               f"{tuple(t.shape)} {t.dtype} on {t.device}")
+    for name, (t, shape, dtype) in zip(("xy", "vis", "size", "merged", "is_left", "pair_index", "relevant"), want):
+        _operand(what, name, t, dtype=dtype, shape=shape, device=dev)
     h, w, image_size, skip, small_map = geometry
     return (int(h), int(w), int(image_size), int(skip), 1 if small_map else 0, xy.data_ptr(), vis.data_ptr(),
             size.data_ptr(), n_img, merged.data_ptr(), is_left.data_ptr(), pair_index.data_ptr(), q,
@@ -898,15 +883,11 @@ def part_purity_update(state: PartPurityState, pooled: Tensor, loc: Tensor, rele
     ``loc[b, p]``.  pooled [B,P] float32 (any row stride, unit column stride), loc [B,P] int32.
     One owner thread per prototype walks the images in order: the state does not depend on the
     batching.  Enqueues one kernel, no host sync."""
-    require_device(pooled, "pooled scores")
-    if pooled.dim() != 2 or pooled.shape[1] != state.prototypes or (pooled.stride(1) != 1 and pooled.shape[1] > 1):
-        raise RuntimeError(f"part_purity_update: pooled {tuple(pooled.shape)} (strides {pooled.stride()}) must be "
-                           f"[B, {state.prototypes}] with unit column stride")
+    _operand("part_purity_update", "pooled", pooled, layout="rows", device=state.n.device)
     b, p = pooled.shape
-    if tuple(loc.shape) != (b, p) or loc.dtype != torch.int32 or loc.device != pooled.device or not loc.is_contiguous():
-        raise RuntimeError("part_purity_update: loc must be a contiguous int32 tensor [B, P] on pooled's device")
-    if state.n.device != pooled.device:
-        raise RuntimeError("part_purity_update: state and scores are on different devices")
+    if p != state.prototypes:
+        raise RuntimeError(f"part_purity_update: pooled {tuple(pooled.shape)} must be [B, {state.prototypes}]")
+    _operand("part_purity_update", "loc", loc, dtype=torch.int32, shape=(b, p), device=pooled.device)
     tail = _part_table_args(state, table, relevant, geometry, "part_purity_update")
     if b == 0:
         return state
@@ -921,13 +902,11 @@ def part_purity_rows(state: PartPurityState, index: Tensor, loc: Tensor, relevan
                      table) -> PartPurityState:
     """Merge explicit rows (mode "topk"): index [P,k] int64 dataset indices (< 0: empty slot) and loc
     [P,k] int32 of a top-k state; slot j of a relevant prototype is its j-th row.  One kernel."""
-    if index.dim() != 2 or index.shape[0] != state.prototypes or not 1 <= index.shape[1] <= 32:
-        raise RuntimeError(f"part_purity_rows: index {tuple(index.shape)} must be [{state.prototypes}, k <= 32]")
-    dev = state.n.device
-    for t, dtype in ((index, torch.int64), (loc, torch.int32)):
-        if t.shape != index.shape or t.dtype != dtype or t.device != dev or not t.is_cuda or not t.is_contiguous():
-            raise RuntimeError("part_purity_rows: index (int64) and loc (int32) must be contiguous device tensors "
-                               "of one shape on the state's device")
+    if index.dim() != 2 or index.shape[0] != state.prototypes or not 1 <= index.shape[1] <= TOPK_MAX_K:
+        raise RuntimeError(f"part_purity_rows: index {tuple(index.shape)} must be [{state.prototypes}, "
+                           f"k <= {TOPK_MAX_K}]")
+    _operand("part_purity_rows", "index", index, dtype=torch.int64, device=state.n.device)
+    _operand("part_purity_rows", "loc", loc, dtype=torch.int32, shape=index.shape, device=state.n.device)
     tail = _part_table_args(state, table, relevant, geometry, "part_purity_rows")
     _launch("part_purity_rows_kernel", 0.0,
             lambda: _lib.call("pipnet_part_purity_rows", index.data_ptr(), loc.data_ptr(), relevant.data_ptr(),
@@ -957,7 +936,7 @@ def part_purity_finish(state: PartPurityState):
     return in_csv.bool(), f64[0], i32[0], i64[0], i32[1], i64[1], f64[1], purity
 
 
-LOCAL_EXPLAIN_MAX = 2048         # prototypes / classes per image (csrc/explain.hip LX_MAX)
+LOCAL_EXPLAIN_MAX = _lib.CONSTANTS["LOCAL_EXPLAIN_MAX"]         # prototypes / classes per image
 
 
 def local_explain(pooled: Tensor, loc: Tensor, out: Tensor, weight: Tensor, top_classes: int, max_entries: int,
@@ -969,28 +948,22 @@ def local_explain(pooled: Tensor, loc: Tensor, out: Tensor, weight: Tensor, top_
     with C = top_classes, M = max_entries.  Classes by logit, prototypes by score, both descending
     with the lower index first among equals; (c, p) kept iff |pooled * weight| > min_abs in fp64;
     n is the true count, empty slots hold (-1, 0, 0, 0, -1).  One kernel, no host sync."""
-    _chk(pooled, "pooled scores")
-    _chk(out, "logits")
-    require_device(weight, "explanation weight")
-    if pooled.dim() != 2 or out.dim() != 2 or weight.dim() != 2:
-        raise RuntimeError("local_explain: pooled, out and weight must be 2-D")
+    _chk_rows("local_explain", pooled, "pooled scores", 2)
+    _chk_rows("local_explain", out, "logits", 2)
     b, p = pooled.shape
     k = out.shape[1]
-    if tuple(loc.shape) != (b, p) or loc.dtype != torch.int32 or not loc.is_cuda or not loc.is_contiguous():
-        raise RuntimeError(f"local_explain: loc {tuple(loc.shape)} {loc.dtype} must be a contiguous int32 device "
-                           f"tensor {(b, p)}")
-    if out.shape[0] != b or tuple(weight.shape) != (k, p):
-        raise RuntimeError(f"local_explain: pooled {tuple(pooled.shape)}, out {tuple(out.shape)} and weight "
-                           f"{tuple(weight.shape)} do not match")
-    if weight.stride(1) != 1 and p > 1:
-        raise RuntimeError("local_explain: weight must have unit column stride")
+    dev = pooled.device
+    if out.shape[0] != b or out.device != dev:
+        raise RuntimeError(f"local_explain: pooled {tuple(pooled.shape)} on {dev} and out {tuple(out.shape)} on "
+                           f"{out.device} do not match")
+    _operand("local_explain", "loc", loc, dtype=torch.int32, shape=(b, p), device=dev)
+    _operand("local_explain", "weight", weight, shape=(k, p), device=dev, layout="rows")
     c, m = int(top_classes), int(max_entries)
     if not (1 <= c <= k <= LOCAL_EXPLAIN_MAX and 1 <= p <= LOCAL_EXPLAIN_MAX and m >= 1):
         raise RuntimeError(f"local_explain: needs 1 <= top_classes ({c}) <= classes ({k}) <= {LOCAL_EXPLAIN_MAX}, "
                            f"1 <= prototypes ({p}) <= {LOCAL_EXPLAIN_MAX} and max_entries ({m}) >= 1")
     if not float(min_abs) >= 0.0:
         raise RuntimeError(f"local_explain: min_abs must be >= 0, got {min_abs}")
-    dev = pooled.device
     ldw = weight.stride(0) if k > 1 else max(weight.stride(0), p)
     i32 = dict(device=dev, dtype=torch.int32)
     f32 = dict(device=dev, dtype=torch.float32)
@@ -1014,16 +987,14 @@ def softmax_pool_linear(feat_nhwc: Tensor, w: Tensor, bias: Optional[Tensor], th
     using the capture stream's cached scratch (one graph node): serialise replays with eager calls
     on that stream."""
     bf = feat_nhwc.dtype == torch.bfloat16
-    if bf:
-        _chk_bf(feat_nhwc, "prototype logits")
-    else:
-        _chk(feat_nhwc, "prototype logits")
-    _chk(w, "classifier weight")
+    _operand("softmax_pool_linear", "prototype logits", feat_nhwc, dtype=torch.bfloat16 if bf else torch.float32)
     b, h, wd, p = feat_nhwc.shape
-    k = w.shape[0]
+    dev = feat_nhwc.device
     if w.dim() != 2 or w.shape[1] != p:
         raise RuntimeError(f"softmax_pool_linear: weight {tuple(w.shape)} vs {p} prototypes")
-    dev = feat_nhwc.device
+    _operand("softmax_pool_linear", "classifier weight", w, device=dev)
+    k = w.shape[0]
+    _operand("softmax_pool_linear", "bias", bias, shape=k, device=dev, optional=True)
     if out is None:
         proto, pooled = _head_out(None, b, h, wd, p, dev)
         x_out = torch.empty((b, p), device=dev, dtype=torch.float32)
@@ -1031,10 +1002,8 @@ def softmax_pool_linear(feat_nhwc: Tensor, w: Tensor, bias: Optional[Tensor], th
     else:
         proto, pooled = _head_out((out[0], out[1]), b, h, wd, p, dev)
         x_out, logits = out[2], out[3]
-        if tuple(x_out.shape) != (b, p) or tuple(logits.shape) != (b, k):
-            raise RuntimeError("softmax_pool_linear: out shapes do not match")
-        _chk(x_out, "classifier input out")
-        _chk(logits, "logits out")
+        _operand("softmax_pool_linear", "classifier input out", x_out, shape=(b, p), device=dev)
+        _operand("softmax_pool_linear", "logits out", logits, shape=(b, k), device=dev)
     part, tickets = _head_workspace(dev, _stream(feat_nhwc), int(_lib.load().pipnet_softmax_pool_linear_part_floats(
         b, h * wd, p)), b)
     _lib.call("pipnet_softmax_pool_linear_bf16" if bf else "pipnet_softmax_pool_linear_f32", feat_nhwc.data_ptr(), b,
@@ -1074,19 +1043,18 @@ def nonneg_linear(x: Tensor, w: Tensor, bias: Optional[Tensor], thresh: Optional
                   out=None) -> Tuple[Tensor, Tensor]:
     """(x', out) with x' = where(x < thresh, 0, x) (or x) and out = x' relu(w)^T + bias.
     ``out`` = (x', logits) to write into."""
-    _chk(x, "classifier input")
-    _chk(w, "classifier weight")
+    _chk_rows("nonneg_linear", x, "classifier input", 2)
     b, d = x.shape
     k = w.shape[0]
+    _operand("nonneg_linear", "classifier weight", w, shape=(k, d), device=x.device)
+    _operand("nonneg_linear", "bias", bias, shape=k, device=x.device, optional=True)
     if out is None:
         x_out = torch.empty_like(x)
         out = torch.empty((b, k), device=x.device, dtype=torch.float32)
     else:
         x_out, out = out
-        if tuple(x_out.shape) != (b, d) or tuple(out.shape) != (b, k):
-            raise RuntimeError("nonneg_linear: out shapes do not match")
-        _chk(x_out, "classifier input out")
-        _chk(out, "logits out")
+        _operand("nonneg_linear", "classifier input out", x_out, shape=(b, d), device=x.device)
+        _operand("nonneg_linear", "logits out", out, shape=(b, k), device=x.device)
     _lib.call("pipnet_nonneg_linear_f32", x.data_ptr(), b, d, w.data_ptr(), _ptr(bias), k,
               0 if thresh is None else 1, 0.0 if thresh is None else float(thresh), x_out.data_ptr(),
               out.data_ptr(), _stream(x))
@@ -1100,10 +1068,8 @@ def count_gumbel(logits_nhwc: Tensor, tau: float, exp_noise_nchw: Optional[Tenso
     (proto, hist) to write into (batch slices of a larger output)."""
     _chk(logits_nhwc, "prototype logits")
     b, h, w, p = logits_nhwc.shape
-    if exp_noise_nchw is not None:
-        _chk(exp_noise_nchw, "exp noise")
-        if tuple(exp_noise_nchw.shape) != (b, p, h, w):
-            raise RuntimeError(f"exp noise shape {tuple(exp_noise_nchw.shape)} != {(b, p, h, w)}")
+    _operand("count_gumbel", "exp noise", exp_noise_nchw, shape=(b, p, h, w), device=logits_nhwc.device,
+             optional=True)
     proto, hist = _gumbel_out(out, logits_nhwc)
     _lib.call("pipnet_count_gumbel_f32", logits_nhwc.data_ptr(), b, h * w, p, float(tau), _ptr(exp_noise_nchw),
               int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), proto.data_ptr(), hist.data_ptr(),
@@ -1117,12 +1083,8 @@ def _gumbel_out(out, logits_nhwc: Tensor) -> Tuple[Tensor, Tensor]:
     if out is None:
         return torch.empty_like(logits_nhwc), torch.empty((b, p), device=logits_nhwc.device, dtype=torch.int32)
     proto, hist = out
-    if tuple(proto.shape) != (b, h, w, p) or tuple(hist.shape) != (b, p) or hist.dtype != torch.int32:
-        raise RuntimeError(f"count_gumbel: out {tuple(proto.shape)}, {tuple(hist.shape)} {hist.dtype} do not "
-                           f"match {(b, h, w, p)}, {(b, p)} int32")
-    _chk(proto, "proto out")
-    if not (hist.is_cuda and hist.is_contiguous()):
-        raise RuntimeError("count_gumbel: hist out must be a contiguous device tensor")
+    _operand("count_gumbel", "proto out", proto, shape=(b, h, w, p), device=logits_nhwc.device)
+    _operand("count_gumbel", "hist out", hist, dtype=torch.int32, shape=(b, p), device=logits_nhwc.device)
     return proto, hist
 
 
@@ -1131,10 +1093,8 @@ def count_gumbel_soft(logits_nhwc: Tensor, tau: float, exp_noise_nchw: Optional[
     """Train-mode (soft) Gumbel-softmax map [B,h,w,P] + fp32 spatial sums (raw counts) [B,P]."""
     _chk(logits_nhwc, "prototype logits")
     b, h, w, p = logits_nhwc.shape
-    if exp_noise_nchw is not None:
-        _chk(exp_noise_nchw, "exp noise")
-        if tuple(exp_noise_nchw.shape) != (b, p, h, w):
-            raise RuntimeError(f"exp noise shape {tuple(exp_noise_nchw.shape)} != {(b, p, h, w)}")
+    _operand("count_gumbel_soft", "exp noise", exp_noise_nchw, shape=(b, p, h, w), device=logits_nhwc.device,
+             optional=True)
     proto = torch.empty_like(logits_nhwc)
     sums = torch.empty((b, p), device=logits_nhwc.device, dtype=torch.float32)
     _lib.call("pipnet_count_gumbel_soft_f32", logits_nhwc.data_ptr(), b, h * w, p, float(tau), _ptr(exp_noise_nchw),
@@ -1145,11 +1105,11 @@ def count_gumbel_soft(logits_nhwc: Tensor, tau: float, exp_noise_nchw: Optional[
 
 def nonneg_linear_dx(d_out: Tensor, w: Tensor) -> Tensor:
     """d_out [N,K] relu(w [K,D]) -> [N,D] (NonNegLinear input gradient)."""
-    _chk(d_out, "d_out")
-    _chk(w, "classifier weight")
+    _chk_rows("nonneg_linear_dx", d_out, "d_out", 2)
     n, k = d_out.shape
-    if w.shape[0] != k:
+    if w.dim() != 2 or w.shape[0] != k:
         raise RuntimeError(f"nonneg_linear_dx: d_out {tuple(d_out.shape)} vs W {tuple(w.shape)}")
+    _operand("nonneg_linear_dx", "classifier weight", w, device=d_out.device)
     dx = torch.empty((n, w.shape[1]), device=d_out.device, dtype=torch.float32)
     _lib.call("pipnet_nonneg_linear_dx_f32", d_out.data_ptr(), w.data_ptr(), n, w.shape[1], k, dx.data_ptr(),
               _stream(d_out))
@@ -1158,10 +1118,8 @@ def nonneg_linear_dx(d_out: Tensor, w: Tensor) -> Tensor:
 
 def bilinear_bwd_prep(g: Tensor, u: Tensor, v: Tensor) -> Tuple[Tensor, Tensor]:
     """(g * v, g * u) for out = u * v."""
-    for t, what in ((g, "grad"), (u, "W(e)"), (v, "V(e)")):
-        _chk(t, what)
-    if not (g.shape == u.shape == v.shape):
-        raise RuntimeError("bilinear_bwd_prep: shape mismatch")
+    _operand("bilinear_bwd_prep", "grad", g)
+    _chk_same("bilinear_bwd_prep", g, **{"W(e)": u, "V(e)": v})
     du, dv = torch.empty_like(g), torch.empty_like(g)
     _lib.call("pipnet_bilinear_bwd_prep_f32", g.data_ptr(), u.data_ptr(), v.data_ptr(), g.numel(), du.data_ptr(),
               dv.data_ptr(), _stream(g))
@@ -1173,10 +1131,8 @@ ONEHOT_STRATEGY = {None: 0, "none": 0, "current_grad": 1, "max_grad": 2}
 
 def count_ste_backward(counts: Tensor, d_clamped: Tensor, max_count: int, use_ste: bool, gated: bool) -> Tensor:
     """d raw counts from d clamped counts through STE_Round / ClampSTE (count_pipnet.py:90-97)."""
-    _chk(counts, "counts")
-    _chk(d_clamped, "d clamped counts")
-    if counts.shape != d_clamped.shape:
-        raise RuntimeError(f"count_ste_backward: counts {tuple(counts.shape)} vs grad {tuple(d_clamped.shape)}")
+    _operand("count_ste_backward", "counts", counts)
+    _operand("count_ste_backward", "d clamped counts", d_clamped, shape=counts.shape, device=counts.device)
     d = torch.empty_like(counts)
     _lib.call("pipnet_count_ste_bwd_f32", counts.data_ptr(), counts.numel(), int(max_count), int(bool(use_ste)),
               int(bool(gated)), d_clamped.data_ptr(), d.data_ptr(), _stream(counts))
@@ -1186,8 +1142,8 @@ def count_ste_backward(counts: Tensor, d_clamped: Tensor, max_count: int, use_st
 def onehot_ste_backward(x: Tensor, g: Tensor, strategy: Optional[str] = None, respect_active: bool = False) -> Tensor:
     """ModifiedSTEFunction.backward (count_pipnet_utils.py:226-321): x [B,P] encoder input,
     g [B,P*M] (or [B,P,M]) encoding gradient -> d x [B,P]."""
-    _chk(x, "one-hot encoder input")
-    _chk(g, "encoding gradient")
+    _operand("onehot_ste_backward", "encoder input", x)
+    _operand("onehot_ste_backward", "encoding gradient", g, device=x.device)
     b, p = x.shape
     if g.numel() % max(x.numel(), 1) or g.shape[0] != b:
         raise RuntimeError(f"onehot_ste_backward: x {tuple(x.shape)} vs grad {tuple(g.shape)}")
@@ -1205,12 +1161,15 @@ def linear_intermediate_backward(x: Tensor, g: Tensor, w: Tensor, want_dx: bool 
                                  dw_out: Optional[Tensor] = None) -> Tuple[Optional[Tensor], Tensor]:
     """LinearIntermediate backward (count_pipnet_utils.py:471-519): x [B,P] counts, g [B,P*E]
     output gradient, w [E,1] -> (d x [B,P] or None, d w [E,1])."""
-    _chk(x, "intermediate input")
-    _chk(g, "intermediate output gradient")
+    fn = "linear_intermediate_backward"
+    _operand(fn, "input", x)
     e = w.numel()
-    if g.numel() != x.numel() * e or g.shape[0] != x.shape[0]:
-        raise RuntimeError(f"linear_intermediate_backward: x {tuple(x.shape)}, grad {tuple(g.shape)}, E={e}")
+    if g.dim() < 1 or g.shape[0] != x.shape[0]:
+        raise RuntimeError(f"{fn}: x {tuple(x.shape)}, grad {tuple(g.shape)}, E={e}")
+    _operand(fn, "output gradient", g, shape=x.numel() * e, device=x.device)
     wv = w.detach().reshape(-1).contiguous()
+    _operand(fn, "weight", wv, device=x.device)
+    _operand(fn, "dw_out", dw_out, shape=e, device=x.device, optional=True)
     dx = torch.empty_like(x) if want_dx else None
     dw = torch.empty(e, 1, device=x.device, dtype=torch.float32) if dw_out is None else dw_out
     part = torch.empty(int(_lib.load().pipnet_linear_inter_partials_floats(e)), device=x.device,
@@ -1224,15 +1183,12 @@ def count_head_backward(proto_nhwc: Tensor, counts: Tensor, d_counts: Optional[T
                         w_tanh: float, tanh_coeff: float, tau: float) -> Tensor:
     """d loss / d logits of the CountPIPNet head (soft Gumbel-softmax / softmax, spatial sum)
     for the align / tanh terms of calculate_loss plus the classifier chain's d counts."""
-    _chk(proto_nhwc, "proto features")
-    _chk(counts, "counts")
+    _chk_rows("count_head_backward", proto_nhwc, "proto features", 4)
     n, h, ww, p = proto_nhwc.shape
-    if tuple(counts.shape) != (n, p) or n % 2:
-        raise RuntimeError(f"count_head_backward: proto {tuple(proto_nhwc.shape)} vs counts {tuple(counts.shape)}")
-    if d_counts is not None:
-        _chk(d_counts, "d counts")
-        if d_counts.shape != counts.shape:
-            raise RuntimeError("count_head_backward: d counts shape")
+    if n % 2:
+        raise RuntimeError(f"count_head_backward: the batch holds both views, so it must be even (got {n})")
+    _operand("count_head_backward", "counts", counts, shape=(n, p), device=proto_nhwc.device)
+    _operand("count_head_backward", "d counts", d_counts, shape=(n, p), device=proto_nhwc.device, optional=True)
     d_logits = torch.empty_like(proto_nhwc)
     dcnt = torch.empty((n, p), device=proto_nhwc.device, dtype=torch.float32)
     _lib.call("pipnet_count_head_bwd_f32", proto_nhwc.data_ptr(), counts.data_ptr(), n // 2, h * ww, p,
@@ -1248,7 +1204,7 @@ def philox_exp1(seed: int, offset: int, n: int, device, log_e: bool = False) -> 
     if n % 4:
         raise RuntimeError(f"philox_exp1: n = {n} must be a multiple of 4")
     out = torch.empty(n, device=device, dtype=torch.float32)
-    _chk(out, "philox output")
+    require_device(out, "philox output")
     _lib.call("pipnet_philox_exp1_f32", int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), n, int(log_e),
               out.data_ptr(), _stream(out))
     return out
@@ -1258,8 +1214,8 @@ def count_gumbel_devseed(logits_nhwc: Tensor, tau: float, seed_state: Tensor, ou
     """count_gumbel with the Philox key in device memory (seed_state: int64[2] on the device),
     advanced on the stream per call -- the form a captured HIP graph replays.  ``out`` as there."""
     _chk(logits_nhwc, "prototype logits")
-    if not (seed_state.is_cuda and seed_state.dtype == torch.int64 and seed_state.numel() == 2):
-        raise RuntimeError("count_gumbel_devseed: seed_state must be a 2-element int64 device tensor")
+    _operand("count_gumbel_devseed", "seed_state", seed_state, dtype=torch.int64, shape=2,
+             device=logits_nhwc.device)
     b, h, w, p = logits_nhwc.shape
     proto, hist = _gumbel_out(out, logits_nhwc)
     _lib.call("pipnet_count_gumbel_devseed_f32", logits_nhwc.data_ptr(), b, h * w, p, float(tau),
@@ -1269,6 +1225,8 @@ def count_gumbel_devseed(logits_nhwc: Tensor, tau: float, seed_state: Tensor, ou
 
 def count_finish(hist: Optional[Tensor], sums: Optional[Tensor], max_count: int, do_round: bool) -> Tuple[Tensor, Tensor]:
     ref = hist if hist is not None else sums
+    _operand("count_finish", "hist", hist, dtype=torch.int32, optional=True)
+    _operand("count_finish", "sums", sums, shape=ref.shape, device=ref.device, optional=hist is not None)
     b, p = ref.shape
     raw = torch.empty((b, p), device=ref.device, dtype=torch.float32)
     clamped = torch.empty_like(raw)
@@ -1278,8 +1236,9 @@ def count_finish(hist: Optional[Tensor], sums: Optional[Tensor], max_count: int,
 
 
 def count_encode(x: Tensor, c: int, kind: int, do_round: bool, w: Optional[Tensor] = None) -> Tensor:
-    _chk(x, "counts")
+    _chk_rows("count_encode", x, "counts", 2)
     b, p = x.shape
+    _operand("count_encode", "w", w, shape=c, device=x.device, optional=kind != 1)
     out = torch.empty((b, p * c), device=x.device, dtype=torch.float32)
     _lib.call("pipnet_count_encode_f32", x.data_ptr(), b, p, c, kind, int(do_round), _ptr(w), out.data_ptr(),
               _stream(x))
@@ -1308,20 +1267,15 @@ def eval_batch(pooled: Tensor, out: Tensor, w: Tensor, ys: Tensor, multiplier: O
                cm: Tensor, acc: Tensor, abstained: Tensor) -> Tuple[Tensor, Tensor]:
     """One eval_pipnet batch on the device; accumulates into cm [K,K] int64, acc [5] fp64,
     abstained [1] int64.  Returns (ys_pred [B] int32, score [B] fp32)."""
-    _chk(pooled, "pooled")
-    _chk(out, "logits")
-    _chk(w, "prototype-class weights")
-    b, p = pooled.shape
-    k = out.shape[1]
-    if tuple(w.shape) != (k, p) or out.shape[0] != b or ys.shape != (b,):
-        raise RuntimeError(f"eval_batch: shapes pooled {tuple(pooled.shape)}, out {tuple(out.shape)}, "
-                           f"w {tuple(w.shape)}, ys {tuple(ys.shape)} disagree")
-    if not (ys.is_cuda and ys.dtype == torch.int64 and ys.is_contiguous()):
-        raise RuntimeError("eval_batch: labels must be a contiguous int64 device tensor")
-    if cm.dtype != torch.int64 or acc.dtype != torch.float64 or abstained.dtype != torch.int64:
-        raise RuntimeError("eval_batch: accumulator dtypes are int64 / float64 / int64")
-    if multiplier is not None:
-        _chk(multiplier, "normalization multiplier")
+    _chk_rows("eval_batch", out, "logits", 2)
+    b, k = out.shape
+    dev, i64 = out.device, torch.int64
+    p = pooled.shape[-1]
+    for what, t, dtype, shape in (("pooled", pooled, torch.float32, (b, p)), ("weights", w, torch.float32, (k, p)),
+                                  ("labels", ys, i64, (b,)), ("multiplier", multiplier, torch.float32, 1),
+                                  ("cm", cm, i64, (k, k)), ("acc", acc, torch.float64, 5),
+                                  ("abstained", abstained, i64, 1)):
+        _operand("eval_batch", what, t, dtype=dtype, shape=shape, device=dev, optional=what == "multiplier")
     ys_pred = torch.empty(b, device=out.device, dtype=torch.int32)
     score = torch.empty(b, device=out.device, dtype=torch.float32)
     ws = torch.empty(5 * b + k, device=out.device, dtype=torch.int32)
@@ -1333,25 +1287,24 @@ def eval_batch(pooled: Tensor, out: Tensor, w: Tensor, ys: Tensor, multiplier: O
 
 # ---- evaluation input transform (util/data.py transform_no_augment) ----------------------
 
+def _ragged_batch(fn: str, pixels: Tensor, offsets: Tensor, sizes: Tensor, sizes_host):
+    """The checked operands of a ragged batch of packed HWC uint8 images: (host [B,2] int32 size table, B)."""
+    import numpy as np
+    _operand(fn, "pixels", pixels, dtype=torch.uint8)
+    sizes_np = np.ascontiguousarray(np.asarray(sizes_host, dtype=np.int32).reshape(-1, 2))
+    b = sizes_np.shape[0]
+    _operand(fn, "offsets", offsets, dtype=torch.int64, shape=(b,), device=pixels.device)
+    _operand(fn, "sizes", sizes, dtype=torch.int32, shape=(b, 2), device=pixels.device)
+    return sizes_np, b
+
+
 def resize_normalize_rgb8(pixels: Tensor, offsets: Tensor, sizes: Tensor, sizes_host, out_hw: Tuple[int, int],
                           mean, std, grayscale: bool = False, want_u8: bool = False):
     """Resize(out_hw, BILINEAR) [+ Grayscale(3)] + ToTensor + Normalize of a ragged batch of
     decoded RGB images packed HWC uint8 on the device (image b at byte offsets[b], shape
     sizes[b] = (h, w)); ``sizes_host`` is the same [B,2] int32 table on the host.
     Returns [B,3,oh,ow] fp32 (and the [B,oh,ow,3] uint8 resized image when ``want_u8``)."""
-    import ctypes
-
-    import numpy as np
-    if not (pixels.is_cuda and pixels.dtype == torch.uint8 and pixels.is_contiguous()):
-        raise RuntimeError("resize_normalize_rgb8: pixels must be a contiguous uint8 ROCm device tensor "
-                           "(there is no CPU fallback)")
-    if not (offsets.is_cuda and offsets.dtype == torch.int64 and sizes.is_cuda and sizes.dtype == torch.int32):
-        raise RuntimeError("resize_normalize_rgb8: offsets (int64) / sizes (int32) must be device tensors")
-    sizes_np = np.ascontiguousarray(np.asarray(sizes_host, dtype=np.int32).reshape(-1, 2))
-    b = sizes_np.shape[0]
-    if offsets.shape != (b,) or tuple(sizes.shape) != (b, 2):
-        raise RuntimeError(f"resize_normalize_rgb8: {b} images but offsets {tuple(offsets.shape)}, "
-                           f"sizes {tuple(sizes.shape)}")
+    sizes_np, b = _ragged_batch("resize_normalize_rgb8", pixels, offsets, sizes, sizes_host)
     oh, ow = int(out_hw[0]), int(out_hw[1])
     kmax, wsb = ctypes.c_int(0), ctypes.c_int64(0)
     _lib.call("pipnet_resize_plan", sizes_np.ctypes.data, b, oh, ow, ctypes.byref(kmax), ctypes.byref(wsb))
@@ -1368,7 +1321,7 @@ def resize_normalize_rgb8(pixels: Tensor, offsets: Tensor, sizes: Tensor, sizes_
 
 
 # ---- two-view training augmentation (csrc/augment_ops.hip) ----------------------------------
-AUG_GEOM_PARAMS, AUG_VIEW_PARAMS = 13, 8        # include/pipnet_amd.h PIPNET_AUG_*_PARAMS
+AUG_GEOM_PARAMS, AUG_VIEW_PARAMS = _lib.CONSTANTS["AUG_GEOM_PARAMS"], _lib.CONSTANTS["AUG_VIEW_PARAMS"]
 AUG_OP_SHARPNESS, AUG_OP_LAST = 4, 8
 
 
@@ -1388,19 +1341,7 @@ def augment_geometry_rgb8(pixels: Tensor, offsets: Tensor, sizes: Tensor, sizes_
     ``resize_normalize_rgb8``: Resize((s1, s1)) -> affine warp (NEAREST) -> flip ->
     crop(box).resize((s2, s2), BILINEAR).  ``gparams`` is the host [B,13] float64 table of
     include/pipnet_amd.h (augment.sample_params draws it).  Returns [B,s2,s2,3] uint8."""
-    import ctypes
-
-    import numpy as np
-    if not (pixels.is_cuda and pixels.dtype == torch.uint8 and pixels.is_contiguous()):
-        raise RuntimeError("augment_geometry_rgb8: pixels must be a contiguous uint8 ROCm device tensor "
-                           "(there is no CPU fallback)")
-    if not (offsets.is_cuda and offsets.dtype == torch.int64 and sizes.is_cuda and sizes.dtype == torch.int32):
-        raise RuntimeError("augment_geometry_rgb8: offsets (int64) / sizes (int32) must be device tensors")
-    sizes_np = np.ascontiguousarray(np.asarray(sizes_host, dtype=np.int32).reshape(-1, 2))
-    b = sizes_np.shape[0]
-    if offsets.shape != (b,) or tuple(sizes.shape) != (b, 2):
-        raise RuntimeError(f"augment_geometry_rgb8: {b} images but offsets {tuple(offsets.shape)}, "
-                           f"sizes {tuple(sizes.shape)}")
+    sizes_np, b = _ragged_batch("augment_geometry_rgb8", pixels, offsets, sizes, sizes_host)
     s1, s2 = int(s1), int(s2)
     gp = _host_params(gparams, (b, AUG_GEOM_PARAMS), "augment_geometry_rgb8 gparams")
     if b:
@@ -1431,11 +1372,9 @@ def augment_view_rgb8(images: Tensor, vparams, s: int, mean, std, grayscale: boo
     [B,S2,S2,3] uint8 (augment_geometry_rgb8's output), ``vparams`` the host [V,B,8] float64
     table of include/pipnet_amd.h.  ``noise`` [V,B,3,s,s] injects the addends of the flagged
     images; None draws N(0, noise_std^2) from Philox keyed by ``seed``.  Returns [V,B,3,s,s] fp32."""
-    import ctypes
-    if not (images.is_cuda and images.dtype == torch.uint8 and images.is_contiguous() and images.dim() == 4
-            and images.shape[1] == images.shape[2] and images.shape[3] == 3):
-        raise RuntimeError("augment_view_rgb8: images must be a contiguous [B,S,S,3] uint8 ROCm device tensor "
-                           "(there is no CPU fallback)")
+    _operand("augment_view_rgb8", "images", images, dtype=torch.uint8)
+    if images.dim() != 4 or images.shape[1] != images.shape[2] or images.shape[3] != 3:
+        raise RuntimeError(f"augment_view_rgb8: images must be [B,S,S,3], got {tuple(images.shape)}")
     b, s2, s = int(images.shape[0]), int(images.shape[1]), int(s)
     vp = torch.as_tensor(vparams)
     if vp.dim() != 3:
@@ -1455,10 +1394,7 @@ def augment_view_rgb8(images: Tensor, vparams, s: int, mean, std, grayscale: boo
         if bool(((vp[:, :, 7] < 0) | (vp[:, :, 7] >= 2 ** 31)).any()):
             raise RuntimeError("augment_view_rgb8: image ids must be in [0, 2^31)")
     dev = images.device
-    if noise is not None:
-        _chk(noise, "noise")
-        if tuple(noise.shape) != (v, b, 3, s, s):
-            raise RuntimeError(f"augment_view_rgb8: noise must be {(v, b, 3, s, s)}, got {tuple(noise.shape)}")
+    _operand("augment_view_rgb8", "noise", noise, shape=(v, b, 3, s, s), device=dev, optional=True)
     out = torch.empty((v, b, 3, s, s), device=dev, dtype=torch.float32)
     m = (ctypes.c_float * 3)(*[float(x) for x in mean])
     sd = (ctypes.c_float * 3)(*[float(x) for x in std])
@@ -1478,18 +1414,16 @@ def train_loss(proto_nhwc: Tensor, pooled: Tensor, out: Tensor, ys: Tensor, mult
                mode: str) -> Tuple[Tensor, Optional[Tensor]]:
     """calculate_loss (pipnet/train.py:154-250) on the device: returns (stats [8] fp32 =
     align, tanh, class, loss, correct, w_align, w_tanh, w_class; d_out [N,K] or None)."""
-    _chk(proto_nhwc, "proto features (NHWC)")
-    _chk(pooled, "pooled")
-    _chk(out, "classifier output")
+    _chk_rows("train_loss", proto_nhwc, "proto features (NHWC)", 4)
     n, h, w, p = proto_nhwc.shape
-    if n % 2 or tuple(pooled.shape) != (n, p) or out.shape[0] != n:
-        raise RuntimeError(f"train_loss: proto {tuple(proto_nhwc.shape)}, pooled {tuple(pooled.shape)}, "
-                           f"out {tuple(out.shape)} must share an even batch = cat([xs1, xs2])")
+    _operand("train_loss", "classifier output", out, device=proto_nhwc.device)
+    if n % 2 or out.dim() != 2 or out.shape[0] != n:
+        raise RuntimeError(f"train_loss: proto {tuple(proto_nhwc.shape)} and out {tuple(out.shape)} must share an "
+                           f"even batch = cat([xs1, xs2])")
     bh, k = n // 2, out.shape[1]
-    if not (ys.is_cuda and ys.dtype == torch.int64 and ys.is_contiguous() and ys.shape == (bh,)):
-        raise RuntimeError("train_loss: labels must be a contiguous int64 device tensor of the half batch")
-    if mult is not None:
-        _chk(mult, "normalization_multiplier")
+    _operand("train_loss", "pooled", pooled, shape=(n, p), device=out.device)
+    _operand("train_loss", "labels", ys, dtype=torch.int64, shape=(bh,), device=out.device)
+    _operand("train_loss", "normalization_multiplier", mult, shape=1, device=out.device, optional=True)
     partial = torch.empty(_lib.load().pipnet_train_align_partials(), device=out.device, dtype=torch.float64)
     s = _stream(out)
     _lib.call("pipnet_train_align_partial_f32", proto_nhwc.data_ptr(), bh, h * w, p, partial.data_ptr(), s)
@@ -1504,13 +1438,11 @@ def train_loss(proto_nhwc: Tensor, pooled: Tensor, out: Tensor, ys: Tensor, mult
 
 def nonneg_linear_backward(d_out: Tensor, x: Tensor, w: Tensor, want_bias: bool) -> Tuple[Tensor, Optional[Tensor]]:
     """Gradients of F.linear(x, relu(w), b) (pipnet.py:54-71): (dW, db or None)."""
-    _chk(d_out, "d_out")
-    _chk(x, "classifier input")
-    _chk(w, "classifier weight")
-    n, d = x.shape
-    k = w.shape[0]
-    if tuple(w.shape) != (k, d) or tuple(d_out.shape) != (n, k):
-        raise RuntimeError("nonneg_linear_backward: shapes disagree")
+    _chk_rows("nonneg_linear_backward", w, "classifier weight", 2)
+    k, d = w.shape
+    n = x.shape[0]
+    _operand("nonneg_linear_backward", "classifier input", x, shape=(n, d), device=w.device)
+    _operand("nonneg_linear_backward", "d_out", d_out, shape=(n, k), device=w.device)
     dw = torch.empty_like(w)
     db = torch.empty(k, device=w.device, dtype=torch.float32) if want_bias else None
     _lib.call("pipnet_nonneg_linear_bwd_f32", d_out.data_ptr(), x.data_ptr(), n, d, w.data_ptr(), k,
@@ -1525,10 +1457,8 @@ def adamw_step_(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor
     bias corrections from the double hyper-parameters, as torch computes them for a
     non-capturable optimizer); ``post`` = (delta, floor) applies p = max(p - delta, floor)
     afterwards (pipnet/train.py:134-140)."""
-    for t, what in ((param, "parameter"), (grad, "gradient"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
-        _chk(t, what)
-        if t.shape != param.shape:
-            raise RuntimeError(f"adamw_step_: {what} shape {tuple(t.shape)} != {tuple(param.shape)}")
+    _operand("adamw_step_", "parameter", param)
+    _chk_same("adamw_step_", param, gradient=grad, exp_avg=exp_avg, exp_avg_sq=exp_avg_sq)
     delta, floor = post if post is not None else (0.0, 0.0)
     _lib.call("pipnet_adamw_step_f32", param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(),
               exp_avg_sq.data_ptr(), param.numel(), lr, beta1, beta2, eps, weight_decay, int(step),
@@ -1546,20 +1476,15 @@ def clamp_min_(x: Tensor, lo: float) -> Tensor:
 # ---- backward building blocks (csrc/backward_ops.hip) ----------------------------------------
 def wgrad(a: Tensor, b: Tensor, out: Optional[Tensor] = None, accumulate: bool = False) -> Tensor:
     """out[N1,N2] (+)= a[M,N1]^T @ b[M,N2] (weight gradient dY^T X), deterministic."""
-    for t, what in ((a, "wgrad A"), (b, "wgrad B")):
-        require_device(t, what)
-        if t.dim() != 2 or t.stride(1) != 1:
-            raise RuntimeError(f"{what}: expects a 2-D row-major view")
+    _operand("wgrad", "A", a, layout="rows")
+    _operand("wgrad", "B", b, device=a.device, layout="rows")
     m, n1 = a.shape
     if b.shape[0] != m:
         raise RuntimeError(f"wgrad: row counts differ {tuple(a.shape)} vs {tuple(b.shape)}")
     n2 = b.shape[1]
+    _operand("wgrad", "out", out, shape=(n1, n2), device=a.device, layout="rows", optional=not accumulate)
     if out is None:
-        if accumulate:
-            raise RuntimeError("wgrad: accumulate needs out")
         out = torch.empty((n1, n2), device=a.device, dtype=torch.float32)
-    elif tuple(out.shape) != (n1, n2) or out.stride(1) != 1:
-        raise RuntimeError("wgrad: out shape")
     nbytes = _lib.load().pipnet_wgrad_workspace_bytes(m, n1, n2)
     ws = torch.empty(max(nbytes // 4, 1), device=a.device, dtype=torch.float32)
     _lib.call("pipnet_wgrad_f32", a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), m, n1, n2, out.data_ptr(),
@@ -1569,16 +1494,12 @@ def wgrad(a: Tensor, b: Tensor, out: Optional[Tensor] = None, accumulate: bool =
 
 def colsum(a: Tensor, out: Optional[Tensor] = None, accumulate: bool = False) -> Tensor:
     """out[N] (+)= a[M,N].sum(0), deterministic."""
-    require_device(a, "colsum input")
-    if a.dim() != 2 or a.shape[1] < 1 or (a.shape[1] > 1 and a.stride(1) != 1) or \
-            (a.shape[0] > 1 and a.stride(0) < a.shape[1]):
-        raise RuntimeError(f"colsum: expects a 2-D row-major view with unit column stride "
-                           f"(got shape {tuple(a.shape)}, stride {a.stride()})")
+    _operand("colsum", "input", a, layout="rows")
     m, n = a.shape
-    _chk_vec("colsum", a, n, out=out)
+    if n < 1:
+        raise RuntimeError(f"colsum: needs at least one column (got shape {tuple(a.shape)})")
+    _operand("colsum", "out", out, shape=n, device=a.device, optional=not accumulate)
     if out is None:
-        if accumulate:
-            raise RuntimeError("colsum: accumulate needs out")
         out = torch.empty(n, device=a.device, dtype=torch.float32)
     ws = torch.empty(_lib.load().pipnet_colsum_workspace_bytes(n) // 4, device=a.device, dtype=torch.float32)
     _lib.call("pipnet_colsum_f32", a.data_ptr(), a.stride(0) if m > 1 else n, m, n, out.data_ptr(), int(accumulate),
@@ -1669,13 +1590,12 @@ def dwconv7_wgrad(dz_nhwc: Tensor, x_nhwc: Tensor, dw_packed: Tensor, db: Tensor
 def wgrad_conv(dy_nhwc: Tensor, x_nhwc: Tensor, kh: int, kw: int, stride: int, out: Tensor,
                accumulate: bool = False, pad: int = 0) -> Tensor:
     """Packed [Cout, KH*KW*Cin] weight gradient of a KHxKW conv (stride, zero padding)."""
-    _chk(dy_nhwc, "d conv output")
-    _chk(x_nhwc, "conv input")
+    _chk_rows("wgrad_conv", x_nhwc, "conv input", 4)
     b, h, w, cin = x_nhwc.shape
     cout = dy_nhwc.shape[-1]
     oh, ow = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
-    if tuple(dy_nhwc.shape) != (b, oh, ow, cout) or out.numel() != cout * kh * kw * cin:
-        raise RuntimeError(f"wgrad_conv: dY {tuple(dy_nhwc.shape)}, x {tuple(x_nhwc.shape)}, k{kh}x{kw}/{stride}")
+    _operand("wgrad_conv", "d conv output", dy_nhwc, shape=(b, oh, ow, cout), device=x_nhwc.device)
+    _operand("wgrad_conv", "out", out, shape=cout * kh * kw * cin, device=x_nhwc.device)
     nbytes = _lib.load().pipnet_wgrad_workspace_bytes(b * oh * ow, cout, kh * kw * cin)
     ws = torch.empty(max(nbytes // 4, 1), device=x_nhwc.device, dtype=torch.float32)
     _lib.call("pipnet_wgrad_conv_f32", dy_nhwc.data_ptr(), x_nhwc.data_ptr(), b, h, w, cin, kh, kw, stride, pad, cout,
@@ -1686,14 +1606,13 @@ def wgrad_conv(dy_nhwc: Tensor, x_nhwc: Tensor, kh: int, kw: int, stride: int, o
 def wgrad_conv2x2(dy_nhwc: Tensor, x_nhwc: Tensor, stride: int, out: Tensor, accumulate: bool = False) -> Tensor:
     """Packed [Cout, 4*Cin] weight gradient of the 2x2 downsample conv."""
     _chk_rows("wgrad_conv2x2", x_nhwc, "conv input", 4)
-    _chk_rows("wgrad_conv2x2", dy_nhwc, "d conv output", 4)
     b, h, w, cin = x_nhwc.shape
     cout = dy_nhwc.shape[-1]
-    if stride not in (1, 2) or h < 2 or w < 2 or dy_nhwc.device != x_nhwc.device or \
-            tuple(dy_nhwc.shape) != (b, (h - 2) // stride + 1, (w - 2) // stride + 1, cout):
-        raise RuntimeError(f"wgrad_conv2x2: dY {tuple(dy_nhwc.shape)} on {dy_nhwc.device}, x {tuple(x_nhwc.shape)} "
-                           f"on {x_nhwc.device}, stride {stride}")
-    _chk_vec("wgrad_conv2x2", x_nhwc, cout * 4 * cin, out=out)
+    if stride not in (1, 2) or h < 2 or w < 2:
+        raise RuntimeError(f"wgrad_conv2x2: x {tuple(x_nhwc.shape)}, stride {stride}")
+    _operand("wgrad_conv2x2", "d conv output", dy_nhwc, device=x_nhwc.device,
+             shape=(b, (h - 2) // stride + 1, (w - 2) // stride + 1, cout))
+    _operand("wgrad_conv2x2", "out", out, shape=cout * 4 * cin, device=x_nhwc.device)
     nbytes = _lib.load().pipnet_wgrad_workspace_bytes(dy_nhwc.numel() // cout, cout, 4 * cin)
     ws = torch.empty(max(nbytes // 4, 1), device=x_nhwc.device, dtype=torch.float32)
     _lib.call("pipnet_wgrad_conv2x2_f32", dy_nhwc.data_ptr(), x_nhwc.data_ptr(), b, h, w, cin, stride, cout,
@@ -1713,10 +1632,9 @@ def head_backward(proto_nhwc: Tensor, pooled: Tensor, d_out: Optional[Tensor], w
     if d_out is not None:
         if w is None:
             raise RuntimeError("head_backward: d_out needs the classifier weight")
-        require_device(w, "head_backward classifier weight")
-        if w.dim() != 2 or w.shape[1] != p or w.shape[0] < 1 or not w.is_contiguous() or w.device != proto_nhwc.device:
-            raise RuntimeError(f"head_backward: the classifier weight must be a contiguous (K, {p}) tensor on "
-                               f"{proto_nhwc.device} (got shape {tuple(w.shape)}, stride {w.stride()})")
+        if w.dim() != 2 or w.shape[0] < 1:
+            raise RuntimeError(f"head_backward: the classifier weight must be (K, {p}), got {tuple(w.shape)}")
+        _operand("head_backward", "classifier weight", w, shape=(w.shape[0], p), device=proto_nhwc.device)
         _chk_vec("head_backward", proto_nhwc, n * w.shape[0], d_out=d_out)
     d_logits = torch.empty_like(proto_nhwc)
     amax = torch.empty((n, p), device=proto_nhwc.device, dtype=torch.int32)
@@ -1794,14 +1712,11 @@ def stride_scatter(x: Tensor, h: int, w: int, stride: int, out: Optional[Tensor]
                    accumulate: bool = False) -> Tensor:
     """NHWC [B, OH, OW, C] -> [B, h, w, C] with x on the stride lattice, zeros elsewhere
     (added into ``out`` when accumulate)."""
-    _chk(x, "scatter input")
+    _chk_rows("stride_scatter", x, "input", 4)
     b, oh, ow, c = x.shape
+    _operand("stride_scatter", "out", out, shape=(b, h, w, c), device=x.device, optional=not accumulate)
     if out is None:
-        if accumulate:
-            raise RuntimeError("stride_scatter: accumulate needs out")
         out = torch.empty((b, h, w, c), device=x.device, dtype=torch.float32)
-    elif tuple(out.shape) != (b, h, w, c):
-        raise RuntimeError(f"stride_scatter: out {tuple(out.shape)}")
     _lib.call("pipnet_stride_scatter_f32", x.data_ptr(), b, oh, ow, c, h, w, stride, int(accumulate), out.data_ptr(),
               _stream(x))
     return out
@@ -1827,9 +1742,7 @@ def attr_path_images(x: Tensor, baseline, alpha: Tensor) -> Tensor:
     _chk_rows("attr_path_images", x, "image", 3)
     if x.shape[0] != 3:
         raise RuntimeError(f"attr_path_images: image must be [3,H,W], got {tuple(x.shape)}")
-    _chk_rows("attr_path_images", alpha, "alpha", 1)
-    if alpha.device != x.device:
-        raise RuntimeError("attr_path_images: alpha must be on the image's device")
+    _operand("attr_path_images", "alpha", alpha, shape=(alpha.numel(),), device=x.device)
     bt, bv = _attr_baseline("attr_path_images", x, baseline)
     _, h, w = x.shape
     out = torch.empty((alpha.numel(), h, w, 4), device=x.device, dtype=torch.float32)
@@ -1844,15 +1757,11 @@ def attr_head_backward(soft_nhwc: Tensor, u: Tensor, loc: Optional[Tensor], pool
     spatial sum.  Any P and any batch."""
     _chk_rows("attr_head_backward", soft_nhwc, "soft map", 4)
     b, h, w, p = soft_nhwc.shape
-    _chk_rows("attr_head_backward", u, "upstream vector", 2)
-    if tuple(u.shape) != (b, p) or u.device != soft_nhwc.device:
-        raise RuntimeError(f"attr_head_backward: u {tuple(u.shape)} vs map {tuple(soft_nhwc.shape)}")
+    _operand("attr_head_backward", "upstream vector", u, shape=(b, p), device=soft_nhwc.device)
     if pool_mode not in (0, 1):
         raise RuntimeError(f"attr_head_backward: pool_mode {pool_mode}")
-    if pool_mode == 0:
-        if loc is None or tuple(loc.shape) != (b, p) or loc.dtype != torch.int32 or not loc.is_contiguous() \
-                or loc.device != soft_nhwc.device:
-            raise RuntimeError("attr_head_backward: max mode needs loc [B,P] int32 contiguous on the map's device")
+    if pool_mode == 0:                                        # max mode reads where each maximum sits
+        _operand("attr_head_backward", "loc", loc, dtype=torch.int32, shape=(b, p), device=soft_nhwc.device)
     d = torch.empty_like(soft_nhwc)
     _lib.call("pipnet_attr_head_bwd_f32", soft_nhwc.data_ptr(), u.data_ptr(), _ptr(loc) if pool_mode == 0 else None,
               b, h * w, p, pool_mode, 1.0 / float(tau), d.data_ptr(), _stream(soft_nhwc))
@@ -1864,17 +1773,16 @@ def attr_stem_dx(dz_nhwc: Tensor, w: Tensor, h: int, wd: int, out: Optional[Tens
     ``out``: [B, ld] rows (ld >= 3 h w) to write the images into (a slice of the path's gradient store)."""
     _chk_rows("attr_stem_dx", dz_nhwc, "dz", 4)
     b, zh, zw, o = dz_nhwc.shape
-    _chk_rows("attr_stem_dx", w, "stem weight", 4)
-    if tuple(w.shape) != (o, 3, 4, 4) or w.device != dz_nhwc.device or (zh, zw) != (h // 4, wd // 4):
-        raise RuntimeError(f"attr_stem_dx: dz {tuple(dz_nhwc.shape)}, weight {tuple(w.shape)}, image {(h, wd)}")
+    _operand("attr_stem_dx", "stem weight", w, shape=(o, 3, 4, 4), device=dz_nhwc.device)
+    if (zh, zw) != (h // 4, wd // 4):
+        raise RuntimeError(f"attr_stem_dx: dz {tuple(dz_nhwc.shape)} does not belong to an image {(h, wd)}")
     n = 3 * h * wd
     if out is None:
         out = torch.empty((b, 3, h, wd), device=dz_nhwc.device, dtype=torch.float32)
         ld = n
     else:
-        require_device(out, "attr_stem_dx out")
-        if out.dim() != 2 or out.shape[0] != b or out.shape[1] < n or out.stride(1) != 1 or out.stride(0) < n \
-                or out.device != dz_nhwc.device:
+        _operand("attr_stem_dx", "out", out, device=dz_nhwc.device, layout="rows")
+        if out.shape[0] != b or out.shape[1] < n or out.stride(0) < n:
             raise RuntimeError(f"attr_stem_dx: out {tuple(out.shape)} stride {out.stride()} cannot hold {(b, n)}")
         ld = out.stride(0)
     _lib.call("pipnet_attr_stem_dx_f32", dz_nhwc.data_ptr(), w.data_ptr(), b, h, wd, o, ld, out.data_ptr(),
@@ -1900,8 +1808,7 @@ def attr_path_weights(scores: Tensor, method: str, alphas: Optional[Tensor] = No
     else:
         weights, cutoff = out
         _chk_same("attr_path_weights", scores, weights=weights)
-        if cutoff.numel() != 1 or cutoff.dtype != torch.int64 or cutoff.device != scores.device:
-            raise RuntimeError("attr_path_weights: cutoff out must be one int64 on the scores' device")
+        _operand("attr_path_weights", "cutoff out", cutoff, dtype=torch.int64, shape=1, device=scores.device)
     _lib.call("pipnet_attr_path_weights_f32", scores.data_ptr(), _ptr(alphas) if method == "idg" else None,
               _ptr(substep) if method == "idg" else None, s, ATTR_METHOD[method], LIG_ALPHA_STAR, weights.data_ptr(),
               cutoff.data_ptr(), _stream(scores))
@@ -1911,10 +1818,10 @@ def attr_path_weights(scores: Tensor, method: str, alphas: Optional[Tensor] = No
 def attr_path_reduce(grads: Tensor, weights: Tensor, x: Tensor, baseline, out: Optional[Tensor] = None) -> Tensor:
     """(x - baseline) * sum_i weights[i] * grads[i] summed in step order: grads [S, ld] rows holding one image's
     gradient each (the first x.numel() floats of a row), x of any shape -> a map of x's shape."""
-    require_device(grads, "attr_path_reduce grads")
-    _chk(x, "attr_path_reduce image")
+    _operand("attr_path_reduce", "image", x)
     n = x.numel()
-    if grads.dim() != 2 or grads.shape[1] < n or grads.stride(1) != 1 or grads.stride(0) < n or grads.device != x.device:
+    _operand("attr_path_reduce", "grads", grads, device=x.device, layout="rows")
+    if grads.shape[1] < n or grads.stride(0) < n:
         raise RuntimeError(f"attr_path_reduce: grads {tuple(grads.shape)} stride {grads.stride()} vs image {n}")
     s = grads.shape[0]
     _chk_vec("attr_path_reduce", x, s, weights=weights)

@@ -319,8 +319,9 @@ int pipnet_softmax_pool_f32(const float* feat, int B, int HW, int P, int pool_mo
  *   (initialise to -1 = empty slot), st_loc [G,P,k] int32, st_fill [G,P] int32 (initialise to 0).
  *   After any sequence of calls the state is the reference's one-image-at-a-time list
  *   (vis_pipnet.py:248-274): the k best by (score descending, dataset index ascending).
- *   1 <= k <= 32.  out [B,K] (NULL to skip): images with amax(out) == 0 are added to *abstained
+ *   1 <= k <= PIPNET_TOPK_MAX_K.  out [B,K] (NULL to skip): images with amax(out) == 0 are added to *abstained
  *   (device int64; vis_pipnet.py:217-219), whatever their group. */
+#define PIPNET_TOPK_MAX_K 32
 int pipnet_softmax_pool_argmax_f32(const float* feat, int B, int H, int W, int P, float* proto, float* pooled,
                                    int32_t* loc, void* workspace, void* stream);
 int pipnet_map_argmax_f32(const float* map, int B, int H, int W, int P, float* val, int32_t* loc, void* stream);
@@ -345,10 +346,11 @@ int pipnet_topk_update(const float* score, const int32_t* loc, int B, int P, int
  *     0 .. min(n, M) - 1 hold the kept pairs in prototype order (prototype, pooled, weight, the
  *     product rounded to fp32, loc), the others (-1, 0, 0, 0, -1).  Every output element is
  *     written by the one kernel (no zeroed buffer, no memset: graph-capturable).
- *   1 <= C <= K <= 2048, 1 <= P <= 2048, M >= 1, B >= 0; a limit violation, a negative (or NaN)
+ *   1 <= C <= K <= PIPNET_LOCAL_EXPLAIN_MAX, 1 <= P <= PIPNET_LOCAL_EXPLAIN_MAX, M >= 1, B >= 0; a limit violation, a negative (or NaN)
  *   min_abs or a NULL pointer returns PIPNET_ERR_ARG before any HIP call; B == 0 is PIPNET_OK.
  *   Non-finite scores / logits land somewhere in the order (a NaN product is never kept); they
  *   cannot make the kernel read or write out of bounds or loop. */
+#define PIPNET_LOCAL_EXPLAIN_MAX 2048 /* the limit on P and K above */
 int pipnet_local_explain_f32(const float* pooled, const int32_t* loc, const float* out, const float* W, int64_t ldw,
                              int B, int P, int K, int C, int M, double min_abs, int32_t* cls, float* cls_logit,
                              int32_t* n, int32_t* e_proto, float* e_sim, float* e_w, float* e_simw, int32_t* e_loc,

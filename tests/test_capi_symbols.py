@@ -4,6 +4,8 @@ import ctypes
 import os
 import re
 
+import pytest
+
 from count_pipnet_amd import _lib, build
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "pipnet_amd.h")
@@ -18,6 +20,100 @@ def test_header_declares_entry_points():
     syms = declared_symbols()
     assert "pipnet_linear_f32" in syms and "pipnet_count_gumbel_f32" in syms
     assert set(syms) == set(_lib.SIGNATURES), "ctypes binding and header disagree"
+
+
+PARSER_SNIPPET = """
+/* a comment with ( and ) and ; int pipnet_not_a_declaration(int x); */
+#define PIPNET_SNIPPET_LIMIT 48   /* trailing ( comment ; ) that
+                                     runs over two lines */
+#define PIPNET_NOT_A_NUMBER (1 << 4)
+// int pipnet_commented_out(void);
+int pipnet_snippet_version(void);
+const char* pipnet_snippet_name(int status);
+int64_t pipnet_snippet_bytes(int M, int64_t n);
+int pipnet_snippet_launch(const float* A, int64_t lda, void* ws, /* why ( */ uint64_t seed,
+                          double lr, float eps,   // the tail ) ;
+                          const int32_t* loc,
+                          void* stream);
+int pipnet_snippet_label(int M, char* buf, int cap);
+"""
+
+
+def test_parser_reads_the_shapes_the_header_uses():
+    P, I32, I64, U64, F32, F64 = _lib.P, _lib.I32, _lib.I64, _lib.U64, _lib.F32, _lib.F64
+    args, res, consts = _lib.parse_header(PARSER_SNIPPET)
+    assert args == {"pipnet_snippet_version": [], "pipnet_snippet_name": [I32], "pipnet_snippet_bytes": [I32, I64],
+                    "pipnet_snippet_launch": [P, I64, P, U64, F64, F32, P, P],
+                    "pipnet_snippet_label": [I32, ctypes.c_char_p, I32]}
+    assert res == {"pipnet_snippet_version": I32, "pipnet_snippet_name": ctypes.c_char_p, "pipnet_snippet_bytes": I64,
+                   "pipnet_snippet_launch": I32, "pipnet_snippet_label": I32}
+    assert consts == {"SNIPPET_LIMIT": 48}
+    assert (I32, I64, U64, F32, F64, P) == (ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float,
+                                            ctypes.c_double, ctypes.c_void_p)
+
+
+@pytest.mark.parametrize("decl", ["int pipnet_x(size_t n);", "int pipnet_x(const float* a, unsigned n);",
+                                  "int pipnet_x(long n, void* stream);", "float pipnet_x(int n);",
+                                  "void pipnet_x(int n);", "int pipnet_x(int);"])
+def test_parser_refuses_a_type_it_does_not_know(decl):
+    with pytest.raises(_lib.PipnetLibraryError, match="pipnet_x"):
+        _lib.parse_header(decl)
+
+
+def test_missing_header_is_a_library_error(monkeypatch, tmp_path):
+    monkeypatch.setattr(_lib, "HEADER", str(tmp_path / "absent.h"))
+    with pytest.raises(_lib.PipnetLibraryError, match="missing"):
+        _lib._read_header()
+
+
+def test_parsed_signatures_of_pinned_entry_points():
+    """Argument lists written out by hand (the table this binding kept before it read the header): between them
+    every scalar type, the label buffers and every non-int return type."""
+    P, I32, I64, U64, F32, F64, S = _lib.P, _lib.I32, _lib.I64, _lib.U64, _lib.F32, _lib.F64, ctypes.c_char_p
+    want = {
+        "pipnet_linear_f32": [P, I64, P, P, P, P, I64, P, I64, I32, I32, I32, I32, P],
+        "pipnet_adamw_step_f32": [P, P, P, P, I64, F64, F64, F64, F64, F64, I64, I32, F32, F32, P],
+        "pipnet_count_gumbel_f32": [P, I32, I32, I32, F32, P, U64, U64, P, P, P],
+        "pipnet_linear_f32_label": [I32, I32, I32, I32, I32, I32, S, I32],
+        "pipnet_part_purity_update": [P, I64, P, P, I32, I32, I64, F64, I32, I32, I32, I32, I32, P, P, P, I64, P, P, P,
+                                      I32, I32, P, P, P, P, P, P],
+        "pipnet_proto_stats_update_f32": [P, I64, P, I32, I32, I32, F32, P, I32, P, P, P, P, P, P, P, P, P],
+    }
+    assert len(want["pipnet_part_purity_update"]) == 28
+    for name, args in want.items():
+        assert _lib.SIGNATURES[name] == args, name
+    other = {"pipnet_wgrad_workspace_bytes": I64, "pipnet_train_partials_floats": I64,
+             "pipnet_bn_workspace_floats": I64, "pipnet_softmax_pool_linear_part_floats": I64,
+             "pipnet_amd_status_string": S, "pipnet_amd_source_digest": S}
+    assert {n: r for n, r in _lib.RESTYPES.items() if r is not I32} == other
+    assert len(_lib.SIGNATURES) == len(declared_symbols()) >= 101
+
+
+def test_python_constants_are_the_headers():
+    from count_pipnet_amd import augment
+    from count_pipnet_amd import kernels as K
+    defines = {m[1]: int(m[2]) for m in re.finditer(r"^#define PIPNET_(\w+) (\d+)\b", open(HEADER).read(), flags=re.M)}
+    assert defines["AUG_GEOM_PARAMS"] == 13 and defines["EPI_DUAL_BIAS_RELU"] == 12      # the regex sees them
+    for py, c in [(K.PROTO_STATS_MAX_BINS, "PROTO_STATS_MAX_BINS"), (K.PART_PURITY_MAX_PARTS, "PART_PURITY_MAX_PARTS"),
+                  (K.AUG_GEOM_PARAMS, "AUG_GEOM_PARAMS"), (K.AUG_VIEW_PARAMS, "AUG_VIEW_PARAMS"),
+                  (augment.GEOM_PARAMS, "AUG_GEOM_PARAMS"), (augment.VIEW_PARAMS, "AUG_VIEW_PARAMS"),
+                  (K.LOCAL_EXPLAIN_MAX, "LOCAL_EXPLAIN_MAX"), (K.TOPK_MAX_K, "TOPK_MAX_K"),
+                  (_lib.ABI_VERSION, "AMD_ABI_VERSION")]:
+        assert py == defines[c], c
+    epi = {k: v for k, v in defines.items() if k.startswith("EPI_")}
+    assert len(epi) == 13 and all(getattr(_lib, k) == v for k, v in epi.items())
+
+
+def test_library_defines_exactly_the_declared_symbols():
+    """Both directions: no declared entry point is missing from the built library, and the library exports no
+    pipnet_* C symbol the header does not declare."""
+    import shutil
+    import subprocess
+    build.build()
+    nm = shutil.which("nm") or "/opt/rocm/lib/llvm/bin/llvm-nm"
+    out = subprocess.run([nm, "-D", "--defined-only", build.LIB], capture_output=True, text=True, check=True).stdout
+    defined = {line.split()[-1] for line in out.splitlines() if line.split() and line.split()[-1].startswith("pipnet_")}
+    assert defined == set(declared_symbols())
 
 
 def test_library_loads_and_exports_all_symbols():
@@ -153,6 +249,5 @@ def test_bf16_labels_come_from_the_library_plan():
         label = K.bf16_conv_kernel_name(64, h, h, cin, cout, k, k, s, pad, epi)
         assert label in out, (name, label)
     # a requested tile is validated, not chosen: tile 8 needs a 3x3 stride-1 halo shape
-    import pytest
     with pytest.raises(RuntimeError):
         K.bf16_conv_plan(64, 56, 56, 256, 512, 1, 1, 2, 0, _lib.EPI_BIAS, 8)
