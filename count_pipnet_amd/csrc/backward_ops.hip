@@ -521,11 +521,25 @@ __global__ __launch_bounds__(256) void argmax_hw_kernel(const float* __restrict_
 
 // d loss / d pooled[b,p] = sum_k d_out[b,k] relu(W[k,p])                      (classifier)
 //                        - w_tanh/2 * C/P * (1 - t^2) / (t + 1e-8),  t = tanh(C * sum_{b' in half} pooled[b',p])
+// The tanh term of one (half, prototype): `half` = the half's Bh rows of pooled [.][P], summed in ascending
+// row order.  Both forms of pool_grad_kernel take the term from here, so they give the same bits.
+PIPNET_DEV float tanh_term_grad(const float* __restrict__ half, int Bh, int P, int p, float w_tanh, float coeff) {
+  float s = 0.f;
+  for (int i = 0; i < Bh; ++i) s += coeff * half[(int64_t)i * P + p];
+  const float th = tanhf(s);
+  return -0.5f * w_tanh / (float)P * coeff * (1.f - th * th) / (th + 1e-8f);
+}
+
+// COEF (the row-sharded entry points): the tanh term is read from tcoef [2][P], computed once by
+// tanh_coef_kernel over the gathered rows of every rank -- the column sum per element below is O(Bh)
+// loads per element, which a global Bh of several hundred no longer hides.
+template <bool COEF = false>
 __global__ __launch_bounds__(256) void pool_grad_kernel(const float* __restrict__ pooled, int Bh, int P,
                                                         const float* __restrict__ d_out, const float* __restrict__ W,
                                                         int K, float w_tanh, float coeff,
                                                         const float* __restrict__ extra,
-                                                        float* __restrict__ dpool) {
+                                                        float* __restrict__ dpool,
+                                                        const float* __restrict__ tcoef = nullptr) {
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int N = 2 * Bh;
   if (t >= (int64_t)N * P) return;
@@ -535,14 +549,24 @@ __global__ __launch_bounds__(256) void pool_grad_kernel(const float* __restrict_
     for (int k = 0; k < K; ++k) g = fmaf(d_out[(int64_t)b * K + k], fmaxf(W[(int64_t)k * P + p], 0.f), g);
   }
   if (w_tanh != 0.f) {
-    const int h0 = (b / Bh) * Bh;
-    float s = 0.f;
-    for (int i = 0; i < Bh; ++i) s += coeff * pooled[(int64_t)(h0 + i) * P + p];
-    const float th = tanhf(s);
-    g += -0.5f * w_tanh / (float)P * coeff * (1.f - th * th) / (th + 1e-8f);
+    if constexpr (COEF) {
+      g += tcoef[(int64_t)(b / Bh) * P + p];
+    } else {
+      const int h0 = (b / Bh) * Bh;
+      g += tanh_term_grad(pooled + (int64_t)h0 * P, Bh, P, p, w_tanh, coeff);
+    }
   }
   if (extra) g += extra[t];
   dpool[t] = g;
+}
+
+// tcoef[half][p] = the tanh term over pooled_all [2 Bh_all][P] (every rank's rows, global batch order)
+__global__ __launch_bounds__(256) void tanh_coef_kernel(const float* __restrict__ pooled_all, int Bh_all, int P,
+                                                        float w_tanh, float coeff, float* __restrict__ tcoef) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= 2 * P) return;
+  const int half = t / P, p = t - half * P;
+  tcoef[t] = tanh_term_grad(pooled_all + (int64_t)half * Bh_all * P, Bh_all, P, p, w_tanh, coeff);
 }
 
 // One wave per pixel pair (view 1 pixel n, view 2 pixel n): align gradient, max-pool
@@ -722,23 +746,51 @@ extern "C" int pipnet_dwconv7_wgrad_f32(const float* dz, const float* x, int B, 
   return finish2(partial, DWG_S, 49 * C, C, dw_packed, db, accumulate, s);
 }
 
-extern "C" int pipnet_head_bwd_f32(const float* proto, const float* pooled, int Bh, int HW, int P, const float* d_out,
-                                   const float* W, int K, float w_align, float w_tanh, float tanh_coeff,
-                                   int32_t* argmax_ws, float* dpool_ws, float* d_logits, void* stream) {
+// d pooled (or d counts) of a head backward.  ``all`` == NULL: the rows are the whole batch and every element sums
+// its own column (the launch the full-batch entry points have always made).  Otherwise the rows are one rank's
+// shard of a batch of 2 Bh_all rows ``all``: the [2][P] tanh terms are computed once into tcoef_ws, then read.
+static int pool_grad_launch(const float* rows, int Bh, int P, const float* d_out, const float* W, int K, float w_tanh,
+                            float coeff, const float* extra, float* dpool, const float* all, int Bh_all,
+                            float* tcoef_ws, hipStream_t s) {
+  const int64_t NP = (int64_t)2 * Bh * P;
+  const dim3 grid((unsigned)((NP + 255) / 256));
+  if (!all) {
+    hipLaunchKernelGGL(pool_grad_kernel<false>, grid, dim3(256), 0, s, rows, Bh, P, d_out, W, K, w_tanh, coeff, extra,
+                       dpool, nullptr);
+    PIPNET_CHECK_LAUNCH();
+    return PIPNET_OK;
+  }
+  if (w_tanh != 0.f) {
+    hipLaunchKernelGGL(tanh_coef_kernel, dim3((unsigned)((2 * P + 255) / 256)), dim3(256), 0, s, all, Bh_all, P, w_tanh,
+                       coeff, tcoef_ws);
+    PIPNET_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(pool_grad_kernel<true>, grid, dim3(256), 0, s, rows, Bh, P, d_out, W, K, w_tanh, coeff, extra,
+                     dpool, tcoef_ws);
+  PIPNET_CHECK_LAUNCH();
+  return PIPNET_OK;
+}
+
+// pooled_all == NULL: pipnet_head_bwd_f32 (Bh_all = Bh); else its row-sharded form
+static int head_bwd_launch(const float* proto, const float* pooled, int Bh, int HW, int P, const float* d_out,
+                           const float* W, int K, const float* pooled_all, int Bh_all, float w_align, float w_tanh,
+                           float tanh_coeff, int32_t* argmax_ws, float* dpool_ws, float* tcoef_ws, float* d_logits,
+                           void* stream) {
   if (Bh <= 0 || HW <= 0 || P <= 0 || (P & 3) || !proto || !pooled || !argmax_ws || !dpool_ws || !d_logits)
     return PIPNET_ERR_ARG;
   if (d_out && (!W || K <= 0)) return PIPNET_ERR_ARG;
   if (P > 2048) return PIPNET_ERR_ARG;       // widest head_bwd_kernel (PIPNET_BY_NJ4): refuse before any launch
+  if (pooled_all && (Bh_all < Bh || !tcoef_ws)) return PIPNET_ERR_ARG;
   if (!aligned16(proto) || !aligned16(d_logits)) return PIPNET_ERR_ALIGN;
   hipStream_t s = (hipStream_t)stream;
   const int64_t NP = (int64_t)2 * Bh * P;
   hipLaunchKernelGGL(argmax_hw_kernel, dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, s, proto, 2 * Bh, HW, P,
                      argmax_ws);
   PIPNET_CHECK_LAUNCH();
-  hipLaunchKernelGGL(pool_grad_kernel, dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, s, pooled, Bh, P, d_out, W,
-                     K, w_tanh, tanh_coeff, nullptr, dpool_ws);
-  PIPNET_CHECK_LAUNCH();
-  const float a = 0.5f * w_align / (float)((int64_t)Bh * HW);
+  const int st = pool_grad_launch(pooled, Bh, P, d_out, W, K, w_tanh, tanh_coeff, nullptr, dpool_ws, pooled_all,
+                                  Bh_all, tcoef_ws, s);
+  if (st != PIPNET_OK) return st;
+  const float a = 0.5f * w_align / (float)((int64_t)Bh_all * HW);
 #define PIPNET_HB(NJ)                                                                                            \
   hipLaunchKernelGGL(head_bwd_kernel<NJ>, dim3(TB_G * 2), dim3(TB_T), 0, s, proto, Bh, HW, P, argmax_ws, dpool_ws, \
                      a, d_logits);
@@ -746,6 +798,22 @@ extern "C" int pipnet_head_bwd_f32(const float* proto, const float* pooled, int 
 #undef PIPNET_HB
   PIPNET_CHECK_LAUNCH();
   return PIPNET_OK;
+}
+
+extern "C" int pipnet_head_bwd_f32(const float* proto, const float* pooled, int Bh, int HW, int P, const float* d_out,
+                                   const float* W, int K, float w_align, float w_tanh, float tanh_coeff,
+                                   int32_t* argmax_ws, float* dpool_ws, float* d_logits, void* stream) {
+  return head_bwd_launch(proto, pooled, Bh, HW, P, d_out, W, K, nullptr, Bh, w_align, w_tanh, tanh_coeff, argmax_ws,
+                         dpool_ws, nullptr, d_logits, stream);
+}
+
+extern "C" int pipnet_head_bwd_rows_f32(const float* proto, const float* pooled, int Bh, int HW, int P,
+                                        const float* d_out, const float* W, int K, const float* pooled_all, int Bh_all,
+                                        float w_align, float w_tanh, float tanh_coeff, int32_t* argmax_ws,
+                                        float* dpool_ws, float* tcoef_ws, float* d_logits, void* stream) {
+  if (!pooled_all) return PIPNET_ERR_ARG;
+  return head_bwd_launch(proto, pooled, Bh, HW, P, d_out, W, K, pooled_all, Bh_all, w_align, w_tanh, tanh_coeff,
+                         argmax_ws, dpool_ws, tcoef_ws, d_logits, stream);
 }
 
 // ---- CountPIPNet head / count backward (pretrain and joint phases) -------------------------
@@ -861,18 +929,20 @@ extern "C" int pipnet_onehot_ste_bwd_f32(const float* x, int64_t rows, int M, co
 // (tau = 1, g = 0 for the plain Softmax add-on).  d counts = d_counts_in (the classifier /
 // intermediate / STE chain, may be NULL) + the tanh term on C * counts; the align term as the
 // PIP-Net head.  proto NHWC [2Bh][HW][P], counts [2Bh][P], dcnt_ws float [2Bh*P].
-extern "C" int pipnet_count_head_bwd_f32(const float* proto, const float* counts, int Bh, int HW, int P,
-                                         const float* d_counts_in, float w_align, float w_tanh, float tanh_coeff,
-                                         float inv_tau, float* dcnt_ws, float* d_logits, void* stream) {
+// counts_all == NULL: pipnet_count_head_bwd_f32 (Bh_all = Bh); else its row-sharded form
+static int count_head_bwd_launch(const float* proto, const float* counts, int Bh, int HW, int P,
+                                 const float* d_counts_in, const float* counts_all, int Bh_all, float w_align,
+                                 float w_tanh, float tanh_coeff, float inv_tau, float* dcnt_ws, float* tcoef_ws,
+                                 float* d_logits, void* stream) {
   if (Bh <= 0 || HW <= 0 || P <= 0 || (P & 3) || !proto || !counts || !dcnt_ws || !d_logits) return PIPNET_ERR_ARG;
   if (P > 2048) return PIPNET_ERR_ARG;       // as pipnet_head_bwd_f32: before pool_grad_kernel is enqueued
+  if (counts_all && (Bh_all < Bh || !tcoef_ws)) return PIPNET_ERR_ARG;
   if (!aligned16(proto) || !aligned16(d_logits)) return PIPNET_ERR_ALIGN;
   hipStream_t s = (hipStream_t)stream;
-  const int64_t NP = (int64_t)2 * Bh * P;
-  hipLaunchKernelGGL(pool_grad_kernel, dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, s, counts, Bh, P, nullptr,
-                     nullptr, 0, w_tanh, tanh_coeff, d_counts_in, dcnt_ws);
-  PIPNET_CHECK_LAUNCH();
-  const float a = 0.5f * w_align / (float)((int64_t)Bh * HW);
+  const int st = pool_grad_launch(counts, Bh, P, nullptr, nullptr, 0, w_tanh, tanh_coeff, d_counts_in, dcnt_ws,
+                                  counts_all, Bh_all, tcoef_ws, s);
+  if (st != PIPNET_OK) return st;
+  const float a = 0.5f * w_align / (float)((int64_t)Bh_all * HW);
 #define PIPNET_CHB(NJ)                                                                                           \
   hipLaunchKernelGGL((head_bwd_kernel<NJ, true>), dim3(TB_G * 2), dim3(TB_T), 0, s, proto, Bh, HW, P, nullptr,  \
                      dcnt_ws, a, d_logits, inv_tau);
@@ -880,4 +950,20 @@ extern "C" int pipnet_count_head_bwd_f32(const float* proto, const float* counts
 #undef PIPNET_CHB
   PIPNET_CHECK_LAUNCH();
   return PIPNET_OK;
+}
+
+extern "C" int pipnet_count_head_bwd_f32(const float* proto, const float* counts, int Bh, int HW, int P,
+                                         const float* d_counts_in, float w_align, float w_tanh, float tanh_coeff,
+                                         float inv_tau, float* dcnt_ws, float* d_logits, void* stream) {
+  return count_head_bwd_launch(proto, counts, Bh, HW, P, d_counts_in, nullptr, Bh, w_align, w_tanh, tanh_coeff, inv_tau,
+                               dcnt_ws, nullptr, d_logits, stream);
+}
+
+extern "C" int pipnet_count_head_bwd_rows_f32(const float* proto, const float* counts, int Bh, int HW, int P,
+                                              const float* d_counts_in, const float* counts_all, int Bh_all,
+                                              float w_align, float w_tanh, float tanh_coeff, float inv_tau,
+                                              float* dcnt_ws, float* tcoef_ws, float* d_logits, void* stream) {
+  if (!counts_all) return PIPNET_ERR_ARG;
+  return count_head_bwd_launch(proto, counts, Bh, HW, P, d_counts_in, counts_all, Bh_all, w_align, w_tanh, tanh_coeff,
+                               inv_tau, dcnt_ws, tcoef_ws, d_logits, stream);
 }

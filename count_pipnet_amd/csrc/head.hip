@@ -302,8 +302,9 @@ __global__ __launch_bounds__(HEAD_THREADS) void nonneg_linear_kernel(const float
 //
 // SOFT (train mode, F.gumbel_softmax(hard=False), count_pipnet_utils.py:34-35): proto =
 // softmax((x - log E) / tau) written for every channel, and the per-prototype spatial sums
-// (the raw counts, count_pipnet.py:88) reduced per workgroup in LDS, one float atomic per
-// (workgroup, channel) into `sums`.
+// (the raw counts, count_pipnet.py:88) reduced per workgroup in LDS and stored as row
+// (b * gridDim.x + blockIdx.x) of `sums` [B * workgroups per image, P]; count_partials_sum_kernel
+// adds an image's rows in workgroup order (float atomics here gave other bits from run to run).
 constexpr int CG_PIX_PER_BLOCK = 16;        // 4 pixels per wave: C5 (64 x 256 px) -> 1024 workgroups
 
 template <int NJ, bool SOFT = false, bool NOISE = false>   // NOISE: injected Exp(1) draw, else Philox
@@ -452,8 +453,22 @@ __global__ __launch_bounds__(HEAD_THREADS) void count_gumbel_kernel(const float*
       float r = red[0][c];
 #pragma unroll
       for (int w = 1; w < HEAD_THREADS / 64; ++w) r += red[w][c];
-      atomicAdd(sums + (int64_t)b * P + c, r);
+      sums[((int64_t)b * gridDim.x + blockIdx.x) * P + c] = r;   // this workgroup's slot: no atomic, no order
     }
+  }
+}
+
+// sums[b][c] = ((0 + part[b][0][c]) + part[b][1][c]) + ...: the workgroups' partial sums of an image added in
+// workgroup order -- what float atomics into a zeroed row give when they arrive in that order, and the same
+// bits in every run.
+__global__ void count_partials_sum_kernel(const float* __restrict__ part, int nblk, int P, int64_t n,
+                                          float* __restrict__ sums) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = i / P;
+    const int c = (int)(i - b * P);
+    float t = 0.f;
+    for (int k = 0; k < nblk; ++k) t += part[(b * nblk + k) * P + c];
+    sums[i] = t;
   }
 }
 
@@ -653,7 +668,10 @@ extern "C" int pipnet_count_gumbel_devseed_f32(const float* logits, int B, int H
 }
 
 // Train-mode (soft) Gumbel head: proto = softmax((x - log E) / tau) [B,HW,P], sums [B,P] = spatial
-// sums (the raw counts; zeroed here).  exp_noise as pipnet_count_gumbel_f32 (NCHW) or NULL (Philox).
+// sums (the raw counts).  exp_noise as pipnet_count_gumbel_f32 (NCHW) or NULL (Philox).  The sums are the
+// same bits in every run: with more than one workgroup per image (HW > 16) the workgroups' partial sums go
+// to a stream-ordered scratch (hipMallocAsync / hipFreeAsync on `stream`: no host wait, nothing shared
+// between streams) and are added in workgroup order.
 extern "C" int pipnet_count_gumbel_soft_f32(const float* logits, int B, int HW, int P, float tau,
                                             const float* exp_noise, uint64_t seed, uint64_t offset, float* proto,
                                             float* sums, void* stream) {
@@ -663,20 +681,38 @@ extern "C" int pipnet_count_gumbel_soft_f32(const float* logits, int B, int HW, 
   const int nj = nj_bucket(P);
   if (nj < 0) return PIPNET_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  if (!zero_fill(reinterpret_cast<uint32_t*>(sums), (int64_t)B * P, s)) return PIPNET_ERR_LAUNCH;
   const dim3 grid((HW + CG_PIX_PER_BLOCK - 1) / CG_PIX_PER_BLOCK, B);
+  const int64_t n = (int64_t)B * P;
+  float* part = sums;                        // one workgroup per image: its partial sum is the sum
+  if (grid.x > 1) {
+    void* ws = nullptr;
+    if (hipMallocAsync(&ws, (size_t)n * grid.x * sizeof(float), s) != hipSuccess || !ws) {
+      (void)hipGetLastError();
+      return PIPNET_ERR_LAUNCH;
+    }
+    part = static_cast<float*>(ws);
+  }
   const float inv_tau = 1.0f / tau;
 #define CG_CALL(N)                                                                                                \
   if (exp_noise)                                                                                                  \
     hipLaunchKernelGGL((count_gumbel_kernel<N, true, true>), grid, dim3(HEAD_THREADS), 0, s, logits, HW, P, inv_tau, \
-                       exp_noise, seed, offset, nullptr, proto, nullptr, sums);                                    \
+                       exp_noise, seed, offset, nullptr, proto, nullptr, part);                                    \
   else                                                                                                            \
     hipLaunchKernelGGL((count_gumbel_kernel<N, true, false>), grid, dim3(HEAD_THREADS), 0, s, logits, HW, P, inv_tau, \
-                       exp_noise, seed, offset, nullptr, proto, nullptr, sums);
+                       exp_noise, seed, offset, nullptr, proto, nullptr, part);
   PIPNET_NJ_SWITCH(nj, CG_CALL)
 #undef CG_CALL
-  PIPNET_CHECK_LAUNCH();
-  return PIPNET_OK;
+  hipError_t err = hipGetLastError();
+  if (part != sums) {
+    if (err == hipSuccess) {
+      const int64_t blocks = (n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048;
+      hipLaunchKernelGGL(count_partials_sum_kernel, dim3((unsigned)blocks), dim3(256), 0, s, part, (int)grid.x, P, n,
+                         sums);
+      err = hipGetLastError();
+    }
+    if (hipFreeAsync(part, s) != hipSuccess && err == hipSuccess) err = hipGetLastError();
+  }
+  return err == hipSuccess ? PIPNET_OK : PIPNET_ERR_LAUNCH;
 }
 
 extern "C" int pipnet_count_finish_f32(const int32_t* hist, const float* sums, int B, int P, int max_count,

@@ -1180,9 +1180,11 @@ def linear_intermediate_backward(x: Tensor, g: Tensor, w: Tensor, want_dx: bool 
 
 
 def count_head_backward(proto_nhwc: Tensor, counts: Tensor, d_counts: Optional[Tensor], w_align: float,
-                        w_tanh: float, tanh_coeff: float, tau: float) -> Tensor:
+                        w_tanh: float, tanh_coeff: float, tau: float, counts_all: Optional[Tensor] = None) -> Tensor:
     """d loss / d logits of the CountPIPNet head (soft Gumbel-softmax / softmax, spatial sum)
-    for the align / tanh terms of calculate_loss plus the classifier chain's d counts."""
+    for the align / tanh terms of calculate_loss plus the classifier chain's d counts.  ``counts_all``
+    [2 Bh_all, P]: the operands are one rank's rows of a batch whose raw counts these are
+    (pipnet_count_head_bwd_rows_f32)."""
     _chk_rows("count_head_backward", proto_nhwc, "proto features", 4)
     n, h, ww, p = proto_nhwc.shape
     if n % 2:
@@ -1191,6 +1193,13 @@ def count_head_backward(proto_nhwc: Tensor, counts: Tensor, d_counts: Optional[T
     _operand("count_head_backward", "d counts", d_counts, shape=(n, p), device=proto_nhwc.device, optional=True)
     d_logits = torch.empty_like(proto_nhwc)
     dcnt = torch.empty((n, p), device=proto_nhwc.device, dtype=torch.float32)
+    if counts_all is not None:
+        bh_all = _chk_all_rows("count_head_backward", counts, counts_all)
+        tcoef = torch.empty((2, p), device=proto_nhwc.device, dtype=torch.float32)
+        _lib.call("pipnet_count_head_bwd_rows_f32", proto_nhwc.data_ptr(), counts.data_ptr(), n // 2, h * ww, p,
+                  _ptr(d_counts), counts_all.data_ptr(), bh_all, float(w_align), float(w_tanh), float(tanh_coeff),
+                  1.0 / float(tau), dcnt.data_ptr(), tcoef.data_ptr(), d_logits.data_ptr(), _stream(proto_nhwc))
+        return d_logits
     _lib.call("pipnet_count_head_bwd_f32", proto_nhwc.data_ptr(), counts.data_ptr(), n // 2, h * ww, p,
               _ptr(d_counts), float(w_align), float(w_tanh), float(tanh_coeff), 1.0 / float(tau), dcnt.data_ptr(),
               d_logits.data_ptr(), _stream(proto_nhwc))
@@ -1420,19 +1429,47 @@ def train_loss(proto_nhwc: Tensor, pooled: Tensor, out: Tensor, ys: Tensor, mult
     if n % 2 or out.dim() != 2 or out.shape[0] != n:
         raise RuntimeError(f"train_loss: proto {tuple(proto_nhwc.shape)} and out {tuple(out.shape)} must share an "
                            f"even batch = cat([xs1, xs2])")
-    bh, k = n // 2, out.shape[1]
+    _operand("train_loss", "pooled", pooled, shape=(n, p), device=out.device)
+    return train_loss_from_partial(train_align_partial(proto_nhwc), h * w, pooled, out, ys, mult, enforce, tanh_coeff,
+                                   w_align, w_tanh, w_class, mode)
+
+
+def train_align_partial(proto_nhwc: Tensor) -> Tensor:
+    """The align term's fp64 partial sums over this map's pixel pairs (rows [view 1 | view 2]): one double per
+    workgroup of a fixed grid.  train_loss_from_partial sums them and divides by the pair count it is given, so
+    the partials of row shards add up elementwise to a batch's (count_pipnet_amd.dist_train)."""
+    _chk_rows("train_align_partial", proto_nhwc, "proto features (NHWC)", 4)
+    n, h, w, p = proto_nhwc.shape
+    if n % 2 or n == 0:
+        raise RuntimeError(f"train_align_partial: the batch holds both views, so it must be even and non-empty "
+                           f"(got {n})")
+    partial = torch.empty(_lib.load().pipnet_train_align_partials(), device=proto_nhwc.device, dtype=torch.float64)
+    _lib.call("pipnet_train_align_partial_f32", proto_nhwc.data_ptr(), n // 2, h * w, p, partial.data_ptr(),
+              _stream(proto_nhwc))
+    return partial
+
+
+def train_loss_from_partial(partial: Tensor, hw: int, pooled: Tensor, out: Tensor, ys: Tensor, mult: Optional[Tensor],
+                            enforce: bool, tanh_coeff: float, w_align: float, w_tanh: float, w_class: float,
+                            mode: str) -> Tuple[Tensor, Optional[Tensor]]:
+    """train_loss after the align partial sums: pooled [N,P], out [N,K], ys [N/2] and ``hw`` pixels per map."""
+    _operand("train_loss", "classifier output", out)
+    if out.dim() != 2 or out.shape[0] % 2 or out.shape[0] == 0 or pooled.dim() != 2:
+        raise RuntimeError(f"train_loss: out {tuple(out.shape)} must be [even N, K] and pooled {tuple(pooled.shape)} "
+                           f"[N, P]")
+    (n, k), p = out.shape, pooled.shape[1]
+    bh = n // 2
     _operand("train_loss", "pooled", pooled, shape=(n, p), device=out.device)
     _operand("train_loss", "labels", ys, dtype=torch.int64, shape=(bh,), device=out.device)
     _operand("train_loss", "normalization_multiplier", mult, shape=1, device=out.device, optional=True)
-    partial = torch.empty(_lib.load().pipnet_train_align_partials(), device=out.device, dtype=torch.float64)
-    s = _stream(out)
-    _lib.call("pipnet_train_align_partial_f32", proto_nhwc.data_ptr(), bh, h * w, p, partial.data_ptr(), s)
+    _operand("train_loss", "align partial sums", partial, dtype=torch.float64,
+             shape=_lib.load().pipnet_train_align_partials(), device=out.device)
     stats = torch.empty(8, device=out.device, dtype=torch.float32)
     m = TRAIN_MODE[mode]
     d_out = None if m == 1 else torch.empty_like(out)
-    _lib.call("pipnet_train_loss_f32", partial.data_ptr(), bh, h * w, pooled.data_ptr(), out.data_ptr(),
+    _lib.call("pipnet_train_loss_f32", partial.data_ptr(), bh, hw, pooled.data_ptr(), out.data_ptr(),
               ys.data_ptr(), p, k, _ptr(mult), int(bool(enforce)), float(tanh_coeff), float(w_align),
-              float(w_tanh), float(w_class), m, _ptr(d_out), stats.data_ptr(), s)
+              float(w_tanh), float(w_class), m, _ptr(d_out), stats.data_ptr(), _stream(out))
     return stats, d_out
 
 
@@ -1620,10 +1657,22 @@ def wgrad_conv2x2(dy_nhwc: Tensor, x_nhwc: Tensor, stride: int, out: Tensor, acc
     return out
 
 
+def _chk_all_rows(fn: str, rows: Tensor, all_rows: Tensor) -> int:
+    """The gathered rows of every rank beside one rank's ``rows`` [2 Bh, P]: [2 Bh_all, P] -> Bh_all."""
+    _operand(fn, "gathered rows of every rank", all_rows, device=rows.device)
+    if all_rows.dim() != 2 or all_rows.shape[1] != rows.shape[1] or all_rows.shape[0] % 2 or \
+            all_rows.shape[0] < rows.shape[0]:
+        raise RuntimeError(f"{fn}: the gathered rows must be [2 Bh_all, {rows.shape[1]}] with Bh_all >= "
+                           f"{rows.shape[0] // 2} (got {tuple(all_rows.shape)})")
+    return all_rows.shape[0] // 2
+
+
 def head_backward(proto_nhwc: Tensor, pooled: Tensor, d_out: Optional[Tensor], w: Optional[Tensor],
-                  w_align: float, w_tanh: float, tanh_coeff: float = 1.0) -> Tensor:
+                  w_align: float, w_tanh: float, tanh_coeff: float = 1.0,
+                  pooled_all: Optional[Tensor] = None) -> Tensor:
     """d loss / d logits of the PIP-Net head (softmax + max-pool) for the align / tanh /
-    classifier terms of calculate_loss (pipnet/train.py:154-265)."""
+    classifier terms of calculate_loss (pipnet/train.py:154-265).  ``pooled_all`` [2 Bh_all, P]: the
+    operands are one rank's rows of a batch whose pooled rows these are (pipnet_head_bwd_rows_f32)."""
     _chk_rows("head_backward", proto_nhwc, "proto features", 4)
     n, h, ww, p = proto_nhwc.shape
     if n % 2 or n == 0:
@@ -1640,10 +1689,28 @@ def head_backward(proto_nhwc: Tensor, pooled: Tensor, d_out: Optional[Tensor], w
     amax = torch.empty((n, p), device=proto_nhwc.device, dtype=torch.int32)
     dpool = torch.empty((n, p), device=proto_nhwc.device, dtype=torch.float32)
     k = 0 if w is None else w.shape[0]
+    if pooled_all is not None:
+        bh_all = _chk_all_rows("head_backward", pooled.view(n, p), pooled_all)
+        tcoef = torch.empty((2, p), device=proto_nhwc.device, dtype=torch.float32)
+        _lib.call("pipnet_head_bwd_rows_f32", proto_nhwc.data_ptr(), pooled.data_ptr(), n // 2, h * ww, p, _ptr(d_out),
+                  _ptr(w), k, pooled_all.data_ptr(), bh_all, w_align, w_tanh, tanh_coeff, amax.data_ptr(),
+                  dpool.data_ptr(), tcoef.data_ptr(), d_logits.data_ptr(), _stream(proto_nhwc))
+        return d_logits
     _lib.call("pipnet_head_bwd_f32", proto_nhwc.data_ptr(), pooled.data_ptr(), n // 2, h * ww, p, _ptr(d_out), _ptr(w),
               k, w_align, w_tanh, tanh_coeff, amax.data_ptr(), dpool.data_ptr(), d_logits.data_ptr(),
               _stream(proto_nhwc))
     return d_logits
+
+
+def pack_tensors(table: Tensor, arena: Tensor) -> None:
+    """One launch gathers fp32 tensors into ``arena`` (pipnet_pack_tensors_f32).  ``table``: device int64 [n, 3]
+    = source address, arena offset in floats (a multiple of 4), element count; the slot padding is zeroed.  The
+    rows are the caller's to get right (count_pipnet_amd.dist_train.GradArena builds them from live tensors)."""
+    _operand("pack_tensors", "arena", arena)
+    _operand("pack_tensors", "table", table, dtype=torch.int64, device=arena.device)
+    if table.dim() != 2 or table.shape[1] != 3:
+        raise RuntimeError(f"pack_tensors: the table must be [n, 3] (got {tuple(table.shape)})")
+    _lib.call("pipnet_pack_tensors_f32", table.data_ptr(), table.shape[0], arena.data_ptr(), _stream(arena))
 
 
 # ---- ResNet training: BatchNorm2d in train mode (csrc/bn_ops.hip) ----------------------------

@@ -165,9 +165,13 @@ def _pipnet_head(m: nn.Module, feats: Tensor) -> _Head:
 
 
 def _pipnet_head_backward(m: nn.Module, hd: _Head, d_out: Optional[Tensor], w_align: float, w_tanh: float,
-                          tanh_loss_coeff: float, to_logits: bool) -> Optional[Tensor]:
-    """d loss / d add-on logits (``to_logits``); a PIP-Net head has no parameter of its own."""
-    return K.head_backward(hd.proto, hd.pooled, d_out, m._classification.weight, w_align, w_tanh) if to_logits else None
+                          tanh_loss_coeff: float, to_logits: bool,
+                          pooled_all: Optional[Tensor] = None) -> Optional[Tensor]:
+    """d loss / d add-on logits (``to_logits``); a PIP-Net head has no parameter of its own.  ``pooled_all``: ``hd``
+    and ``d_out`` are one rank's rows of a batch with these pooled rows (dist_train)."""
+    if not to_logits:
+        return None
+    return K.head_backward(hd.proto, hd.pooled, d_out, m._classification.weight, w_align, w_tanh, pooled_all=pooled_all)
 
 
 def train_forward_hip(net: nn.Module, xs: Tensor, sd_keep: Optional[Dict[int, Tensor]],
@@ -246,10 +250,12 @@ def _count_tail(m: nn.Module, clamped: Tensor):
     return saved, inter, out
 
 
-def _count_head(m: nn.Module, feats: Tensor) -> _Head:
+def _count_head(m: nn.Module, feats: Tensor, gumbel=None) -> _Head:
     """CountPIPNet.forward in train mode after the backbone: soft Gumbel-softmax / softmax map,
     spatial sums = raw counts, STE round and clamp, intermediate layer, classifier.  ``saved``
-    keeps the head's temperature (``tau``) and the clamped counts with the tail's activations."""
+    keeps the head's temperature (``tau``) and the clamped counts with the tail's activations.
+    ``gumbel(logits, act) -> (proto, sums)`` draws the Gumbel head's noise in place of the two forms
+    below (dist_train: a rank's rows take the draw of their place in the global batch)."""
     from .count_pipnet_utils import GumbelSoftmax
     from .count_pipnet import _fresh_seed
     from .pipnet import add_on_activation, add_on_logits_hip
@@ -257,7 +263,9 @@ def _count_head(m: nn.Module, feats: Tensor) -> _Head:
     if isinstance(act, GumbelSoftmax):
         logits = add_on_logits_hip(m._add_on, feats, activation=GumbelSoftmax)
         noise = act.exp_noise
-        if noise is not None:
+        if gumbel is not None:
+            proto, sums = gumbel(logits, act)
+        elif noise is not None:
             proto, sums = K.count_gumbel_soft(logits, act.tau, noise.to(device=logits.device,
                                                                         dtype=torch.float32).contiguous(), 0)
         else:
@@ -331,7 +339,8 @@ def _intermediate_backward(layer: nn.Module, x: Tensor, saved: dict, d_inter: Te
 
 
 def _count_head_backward(m: nn.Module, hd: _Head, d_out: Optional[Tensor], w_align: float, w_tanh: float,
-                         tanh_loss_coeff: float, to_logits: bool) -> Optional[Tensor]:
+                         tanh_loss_coeff: float, to_logits: bool,
+                         pooled_all: Optional[Tensor] = None) -> Optional[Tensor]:
     """Backward below the classifier: intermediate layer (parameter gradients; ModifiedSTE for a
     one-hot encoder) and, with ``to_logits``, on through ClampSTE / STE_Round -> d counts (+ the
     tanh term) -> d proto (+ the align term) -> soft-max backward scaled by 1 / tau.  Without it
@@ -346,7 +355,8 @@ def _count_head_backward(m: nn.Module, hd: _Head, d_out: Optional[Tensor], w_ali
                                             not m._is_clamp_backward_identity or not m._use_ste)
     if not to_logits:
         return None
-    return K.count_head_backward(hd.proto, hd.pooled, d_counts, w_align, w_tanh, tanh_loss_coeff, hd.saved["tau"])
+    return K.count_head_backward(hd.proto, hd.pooled, d_counts, w_align, w_tanh, tanh_loss_coeff, hd.saved["tau"],
+                                 counts_all=pooled_all)
 
 
 # ------------------------------------------------------------------------------------------
@@ -636,6 +646,20 @@ def _step_optimizers(m: nn.Module, optimizer_classifier, optimizer_net, enforce_
         K.clamp_min_(cls.normalization_multiplier.detach(), 1.0)
 
 
+def _classifier_grads(cls: nn.Module, hd: _Head, d_out: Optional[Tensor], finetune: bool) -> None:
+    """.grad of the classifier's weight and bias from d loss / d out (None in pretrain: no class term)."""
+    has_bias = cls.bias is not None
+    if d_out is not None and (finetune or cls.weight.requires_grad or (has_bias and cls.bias.requires_grad)):
+        # db is only ever kept under requires_grad (_set_grad), so asking for it is a matter of cost alone:
+        # the finetune steps have always skipped a frozen bias's column sum, the other phases compute it
+        # whenever there is a bias; each phase goes on launching what it did
+        want_bias = has_bias and (cls.bias.requires_grad or not finetune)
+        dw, db = K.nonneg_linear_backward(d_out, hd.cls_in, cls.weight, want_bias)
+        _set_grad(cls.weight, dw)
+        if want_bias:
+            _set_grad(cls.bias, db)
+
+
 def _train_step(m: nn.Module, xs1: Tensor, xs2: Tensor, ys: Tensor, *, phase: str, optimizer_classifier,
                 optimizer_net=None, w: Tuple[float, float, float], enforce_weight_sparsity: bool,
                 tanh_loss_coeff: float = 1.0, sd_keep: Optional[Dict[int, Tensor]], generator, step_optimizers=True):
@@ -659,16 +683,7 @@ def _train_step(m: nn.Module, xs1: Tensor, xs2: Tensor, ys: Tensor, *, phase: st
         hd = head(m, feats)
         stats, d_out = K.train_loss(hd.proto, hd.pooled, hd.out, ys, cls.normalization_multiplier,
                                     enforce_weight_sparsity, tanh_loss_coeff, w_align, w_tanh, w_class, phase)
-        has_bias = cls.bias is not None
-        if d_out is not None and (finetune or cls.weight.requires_grad or (has_bias and cls.bias.requires_grad)):
-            # db is only ever kept under requires_grad (_set_grad), so asking for it is a matter of cost alone:
-            # the finetune steps have always skipped a frozen bias's column sum, the other phases compute it
-            # whenever there is a bias; each phase goes on launching what it did
-            want_bias = has_bias and (cls.bias.requires_grad or not finetune)
-            dw, db = K.nonneg_linear_backward(d_out, hd.cls_in, cls.weight, want_bias)
-            _set_grad(cls.weight, dw)
-            if want_bias:
-                _set_grad(cls.bias, db)
+        _classifier_grads(cls, hd, d_out, finetune)
         d_logits = head_backward(m, hd, d_out, w_align, w_tanh, tanh_loss_coeff, to_logits=not finetune)
         del hd
         if not finetune:

@@ -151,7 +151,10 @@ int pipnet_conv2d_nhwc_bf16_tile(const void* x, int B, int H, int W, int Cin, co
  * intermediate layer train) ------------------------------------------------------------
  * Train-mode (soft) Gumbel head, F.gumbel_softmax(hard=False) (count_pipnet_utils.py:34-35):
  * proto = softmax((x - log E) / tau) [B,HW,P] NHWC, sums [B,P] = spatial sums = the raw
- * counts (count_pipnet.py:88).  exp_noise / seed / offset as pipnet_count_gumbel_f32. */
+ * counts (count_pipnet.py:88), added in a fixed order: the same bits in every run.  With
+ * HW > 16 the call takes a scratch of B * ceil(HW / 16) * P floats from the device's
+ * stream-ordered pool on `stream` and returns it there.  exp_noise / seed / offset as
+ * pipnet_count_gumbel_f32. */
 int pipnet_count_gumbel_soft_f32(const float* logits, int B, int HW, int P, float tau, const float* exp_noise,
                                  uint64_t seed, uint64_t offset, float* proto, float* sums, void* stream);
 
@@ -625,6 +628,31 @@ int pipnet_onehot_ste_bwd_f32(const float* x, int64_t rows, int M, const float* 
 int pipnet_count_head_bwd_f32(const float* proto, const float* counts, int Bh, int HW, int P, const float* d_counts_in,
                               float w_align, float w_tanh, float tanh_coeff, float inv_tau, float* dcnt_ws,
                               float* d_logits, void* stream);
+
+/* ---- data-parallel training (count_pipnet_amd/dist_train.py; csrc/backward_ops.hip, dist_train_ops.hip) ----
+ * One process per GPU; a rank holds Bh of the global batch's Bh_all rows per view (both views of its rows).
+ * pipnet_head_bwd_rows_f32 / pipnet_count_head_bwd_rows_f32: pipnet_head_bwd_f32 / pipnet_count_head_bwd_f32 for
+ *   a shard of rows.  proto, pooled / counts, d_out / d_counts_in and d_logits cover the rank's 2 Bh rows
+ *   ([view 1 | view 2]); the tanh term's column sums run over pooled_all / counts_all [2 Bh_all][P], the gathered
+ *   rows of every rank in global order ([view 1 of all ranks | view 2 of all ranks]), each half's rows in
+ *   ascending order; the align factor is 0.5 w_align / (Bh_all HW).  tcoef_ws float [2 P]: the tanh term per
+ *   (half, prototype), computed once by a small kernel ahead of the d pooled kernel.  The device code is the
+ *   full-batch entry points' own: a shard's d_logits equals the same rows of the full-batch call bit for bit,
+ *   and with pooled_all == pooled, Bh_all == Bh the whole output does.
+ * pipnet_pack_tensors_f32: one launch gathers n fp32 tensors into a flat arena (the gradients, ahead of the one
+ *   all-reduce).  table: device int64 [n][3] = source address, arena offset in floats (a multiple of 4: slots
+ *   start on 16 bytes), element count; a slot is the count rounded up to a multiple of 4 and its padding is
+ *   written as 0; nothing outside the slots is written.  arena 16-byte aligned, n <= 65535; 16-byte loads and
+ *   stores where the source is 16-byte aligned, element by element otherwise. */
+int pipnet_head_bwd_rows_f32(const float* proto, const float* pooled, int Bh, int HW, int P, const float* d_out,
+                             const float* W, int K, const float* pooled_all, int Bh_all, float w_align, float w_tanh,
+                             float tanh_coeff, int32_t* argmax_ws, float* dpool_ws, float* tcoef_ws, float* d_logits,
+                             void* stream);
+int pipnet_count_head_bwd_rows_f32(const float* proto, const float* counts, int Bh, int HW, int P,
+                                   const float* d_counts_in, const float* counts_all, int Bh_all, float w_align,
+                                   float w_tanh, float tanh_coeff, float inv_tau, float* dcnt_ws, float* tcoef_ws,
+                                   float* d_logits, void* stream);
+int pipnet_pack_tensors_f32(const int64_t* table, int n, float* arena, void* stream);
 
 /* fp64-accumulated product for inference-time weight folds (csrc/fold_f64.hip):
  *   C[M,N] (ldc) = RNE_f32( sum_k double(A[m,k]) * double(B[k,n]) ), A [M,K] (lda) and B [K,N]
