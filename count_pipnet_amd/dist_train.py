@@ -27,7 +27,10 @@ Randomness comes from one host ``torch.Generator`` that is the same on every ran
 masks (each rank keeps its rows of each view) and, for a CountPIPNet, the step's Philox seed -- global row g of
 the ``cat([xs1, xs2])`` stream gets the draw ``kernels.count_gumbel_soft(logits, tau, None, seed)`` gives row g.
 
-World 1 (no group, or a group of one) is ``train._train_step`` itself: no arena, no collective.
+Every world runs the one ``train._train_step``: it is handed a ``Shard`` and asks it in the five places where a
+rank's rows are not the whole batch -- the masks' rows, the Gumbel draw, the loss on the gathered rows, the gathered
+pooled rows of the head backward, the gradient all-reduce.  World 1 (no group, or a group of one) hands it none: the
+single-device step itself, no arena, no collective.
 A ResNet backbone at world > 1 is refused: see ``_RESNET_REFUSAL``.
 """
 from __future__ import annotations
@@ -166,8 +169,8 @@ class ShardedTraining(nn.Module):
         super().__init__()
         self.module = T._inner(net)
         self.process_group = process_group
-        # measurement only (tools/bench_dist_train.py): world 1 takes the sharded path too -- packed rows, rows
-        # kernels, loss on the "gathered" arrays, arena pack -- with the collectives themselves left out
+        # world 1 gets a Shard too, of one shard that is the whole batch -- packed rows, rows kernels, loss on the
+        # "gathered" arrays, arena pack, no collective: how one GPU measures and tests the step of world > 1
         self.force_exchange = force_exchange
         self.world, self.rank = _group_size_rank(process_group)
         if seed is None:
@@ -225,68 +228,11 @@ class ShardedTraining(nn.Module):
             raise ValueError(f"dist_train: xs1 {tuple(xs1.shape)}, xs2 {tuple(xs2.shape)} and ys {tuple(ys.shape)} "
                              f"must hold the same rows")
         sizes = self.check(phase, xs1.shape[0], sizes)
-        w = T._loss_weights(phase == "pretrain", epoch, nr_epochs)
-        if self.world == 1 and not self.force_exchange:
-            return T._train_step(self.module, xs1, xs2, ys, phase=phase, optimizer_classifier=optimizer_classifier,
-                                 optimizer_net=optimizer_net, w=w, enforce_weight_sparsity=enforce_weight_sparsity,
-                                 tanh_loss_coeff=tanh_loss_coeff, sd_keep=sd_keep, generator=self.generator,
-                                 step_optimizers=step_optimizers)
-        return self._sharded_step(xs1, xs2, ys, optimizer_net, optimizer_classifier, phase, w,
-                                  enforce_weight_sparsity, tanh_loss_coeff, sizes, sd_keep, step_optimizers)
-
-    def _gumbel(self, seed: int, start: int, rows: int, batch: int):
-        """The Gumbel head of this rank's rows ``[view 1 | view 2]`` on the draw of their global rows: an injected
-        ``act.exp_noise`` is the global tensor, sliced; otherwise one Philox launch per view segment, whose first
-        row g0 starts at block g0 * h * w * P / 4 (P % 4 == 0 for every head kernel, so that is exact)."""
-        def draw(logits: Tensor, act) -> Tuple[Tensor, Tensor]:
-            if act.exp_noise is not None:
-                noise = act.exp_noise.to(device=logits.device, dtype=torch.float32)
-                return K.count_gumbel_soft(logits, act.tau, shard_rows(noise, start, rows, batch).contiguous(), 0)
-            per = logits[0].numel()
-            halves = [K.count_gumbel_soft(logits[v * rows:(v + 1) * rows], act.tau, None, seed,
-                                          offset=(v * batch + start) * per // 4) for v in (0, 1)]
-            return torch.cat([halves[0][0], halves[1][0]]), torch.cat([halves[0][1], halves[1][1]])
-        return draw
-
-    def _sharded_step(self, xs1, xs2, ys, optimizer_net, optimizer_classifier, phase, w, enforce_weight_sparsity,
-                      tanh_loss_coeff, sizes, sd_keep, step_optimizers) -> Tensor:
-        m, group = self.module, self.process_group
-        rows, batch, start = xs1.shape[0], sum(sizes), sum(sizes[:self.rank])
-        count, finetune = hasattr(m, "_max_count"), phase == "finetune"
-        cls = m._classification
-        masks = shard_masks(self.draw_masks(batch) if sd_keep is None else sd_keep, start, rows, batch)
-        xs = torch.cat([xs1, xs2])
-        w_align, w_tanh, w_class = w
-        with torch.no_grad():
-            if finetune:
-                feats, suffix = T._backbone_train_forward(m, xs, masks), None
-            else:
-                feats, suffix = T._backbone_forward_saving(m, xs, T.trainable_suffix_start(m), masks)
-            if count:
-                hd = T._count_head(m, feats, self._gumbel(self.draw_seed(), start, rows, batch))
-                head_backward = T._count_head_backward
-            else:
-                hd, head_backward = T._pipnet_head(m, feats), T._pipnet_head_backward
-            pooled_all, out_all, ys_all = exchange_rows(hd.pooled, hd.out, ys, sizes, group)
-            partial = K.train_align_partial(hd.proto)
-            if self.world > 1:
-                dist.all_reduce(partial, group=group)
-            stats, d_out_all = K.train_loss_from_partial(partial, hd.proto.shape[1] * hd.proto.shape[2], pooled_all,
-                                                         out_all, ys_all, cls.normalization_multiplier,
-                                                         enforce_weight_sparsity, tanh_loss_coeff, w_align, w_tanh,
-                                                         w_class, phase)
-            d_out = None if d_out_all is None else shard_rows(d_out_all, start, rows, batch)
-            T._classifier_grads(cls, hd, d_out, finetune)
-            d_logits = head_backward(m, hd, d_out, w_align, w_tanh, tanh_loss_coeff, to_logits=not finetune,
-                                     pooled_all=pooled_all)
-            del hd
-            if not finetune:
-                T._addon_suffix_backward(m, feats, suffix, d_logits)
-            self.reduce_gradients(phase, optimizer_classifier, optimizer_net)
-            if step_optimizers:
-                T._step_optimizers(m, None if phase == "pretrain" else optimizer_classifier,
-                                   None if finetune else optimizer_net, enforce_weight_sparsity)
-        return stats
+        return T._train_step(self.module, xs1, xs2, ys, phase=phase, optimizer_classifier=optimizer_classifier,
+                             optimizer_net=optimizer_net, w=T._loss_weights(phase == "pretrain", epoch, nr_epochs),
+                             enforce_weight_sparsity=enforce_weight_sparsity, tanh_loss_coeff=tanh_loss_coeff,
+                             sd_keep=sd_keep, generator=self.generator, step_optimizers=step_optimizers,
+                             shard=None if self.world == 1 and not self.force_exchange else Shard(self, sizes))
 
     def reduce_gradients(self, phase: str, optimizer_classifier, optimizer_net) -> Optional[GradArena]:
         """Sum every rank's gradients: pack them into the arena, ONE all-reduce, and each ``.grad`` becomes a view
@@ -304,15 +250,48 @@ class ShardedTraining(nn.Module):
         return self._arena
 
 
-class _ShardedEpoch(T.HipEpoch):
-    """``HipEpoch`` whose accuracy is over the global batch: the loader yields this rank's rows (equal shards)."""
+class Shard:
+    """A rank's place in one step's global batch -- rows [start, start + rows) of each view's ``batch`` -- and the
+    five things ``train._train_step`` asks of it, where such a step differs from one on the whole batch."""
 
-    def __init__(self, step, weights, track_acc: bool, world: int):
-        super().__init__(step, weights, track_acc)
-        self.world = world
+    def __init__(self, owner: ShardedTraining, sizes: Sequence[int]):
+        self.owner, self.sizes = owner, list(sizes)
+        self.start, self.rows, self.batch = sum(sizes[:owner.rank]), sizes[owner.rank], sum(sizes)
+        self.reduce_gradients = owner.reduce_gradients                # (5) the arena's all-reduce before AdamW
 
-    def _add(self, stats: Tensor, labels: int) -> None:
-        super()._add(stats, labels * self.world)
+    def masks(self, sd_keep: Optional[Dict[int, Tensor]]) -> Dict[int, Tensor]:
+        """(1) The rank's rows of the global masks ``sd_keep`` (None: drawn from the shared generator)."""
+        return shard_masks(self.owner.draw_masks(self.batch) if sd_keep is None else sd_keep, self.start, self.rows,
+                           self.batch)
+
+    def gumbel(self):
+        """(2) The Gumbel head of this rank's rows ``[view 1 | view 2]`` on the draw of their global rows: an injected
+        ``act.exp_noise`` is the global tensor, sliced; otherwise one Philox launch per view segment, whose first
+        row g0 starts at block g0 * h * w * P / 4 (P % 4 == 0 for every head kernel, so that is exact)."""
+        seed, start, rows, batch = self.owner.draw_seed(), self.start, self.rows, self.batch
+
+        def draw(logits: Tensor, act) -> Tuple[Tensor, Tensor]:
+            if act.exp_noise is not None:
+                noise = act.exp_noise.to(device=logits.device, dtype=torch.float32)
+                return K.count_gumbel_soft(logits, act.tau, shard_rows(noise, start, rows, batch).contiguous(), 0)
+            per = logits[0].numel()
+            halves = [K.count_gumbel_soft(logits[v * rows:(v + 1) * rows], act.tau, None, seed,
+                                          offset=(v * batch + start) * per // 4) for v in (0, 1)]
+            return torch.cat([halves[0][0], halves[1][0]]), torch.cat([halves[0][1], halves[1][1]])
+        return draw
+
+    def loss(self, hd, ys: Tensor, loss_args: tuple) -> Tuple[Tensor, Optional[Tensor], Tensor]:
+        """(3) ``kernels.train_loss`` on the gathered rows of every rank -> (the global batch's stats, this rank's
+        rows of d loss / d out, the gathered pooled rows: (4), what the rows form of the head backward needs)."""
+        group = self.owner.process_group
+        pooled_all, out_all, ys_all = exchange_rows(hd.pooled, hd.out, ys, self.sizes, group)
+        partial = K.train_align_partial(hd.proto)
+        if self.owner.world > 1:
+            dist.all_reduce(partial, group=group)
+        stats, d_out_all = K.train_loss_from_partial(partial, hd.proto.shape[1] * hd.proto.shape[2], pooled_all,
+                                                     out_all, ys_all, *loss_args)
+        d_out = None if d_out_all is None else shard_rows(d_out_all, self.start, self.rows, self.batch)
+        return stats, d_out, pooled_all
 
 
 def train_pipnet(net, train_loader, optimizer_net, optimizer_classifier, scheduler_net, scheduler_classifier,
@@ -333,22 +312,13 @@ def train_pipnet(net, train_loader, optimizer_net, optimizer_classifier, schedul
     if hasattr(m, "_max_count") != bool(is_count_pipnet):
         raise NotImplementedError(T._STEPS[bool(is_count_pipnet), bool(finetune)][2])
     phase = "pretrain" if pretrain else "finetune" if finetune else "train"
-    weights = T._loss_weights(pretrain, epoch, nr_epochs)
 
     def step(a, b, labels):
         return sharded.step(a, b, labels, optimizer_net, optimizer_classifier, phase=phase, epoch=epoch,
                             nr_epochs=nr_epochs, enforce_weight_sparsity=enforce_weight_sparsity,
                             tanh_loss_coeff=tanh_loss_coeff)
 
-    m.train()
-    m._classification.requires_grad = not pretrain
-    runner = _ShardedEpoch(step, weights, track_acc=not pretrain, world=sharded.world)
-    opts = [o for o in (optimizer_classifier, optimizer_net) if o is not None]
-    opts = [o for i, o in enumerate(opts) if all(o is not q for q in opts[:i])]
-    runner.run(train_loader, opts, epoch, device, None if pretrain else scheduler_classifier,
-               None if finetune else scheduler_net)
-    info = runner.summary()
-    if verbose and sharded.rank == 0:
-        terms = ", ".join(f"{t}={info[t + '_loss_raw']:.4f}" for t in T.HipEpoch.TERMS)
-        print(f"[{progress_prefix} {epoch}] HIP x{sharded.world}: {runner.count} iterations, {terms}", flush=True)
-    return info
+    return T._run_epoch(m, step, train_loader, optimizer_net, optimizer_classifier, scheduler_net, scheduler_classifier,
+                        epoch, nr_epochs, device, pretrain, finetune, world=sharded.world,
+                        say=f"[{progress_prefix} {epoch}] HIP x{sharded.world}" if verbose and sharded.rank == 0
+                        else None)

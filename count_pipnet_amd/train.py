@@ -662,32 +662,46 @@ def _classifier_grads(cls: nn.Module, hd: _Head, d_out: Optional[Tensor], finetu
 
 def _train_step(m: nn.Module, xs1: Tensor, xs2: Tensor, ys: Tensor, *, phase: str, optimizer_classifier,
                 optimizer_net=None, w: Tuple[float, float, float], enforce_weight_sparsity: bool,
-                tanh_loss_coeff: float = 1.0, sd_keep: Optional[Dict[int, Tensor]], generator, step_optimizers=True):
+                tanh_loss_coeff: float = 1.0, sd_keep: Optional[Dict[int, Tensor]], generator, step_optimizers=True,
+                shard=None):
     """One iteration of ``phase`` ("pretrain" | "train" | "finetune", also the loss kernel's mode):
     concatenate the views and draw the stochastic-depth masks; backbone, head and loss; classifier
     gradients; outside finetune the backward through head, add-on and the trainable suffix (whose
-    activations the forward then kept); AdamW on the device and the sparsity clamps."""
-    head, head_backward = (_count_head, _count_head_backward) if hasattr(m, "_max_count") else \
-        (_pipnet_head, _pipnet_head_backward)
-    finetune = phase == "finetune"
+    activations the forward then kept); AdamW on the device and the sparsity clamps.
+    ``shard`` (a ``dist_train.Shard``): the rows here are one rank's rows of a global batch, and ``sd_keep`` is
+    the global batch's; None: they are the whole batch.  It is asked in five places, marked (1) .. (5)."""
+    count, finetune = hasattr(m, "_max_count"), phase == "finetune"
+    head_backward = _count_head_backward if count else _pipnet_head_backward
     cls = m._classification
     xs = torch.cat([xs1, xs2])
-    if sd_keep is None:
+    if shard is not None:
+        sd_keep = shard.masks(sd_keep)                                    # (1) the rank's rows of the global masks
+    elif sd_keep is None:
         sd_keep = _sd_masks(m, xs.shape[0], generator)
     w_align, w_tanh, w_class = w
+    loss_args = (cls.normalization_multiplier, enforce_weight_sparsity, tanh_loss_coeff, w_align, w_tanh, w_class,
+                 phase)
     with torch.no_grad():
         if finetune:
             feats, suffix = _backbone_train_forward(m, xs, sd_keep), None
         else:
             feats, suffix = _backbone_forward_saving(m, xs, trainable_suffix_start(m), sd_keep)
-        hd = head(m, feats)
-        stats, d_out = K.train_loss(hd.proto, hd.pooled, hd.out, ys, cls.normalization_multiplier,
-                                    enforce_weight_sparsity, tanh_loss_coeff, w_align, w_tanh, w_class, phase)
+        if count:                                                         # (2) the draw of the rows' global place
+            hd = _count_head(m, feats, None if shard is None else shard.gumbel())
+        else:
+            hd = _pipnet_head(m, feats)
+        if shard is None:
+            (stats, d_out), pooled_all = K.train_loss(hd.proto, hd.pooled, hd.out, ys, *loss_args), None
+        else:                                                             # (3) the loss on every rank's rows
+            stats, d_out, pooled_all = shard.loss(hd, ys, loss_args)
         _classifier_grads(cls, hd, d_out, finetune)
-        d_logits = head_backward(m, hd, d_out, w_align, w_tanh, tanh_loss_coeff, to_logits=not finetune)
+        d_logits = head_backward(m, hd, d_out, w_align, w_tanh, tanh_loss_coeff, to_logits=not finetune,
+                                 pooled_all=pooled_all)                   # (4)
         del hd
         if not finetune:
             _addon_suffix_backward(m, feats, suffix, d_logits)
+        if shard is not None:                                             # (5) the ranks' gradients, summed
+            shard.reduce_gradients(phase, optimizer_classifier, optimizer_net)
         if step_optimizers:
             _step_optimizers(m, None if phase == "pretrain" else optimizer_classifier,
                              None if finetune else optimizer_net, enforce_weight_sparsity)
@@ -770,19 +784,21 @@ class HipEpoch:
     advance as in the reference -- the classifier's CosineAnnealingWarmRestarts to the
     fractional epoch position (train.py:120, not in pretrain), the backbone's scheduler once
     per iteration (train.py:124-126, not in finetune).  The five running sums (align, tanh,
-    class, loss, accuracy) live in one device vector; ``summary()`` is the single host read."""
+    class, loss, accuracy) live in one device vector; ``summary()`` is the single host read.
+    ``world``: the batches are one rank's rows of ``world`` equal shards and ``step`` returns the global batch's
+    stats (dist_train), so the accuracy is over ``world`` times the labels here."""
 
     TERMS = ("align", "tanh", "class")
 
-    def __init__(self, step, weights: Tuple[float, float, float], track_acc: bool):
-        self.step, self.weights, self.track_acc = step, weights, track_acc
+    def __init__(self, step, weights: Tuple[float, float, float], track_acc: bool, world: int = 1):
+        self.step, self.weights, self.track_acc, self.world = step, weights, track_acc, world
         self.sums: Optional[Tensor] = None
         self.count = 0
         self.lrs_class: list = []
         self.lrs_net: list = []
 
     def _add(self, stats: Tensor, labels: int) -> None:
-        acc = stats[4:5] / float(2 * labels) if self.track_acc else torch.zeros_like(stats[4:5])
+        acc = stats[4:5] / float(2 * labels * self.world) if self.track_acc else torch.zeros_like(stats[4:5])
         row = torch.cat([stats[:4], acc]).double()
         self.sums = row if self.sums is None else self.sums.add_(row)
         self.count += 1
@@ -847,7 +863,6 @@ def train_pipnet(net, train_loader, optimizer_net, optimizer_classifier, schedul
     hip_step, supported, refusal = _STEPS[count, finetune]
     if not supported(net):
         raise NotImplementedError(refusal)
-    weights = _loss_weights(pretrain, epoch, nr_epochs)
     args = (optimizer_classifier,) if finetune else (optimizer_net, optimizer_classifier, pretrain, epoch, nr_epochs)
     kwargs = dict(tanh_loss_coeff=tanh_loss_coeff) if count else {}
 
@@ -855,15 +870,25 @@ def train_pipnet(net, train_loader, optimizer_net, optimizer_classifier, schedul
         return hip_step(net, a, b, labels, *args, enforce_weight_sparsity=enforce_weight_sparsity,
                         generator=generator, **kwargs)
 
+    return _run_epoch(net, step, train_loader, optimizer_net, optimizer_classifier, scheduler_net, scheduler_classifier,
+                      epoch, nr_epochs, device, pretrain, finetune,
+                      say=f"[{progress_prefix} {epoch}] HIP" if verbose else None)
+
+
+def _run_epoch(net, step, train_loader, optimizer_net, optimizer_classifier, scheduler_net, scheduler_classifier,
+               epoch, nr_epochs, device, pretrain, finetune, world: int = 1, say: Optional[str] = None) -> dict:
+    """The epoch of ``train_pipnet`` here and in ``dist_train`` once ``step(a, b, labels) -> stats`` is chosen:
+    train mode, the classifier's ``requires_grad`` flag, ``HipEpoch`` (accuracy over ``world`` shards) with each
+    optimizer once, ``train_info``; ``say``: the head of the one progress line, None for none."""
     net.train()
     _inner(net)._classification.requires_grad = not pretrain
-    runner = HipEpoch(step, weights, track_acc=not pretrain)
+    runner = HipEpoch(step, _loss_weights(pretrain, epoch, nr_epochs), track_acc=not pretrain, world=world)
     opts = [o for o in (optimizer_classifier, optimizer_net) if o is not None]
     opts = [o for i, o in enumerate(opts) if all(o is not q for q in opts[:i])]
     runner.run(train_loader, opts, epoch, device, None if pretrain else scheduler_classifier,
                None if finetune else scheduler_net)
     info = runner.summary()
-    if verbose:
+    if say is not None:
         terms = ", ".join(f"{t}={info[t + '_loss_raw']:.4f}" for t in HipEpoch.TERMS)
-        print(f"[{progress_prefix} {epoch}] HIP: {runner.count} iterations, {terms}", flush=True)
+        print(f"{say}: {runner.count} iterations, {terms}", flush=True)
     return info

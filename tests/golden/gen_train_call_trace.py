@@ -8,7 +8,12 @@ launch is MEANT to change, twice:
     python tests/golden/gen_train_call_trace.py            # records traces and digests
     python tests/golden/gen_train_call_trace.py --merge    # a second run: keeps what both runs agree on
 
-(``--out FILE`` writes elsewhere, ``--parent HASH`` names the commit where git cannot.)
+(``--out FILE`` writes elsewhere, and ``--merge`` then merges with that file; ``--parent HASH`` names the commit where git cannot.)
+
+``--sharded`` records tests/golden/dist_train_call_trace.json instead: ``train_trace_cases.SHARDED_CASES`` through
+``dist_train.ShardedTraining.step`` at world 1 with the exchange path forced.  That file was recorded at the
+commit in its own "parent" field, while the sharded step was still a second copy of the plain one;
+tests/test_gpu_dist_train_trace.py holds the tree to it.
 
 Every case runs twice in each invocation as well.  Traces must agree in every run (an argument position that
 does not goes into ``train_trace_cases.MASKED`` and is listed in the header); a state digest is kept only for
@@ -29,11 +34,12 @@ import train_trace_cases as C                                    # noqa: E402
 from count_pipnet_amd import _lib, build                         # noqa: E402
 
 PATH = os.path.join(HERE, "train_call_trace.json")
+SHARDED_PATH = os.path.join(HERE, "dist_train_call_trace.json")
 
 
-def load():
+def load(path=PATH):
     """The file -> (header, {case: [[name, args], ...]}, {case: digest or None})."""
-    with open(PATH) as f:
+    with open(path) as f:
         doc = json.load(f)
     calls = doc["calls"]
     return doc, {n: [calls[k] for k in c["trace"]] for n, c in doc["cases"].items()}, \
@@ -43,18 +49,21 @@ def load():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--merge", action="store_true")
-    ap.add_argument("--out", default=PATH)
+    ap.add_argument("--sharded", action="store_true")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--parent", default=None)
     a = ap.parse_args()
+    a.out = a.out or (SHARDED_PATH if a.sharded else PATH)
+    names = C.SHARDED_CASES if a.sharded else C.CASES
     build.build()
     _lib.load()
     gpu = torch.device("cuda:0")
     traces, digests = {}, {}
     if a.merge:
-        _, traces, digests = load()
-    for name in C.CASES:
+        _, traces, digests = load(a.out)
+    for name in names:
         for _ in range(2):
-            trace, digest = C.trace_and_digest(name, gpu)
+            trace, digest = C.trace_and_digest(name, gpu, a.sharded)
             if name not in traces:
                 traces[name], digests[name] = trace, digest
                 continue
@@ -67,7 +76,7 @@ def main():
         print(f"{name}: {len(traces[name])} calls, digest {'kept' if digests[name] else 'not reproducible'}",
               flush=True)
     table, cases = {}, {}
-    for name in C.CASES:                 # the same launch recurs in many cases: store each distinct one once
+    for name in names:                   # the same launch recurs in many cases: store each distinct one once
         idx = [table.setdefault(json.dumps(c), len(table)) for c in traces[name]]
         cases[name] = {"digest": digests[name], "trace": idx}
     head = {"parent": a.parent or subprocess.run(["git", "rev-parse", "HEAD"], cwd=HERE, capture_output=True,

@@ -6,7 +6,8 @@ Kernels, in process:
   2. pipnet_pack_tensors_f32 against ``copy_`` into the slots: vector and scalar paths, zeroed padding, nothing
      written behind the arena;
   3. the Gumbel head on a row range with its Philox offset against those rows of the full-batch launch;
-  4. world 1: ``ShardedTraining.step`` is the plain step, bit for bit (stats, every .grad, parameters after 2 steps).
+  4. world 1: ``ShardedTraining.step`` is the plain step, bit for bit (stats, every .grad, parameters after 2 steps),
+     also with the exchange path forced (``force_exchange``: one shard that is the whole batch).
 
 Multi-rank, as tests/test_gpu_dist.py: torch.multiprocessing spawn, gloo, every rank on cuda:0 (RCCL refuses two
 ranks on one device), ONE spawn per world size running every scenario of that world:
@@ -296,13 +297,19 @@ def _same_tensors(a, b):
 # ------------------------------------------------------------------------------------------
 # 4. world 1
 # ------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["train_joint_mid_addon", "train_pretrain_mid_addon", "train_finetune_mid_addon",
-                                  "train_count_joint_onehot", "train_count_finetune_bilinear"])
-def test_world1_is_the_plain_step_bitwise(gpu, name):
+WORLD1 = ["train_joint_mid_addon", "train_pretrain_mid_addon", "train_finetune_mid_addon", "train_count_joint_onehot",
+          "train_count_finetune_bilinear"]
+
+
+@pytest.mark.parametrize("name,force_exchange", [(n, f) for f in (False, True) for n in WORLD1],
+                         ids=[n + f for f in ("", "-forced") for n in WORLD1])
+def test_world1_is_the_plain_step_bitwise(gpu, name, force_exchange):
+    """``force_exchange``: the exchange path on one shard that is the whole batch -- the rows kernels give the
+    full-batch bits, ``exchange_rows`` and the arena pack are copies, the GEMMs run at the same M."""
     import train_trace_cases as C
     from count_pipnet_amd.dist_train import ShardedTraining
     plain, dp = _Case(name, gpu), _Case(name, gpu)
-    st = ShardedTraining(dp.net, seed=3)
+    st = ShardedTraining(dp.net, seed=3, force_exchange=force_exchange)
     assert st.world == 1 and st.rank == 0 and st.module is dp.net
     for i in range(2):
         xs1, xs2, ys = (t.to(gpu) for t in plain.batches[i])
@@ -323,7 +330,7 @@ def test_world1_is_the_plain_step_bitwise(gpu, name):
         assert torch.equal(stats[0], stats[1]), (i, stats)
         assert len(g0) >= 2 and _same_tensors(g0, g1), (i, differ)
     assert _same_tensors(dict(plain.net.named_parameters()), dict(dp.net.named_parameters()))
-    assert st._arena is None                                  # no arena, no collective at world 1
+    assert (st._arena is not None) == force_exchange          # no arena, no collective at world 1 unless forced
 
 
 # ------------------------------------------------------------------------------------------

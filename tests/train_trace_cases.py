@@ -4,13 +4,17 @@
 schedulers up as the reference run did (the setup helpers below are the ones tests/test_gpu_train.py uses) and
 returns ``(net, optimizers, run)``; ``run(i)`` is iteration i on the HIP step of the fixture's phase, with the
 fixture's recorded stochastic-depth masks and injected Gumbel noise, so no fresh seed is drawn.
+``prepare(name, gpu, sharded=True)`` runs the same iteration through ``dist_train.ShardedTraining.step`` at world 1
+with the exchange path forced (one shard that is the whole batch; no process group, no collective);
+``SHARDED_CASES`` are the fixtures recorded that way.
 
 ``record_calls()`` wraps ``_lib.call`` -- every kernel launch goes through it -- and keeps ``[name, args]`` per
 call: an argument whose entry in ``_lib.SIGNATURES[name]`` is the pointer type is kept as 0 (null) or 1, every
 other one by value (floats as ``float.hex``).  ``state_digest`` is a sha256 over every parameter, every AdamW
 ``step`` / ``exp_avg`` / ``exp_avg_sq`` and every BatchNorm buffer.  tests/golden/gen_train_call_trace.py records
-both on the parent commit into tests/golden/train_call_trace.json; tests/test_gpu_train_trace.py holds the tree
-to them.
+both on the parent commit into tests/golden/train_call_trace.json (``--sharded``: the sharded step, into
+tests/golden/dist_train_call_trace.json); tests/test_gpu_train_trace.py and tests/test_gpu_dist_train_trace.py
+hold the tree to them.
 """
 import contextlib
 import hashlib
@@ -25,6 +29,10 @@ from golden_util import load_train_golden, train_golden_names, train_loader_batc
 from model_util import build_model
 
 CASES = train_golden_names()
+# the sharded step's record: 8 x 8 maps; every phase, a trainable stem, the Gumbel head, a bilinear layer
+SHARDED_CASES = ["train_joint_mid_addon", "train_pretrain_mid_addon", "train_finetune_mid_addon",
+                 "train_full_mid_addon", "train_count_joint_onehot", "train_count_joint_bilinear",
+                 "train_count_finetune_bilinear"]
 ITERATIONS = 2            # the trace is iteration 0; the digest is taken after iteration 1
 # (kernel name, argument position) pairs that differ between two runs of the parent and are left out
 MASKED = ()
@@ -162,8 +170,9 @@ def _inject_noise(net, meta, rec, i, gpu):
 
 
 # ---- one iteration per fixture -------------------------------------------------------------
-def prepare(name, gpu):
-    """(net, optimizers, run) of a fixture; ``run(i)`` is iteration i as the fixture's test steps it."""
+def prepare(name, gpu, sharded=False):
+    """(net, optimizers, run) of a fixture; ``run(i)`` is iteration i as the fixture's test steps it, ``sharded``:
+    through ``ShardedTraining(net, seed=5, force_exchange=True).step`` at world 1."""
     count, finetune = name.startswith("train_count_"), "_finetune_" in name
     if finetune:
         meta, rec, _, net, opt, sched, batches = (_count_setup if count else _finetune_setup)(name, gpu)
@@ -180,6 +189,11 @@ def prepare(name, gpu):
         batches = train_loader_batches(c["size"], c["num_classes"], meta["iterations"], meta["batch_per_view"],
                                        meta["seed"])
     assert len(batches) >= ITERATIONS, name
+    st = None
+    if sharded:
+        from count_pipnet_amd.dist_train import ShardedTraining
+        st = ShardedTraining(net, seed=5, force_exchange=True)
+        assert st.world == 1 and st.process_group is None
 
     def run(i):
         xs1, xs2, ys = (t.to(gpu) for t in batches[i])
@@ -188,7 +202,10 @@ def prepare(name, gpu):
             _inject_noise(net, meta, rec, i, gpu)
         for opt in opts:
             opt.zero_grad(set_to_none=True)
-        if finetune and count:
+        if sharded:
+            st.step(xs1, xs2, ys, None if finetune else opts[0], opts[-1], epoch=1, nr_epochs=2 if pretrain else 1,
+                    phase="finetune" if finetune else "pretrain" if pretrain else "train", sd_keep=sd_keep)
+        elif finetune and count:
             T.hip_count_finetune_step(net, xs1, xs2, ys, opts[0], True, 1.0, sd_keep=sd_keep)
         elif finetune:
             T.hip_finetune_step(net, xs1, xs2, ys, opts[0], True, sd_keep=sd_keep)
@@ -254,9 +271,9 @@ def state_digest(net, optimizers):
     return h.hexdigest()
 
 
-def trace_and_digest(name, gpu):
+def trace_and_digest(name, gpu, sharded=False):
     """Iteration 0's library calls and the state digest after ``ITERATIONS`` iterations."""
-    net, opts, run = prepare(name, gpu)
+    net, opts, run = prepare(name, gpu, sharded)
     with record_calls() as calls:
         run(0)
     for i in range(1, ITERATIONS):
