@@ -20,7 +20,7 @@ Percentile normalisation, colouring and plotting stay with the caller.
 """
 from __future__ import annotations
 
-from dataclasses import dataclass, fields
+from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -29,7 +29,7 @@ from torch import Tensor
 
 from . import kernels as K
 from .backend import _forced_torch, torch_backend
-from .topk import _unwrap
+from .explain_forward import HostCopy, is_count, map_is_small, note_map, unwrap
 
 METHODS = ("ig", "lig", "idg")
 KINDS = ("prototype", "class")
@@ -37,7 +37,7 @@ LIG_ALPHA_STAR = K.LIG_ALPHA_STAR
 
 
 @dataclass
-class Attribution:
+class Attribution(HostCopy):
     """Result of ``attribute``; tensors stay on the net's device until ``.cpu()`` is asked for.
     T = targets, S = steps."""
     maps: Tensor          # [T, 3, H, W] float32: what IG / IDG return per target
@@ -45,9 +45,6 @@ class Attribution:
     alphas: Tensor        # [T, S] path positions of the gradient pass
     weights: Tensor       # [T, S] per-step coefficient applied to the gradients
     cutoff: Tensor        # [T] int64 steps averaged: S unless lig
-
-    def cpu(self) -> "Attribution":
-        return Attribution(**{f.name: getattr(self, f.name).cpu() for f in fields(self)})
 
 
 def idg_schedule(slopes: Tensor, steps: int, step_size: float) -> Tuple[Tensor, Tensor]:
@@ -88,10 +85,6 @@ def uniform_slopes(scores: Tensor) -> Tuple[Tensor, float]:
     return slopes, step
 
 
-def _is_count(m: nn.Module) -> bool:
-    return hasattr(m, "_max_count")
-
-
 def _check_args(m: nn.Module, x: Tensor, targets, kind: str, method: str, steps: int, batch_size: int):
     if method not in METHODS:
         raise ValueError(f"attribute: unknown method {method!r} (expected one of {METHODS})")
@@ -126,7 +119,7 @@ def _hip_supported(m: nn.Module) -> Optional[str]:
         return f"the {m._net.hip_precision} build"
     if not all(p.dtype == torch.float32 for p in m.parameters()):
         return "non-float32 parameters"
-    if _is_count(m):
+    if is_count(m):
         if not isinstance(m._intermediate, (IdentityIntermediate, OneHotEncoder, LinearFull, LinearIntermediate,
                                             BilinearIntermediate)):
             return f"the intermediate layer {type(m._intermediate).__name__} (no HIP backward)"
@@ -168,7 +161,7 @@ def attribute(net, x: Tensor, targets: Sequence[int], *, kind: str = "prototype"
     ``backend.torch_backend()`` (torch autograd through the module's own forward, also the path of
     a CPU net).  Bad arguments raise ValueError (the reference prints and returns zeros).  No
     parameter's ``.grad`` or ``requires_grad`` changes; the call works with grad mode on or off."""
-    m = _unwrap(net)
+    m = unwrap(net, "attribute")
     x, targets = _check_args(m, x, targets, kind, method, int(steps), int(batch_size))
     steps, batch_size = int(steps), int(batch_size)
     m.eval()
@@ -313,16 +306,14 @@ def _gumbel_heads(logits: Tensor, tau: float, noise: Optional[Tensor], seed: int
 def _chunk_forward(m, x, baseline, alpha: Tensor, noise: Optional[Tensor], seed: int, step0: int) -> _Chunk:
     """Eval-mode forward of the path images at ``alpha`` (a chunk) keeping the activations."""
     from .count_pipnet_utils import GumbelSoftmax
-    from .local import _map_is_small, _note_map
     from .pipnet import add_on_activation, add_on_logits_hip
     from .train import _count_tail, _forward_saving
     ck = _Chunk()
     b = alpha.numel()
     images = K.attr_path_images(x, baseline, alpha)
     probe = x.unsqueeze(0)
-    small = _map_is_small(m, probe)
-    # small maps: per-image GEMM plan, as in explain_predictions (a Gumbel near-tie must not flip with
-    # the chunk size)
+    small = map_is_small(m, probe)
+    # small maps: per-image GEMM plan, so that the bits do not depend on the chunk size (explain_forward.small_map)
     with K.per_image_gemm_plan(b if small is not False else 1):
         ck.feats, ck.saved = _forward_saving(m, None, 0, {}, eval_mode=True, nhwc4=images)
         act = add_on_activation(m._add_on)
@@ -330,9 +321,9 @@ def _chunk_forward(m, x, baseline, alpha: Tensor, noise: Optional[Tensor], seed:
         logits = add_on_logits_hip(m._add_on, ck.feats, activation=GumbelSoftmax if gumbel else nn.Softmax)
     _, h, w, p = logits.shape
     ck.hw = (h, w)
-    _note_map(m, probe, ck.hw)
+    note_map(m, probe, ck.hw)
     ck.loc = ck.counts = ck.clamped = ck.inter_saved = None
-    if not _is_count(m):
+    if not is_count(m):
         ck.soft, ck.pooled, ck.loc = K.softmax_pool_argmax(logits, write_proto=True)
         ck.mode, ck.tau = 0, 1.0
         _, ck.out = K.nonneg_linear(ck.pooled, m._classification.weight, m._classification.bias, None)
@@ -362,7 +353,7 @@ def _upstream(m, ck: _Chunk, kind: str, t: int) -> Tensor:
         u[:, t] = 1.0
         return u
     cls = m._classification
-    if not _is_count(m):
+    if not is_count(m):
         return torch.relu(cls.weight.detach()[t]).expand(b, p).contiguous()
     d_out = torch.zeros((b, cls.weight.shape[0]), device=dev, dtype=torch.float32)
     d_out[:, t] = 1.0

@@ -16,22 +16,21 @@ cropping, drawing the rectangle, PNG writing and file names stay with the caller
 """
 from __future__ import annotations
 
-import argparse
-from dataclasses import dataclass, fields
+from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import torch
 from torch import Tensor
 
 from . import kernels as K
-from .convnext_features import as_nhwc
-from .topk import PATCH_SIZE, _pipnet_batch, _unwrap, img_coordinates, patch_size
+from .explain_forward import (PATCH_SIZE, HostCopy, is_count, located_forward, map_is_small, note_map, patch_geometry,
+                              patch_skip, unwrap)
 
 MIN_SIMWEIGHT = 0.01            # visualize_prediction.py:75: abs(simweight) > 0.01
 
 
 @dataclass
-class LocalExplanation:
+class LocalExplanation(HostCopy):
     """Result of ``explain_predictions``; tensors stay on the device until ``.cpu()`` is asked for.
     C = class ranks (rank 0 = the largest logit), M = ``max_entries`` slots per (image, class) in
     prototype order (pooled score descending, lower index first among equals).  Empty slots hold
@@ -49,10 +48,6 @@ class LocalExplanation:
     rect: Tensor          # [B, C, M, 4] int64 (x0, y0, x1, y1): the rectangle the reference draws (:87)
     proto_shape: Tuple[int, int, int, int]   # (1, P, H, W) handed to img_coordinates
 
-    def cpu(self) -> "LocalExplanation":
-        return LocalExplanation(**{f.name: (getattr(self, f.name).cpu() if torch.is_tensor(getattr(self, f.name))
-                                            else getattr(self, f.name)) for f in fields(self)})
-
 
 def count_importance_matrix(net, classifier_input_scalars: Optional[Tensor] = None) -> Tensor:
     """[K, P] with column p = ``net.get_prototype_importance_per_class(p, classifier_input_scalars)``:
@@ -65,17 +60,6 @@ def count_importance_matrix(net, classifier_input_scalars: Optional[Tensor] = No
             net._intermediate.prototype_to_classifier_input_weights(0).device)
     return torch.stack([net.get_prototype_importance_per_class(p, classifier_input_scalars)
                         for p in range(net._num_prototypes)], dim=1)
-
-
-def _map_is_small(net, xs: Tensor) -> Optional[bool]:
-    """Whether the latent map of this input size has at most K.SPLITK_MAX_M pixels; None until a
-    first call has seen it (``_note_map``)."""
-    hw = net.__dict__.get("_explain_hw", {}).get(tuple(xs.shape[2:]))
-    return None if hw is None else hw[0] * hw[1] <= K.SPLITK_MAX_M
-
-
-def _note_map(net, xs: Tensor, hw) -> None:
-    net.__dict__.setdefault("_explain_hw", {})[tuple(xs.shape[2:])] = tuple(hw)     # plain attribute, not a buffer
 
 
 def explain_predictions(net, xs: Tensor, top_classes: Optional[int] = 3, *, image_size: int,
@@ -95,9 +79,9 @@ def explain_predictions(net, xs: Tensor, top_classes: Optional[int] = 3, *, imag
     ``_classification.weight`` for PIP-Net, the per-class prototype importance for CountPIPNet
     (``count_importance_matrix``).  ``count`` holds the true number of kept prototypes; only the
     first ``max_entries`` are stored.  Nothing in the call waits for the device."""
-    net = _unwrap(net)
+    net = unwrap(net, "explain_predictions")
     net.eval()
-    count = hasattr(net, "_max_count")
+    count = is_count(net)
     pn = net._num_prototypes
     kc = net._classification.weight.shape[0]
     c = kc if top_classes is None else int(top_classes)
@@ -121,30 +105,16 @@ def explain_predictions(net, xs: Tensor, top_classes: Optional[int] = 3, *, imag
             w = count_importance_matrix(net).to(device=dev, dtype=torch.float32)
         else:
             w = net._classification.weight.detach()
-        small = _map_is_small(net, xs)
-        if count:
-            # small maps: per-image GEMM plan, as in prototype_topk (a Gumbel near-tie must not flip
-            # with the batch size)
-            with K.per_image_gemm_plan(xs.shape[0] if small is not False else 1):
-                proto, clamped, out = net(xs, inference=True)
-            _, loc = K.map_argmax(as_nhwc(proto))
-            hw = tuple(proto.shape[2:])
-        else:
-            clamped, loc, out, hw = _pipnet_batch(net, xs, small)
-        _note_map(net, xs, hw)
+        fwd = located_forward(net, xs, map_is_small(net, xs))
+        note_map(net, xs, fwd.hw)
         cls, cls_logit, n, e_proto, e_sim, e_w, e_simw, e_loc = K.local_explain(
-            clamped, loc, out, w, c, max_entries, min_simweight)
-        h, wd = hw
-        shape = (1, pn, h, wd)
-        _, skip = patch_size(argparse.Namespace(image_size=image_size, wshape=wd))
+            fwd.scores, fwd.loc, fwd.out, w, c, max_entries, min_simweight)
         empty = e_proto < 0
-        l = e_loc.long().clamp(min=0)
-        h_idx, w_idx = l // wd, l % wd
-        coords = torch.stack(img_coordinates(image_size, shape, PATCH_SIZE, skip, h_idx, w_idx), dim=-1)
+        h_idx, w_idx, coords, shape = patch_geometry(e_loc, empty, pn, fwd.hw[0], fwd.hw[1], image_size)
+        skip = patch_skip(image_size, fwd.hw[1])
         rect = torch.stack((w_idx * skip, h_idx * skip, torch.clamp(w_idx * skip + PATCH_SIZE, max=image_size),
-                            torch.clamp(h_idx * skip + PATCH_SIZE, max=image_size)), dim=-1)
+                            torch.clamp(h_idx * skip + PATCH_SIZE, max=image_size)), dim=-1)      # empty slots: masked below
         return LocalExplanation(
             classes=cls.long(), logits=cls_logit, count=n.long(), prototype=e_proto.long(), similarity=e_sim,
-            weight=e_w, simweight=e_simw, h_idx=h_idx.masked_fill(empty, -1), w_idx=w_idx.masked_fill(empty, -1),
-            coords=coords.masked_fill(empty.unsqueeze(-1), -1), rect=rect.masked_fill(empty.unsqueeze(-1), -1),
-            proto_shape=shape)
+            weight=e_w, simweight=e_simw, h_idx=h_idx, w_idx=w_idx, coords=coords,
+            rect=rect.masked_fill(empty.unsqueeze(-1), -1), proto_shape=shape)

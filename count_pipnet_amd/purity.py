@@ -6,7 +6,7 @@ images of every relevant prototype), then ``eval_prototypes_cub_parts_csv`` re-r
 image for its size and loops over nested dicts.  ``part_purity`` computes the same numbers in one
 pass at any batch size with no host synchronisation inside the loop:
 
-  batch-invariant forward with patch locations (topk._pipnet_batch)
+  batch-invariant forward with patch locations (explain_forward.located_forward)
     "all"   -> pipnet_part_purity_update per batch
     "topk"  -> pipnet_topk_update per batch, one pipnet_part_purity_rows at the end
   -> pipnet_part_purity_finish
@@ -20,7 +20,6 @@ thread in dataset order: the result is bitwise independent of the batch size.
 """
 from __future__ import annotations
 
-import argparse
 import csv
 from dataclasses import dataclass, fields
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -30,7 +29,8 @@ import torch
 from torch import Tensor
 
 from . import kernels as K
-from .topk import PATCH_SIZE, _pipnet_batch, _unwrap, img_coordinates, patch_size
+from .explain_forward import (PATCH_SIZE, HostCopy, img_coordinates, is_count, located_forward, patch_skip, small_map,
+                              unwrap)
 
 CSV_HEADER = ["prototype", "img name", "h_min_224", "h_max_224", "w_min_224", "w_max_224"]
 
@@ -171,7 +171,7 @@ def _summary(max_purity, most_purity) -> Tuple[float, float, float, float, int, 
 
 
 @dataclass
-class PartPurity:
+class PartPurity(HostCopy):
     """Result of ``part_purity``; tensors stay on the device until ``.cpu()`` is asked for.
     P = prototypes, M = merged parts (``merged_names``)."""
     mode: str
@@ -194,10 +194,6 @@ class PartPurity:
     merged_names: List[str]
     images: int
     geometry: Tuple[int, int, int, int, bool]     # (H, W, image_size, skip, small-stride rule)
-
-    def cpu(self) -> "PartPurity":
-        return PartPurity(**{f.name: (getattr(self, f.name).cpu() if torch.is_tensor(getattr(self, f.name))
-                                      else getattr(self, f.name)) for f in fields(self)})
 
     def csv_order(self) -> np.ndarray:
         """The in-csv prototypes in the order of the reference's dict: first appearance in the CSV
@@ -235,7 +231,7 @@ class PartPurity:
 
 
 def _geometry(h: int, w: int, image_size: int):
-    skip = patch_size(argparse.Namespace(image_size=image_size, wshape=w))[1] if w > 1 else 0
+    skip = patch_skip(image_size, w) if w > 1 else 0
     return (h, w, image_size, skip, h == 26 and w == 26)
 
 
@@ -253,8 +249,8 @@ def part_purity(net, loader, annotations: PartAnnotations, *, image_size: int, m
     depend on the batch size.  Nothing inside the batch loop waits for the device."""
     if mode not in ("all", "topk"):
         raise ValueError(f"part_purity: mode must be 'all' or 'topk', got {mode!r}")
-    net = _unwrap(net)
-    if hasattr(net, "_max_count"):
+    net = unwrap(net, "part_purity")
+    if is_count(net):
         raise NotImplementedError("part_purity: CountPIPNet is not supported (the reference's evaluation reads "
                                   "PIP-Net's pooled softmax scores); pass a PIPNet")
     if image_size < PATCH_SIZE:
@@ -277,8 +273,7 @@ def part_purity(net, loader, annotations: PartAnnotations, *, image_size: int, m
         for xs, _ in loader:
             xs = xs.to(dev, non_blocking=True)
             K.require_device(xs, "input images")
-            _, loc, _, hw, raw = _pipnet_batch(net, xs, None if hw is None else hw[0] * hw[1] <= K.SPLITK_MAX_M,
-                                               with_raw=True)
+            _, loc, _, hw, raw = located_forward(net, xs, small_map(hw), with_raw=True)
             if geo is None:
                 geo = _geometry(hw[0], hw[1], image_size)
             if mode == "all":

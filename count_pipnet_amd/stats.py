@@ -17,7 +17,7 @@ and HTML stay with the caller.
 """
 from __future__ import annotations
 
-from dataclasses import dataclass, fields
+from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import numpy as np
@@ -26,7 +26,7 @@ from torch import Tensor
 
 from . import kernels as K
 from .backend import use_hip
-from .topk import _unwrap
+from .explain_forward import HostCopy, is_count, unwrap
 
 NEAR_ZERO_THRESHOLD = 0.01      # histograms.py:395
 PIPNET_BINS = 50                # histograms.py:397 num_bins_continuous
@@ -58,7 +58,7 @@ def _ratio(num: Tensor, den: Tensor) -> Tensor:
 
 
 @dataclass
-class PrototypeClassStats:
+class PrototypeClassStats(HostCopy):
     """Result of ``class_prototype_stats``; tensors stay on the device until ``.cpu()`` is asked
     for.  K = classes, P = prototypes, NB = histogram bins."""
     n_class: Tensor       # [K] int64 images of class k
@@ -71,10 +71,6 @@ class PrototypeClassStats:
     edges: Optional[Tensor]   # [NB + 1] float32, None without histogram
     threshold: float      # the fp32 near-zero threshold compared against
     images: int           # images of the pass
-
-    def cpu(self) -> "PrototypeClassStats":
-        return PrototypeClassStats(**{f.name: (getattr(self, f.name).cpu() if torch.is_tensor(getattr(self, f.name))
-                                               else getattr(self, f.name)) for f in fields(self)})
 
     def mean_per_class(self) -> Tensor:
         """[P, K] float64 mean activation of prototype p over the images of class k
@@ -182,9 +178,9 @@ def class_prototype_stats(net, loader, *, num_classes: Optional[int] = None, max
     the result carries ``vmax`` for a second pass).  A label outside [0, num_classes) raises
     ValueError after the pass.  On a ROCm device the statistics are accumulated by one HIP kernel
     per batch; under ``torch_backend()`` or for a CPU net by torch ops in the same order."""
-    net = _unwrap(net)
+    net = unwrap(net, "class_prototype_stats")
     net.eval()
-    count = hasattr(net, "_max_count")
+    count = is_count(net)
     if continuous and not count:
         raise ValueError("class_prototype_stats: continuous=True applies to a CountPIPNet only")
     if edges is None:
@@ -219,9 +215,9 @@ def mean_intermediate_features(net, loader) -> Tensor:
     (pipnet_colsum_accum_f64), so no batch's counts are kept and the result does not depend on
     the batching."""
     from .count_pipnet import intermediate_hip
-    net = _unwrap(net)
+    net = unwrap(net, "mean_intermediate_features")
     net.eval()
-    if not hasattr(net, "_max_count"):
+    if not is_count(net):
         raise ValueError("mean_intermediate_features: needs a CountPIPNet")
     acc = []
 
@@ -249,7 +245,7 @@ def virtual_weights(net, loader=None, custom_onehot_scale: bool = False) -> Tens
     needs ``loader``), else None."""
     from .count_pipnet_utils import OneHotEncoder
     from .local import count_importance_matrix
-    net = _unwrap(net)
+    net = unwrap(net, "virtual_weights")
     scalars = None
     if custom_onehot_scale and isinstance(net._intermediate, OneHotEncoder):
         if loader is None:

@@ -46,31 +46,21 @@ def load(path=PATH):
         {n: c["digest"] for n, c in doc["cases"].items()}
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--merge", action="store_true")
-    ap.add_argument("--sharded", action="store_true")
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--parent", default=None)
-    a = ap.parse_args()
-    a.out = a.out or (SHARDED_PATH if a.sharded else PATH)
-    names = C.SHARDED_CASES if a.sharded else C.CASES
-    build.build()
-    _lib.load()
-    gpu = torch.device("cuda:0")
+def record(names, run_case, out, merge, parent, note, masked):
+    """Run every case twice (``run_case(name) -> (trace, digest)``), merge with ``out`` if asked, and write ``out``."""
     traces, digests = {}, {}
-    if a.merge:
-        _, traces, digests = load(a.out)
+    if merge:
+        _, traces, digests = load(out)
     for name in names:
         for _ in range(2):
-            trace, digest = C.trace_and_digest(name, gpu, a.sharded)
+            trace, digest = run_case(name)
             if name not in traces:
                 traces[name], digests[name] = trace, digest
                 continue
             diff = [(x, y) for x, y in zip(traces[name], trace) if x != y]
             if diff or len(trace) != len(traces[name]):
                 raise SystemExit(f"{name}: the trace differs between two runs ({len(traces[name])} / {len(trace)} "
-                                 f"calls); first difference {diff[:1]}: mask the position in train_trace_cases.MASKED")
+                                 f"calls); first difference {diff[:1]}: mask the position in the cases' MASKED")
             if digests[name] != digest:
                 digests[name] = None
         print(f"{name}: {len(traces[name])} calls, digest {'kept' if digests[name] else 'not reproducible'}",
@@ -79,17 +69,31 @@ def main():
     for name in names:                   # the same launch recurs in many cases: store each distinct one once
         idx = [table.setdefault(json.dumps(c), len(table)) for c in traces[name]]
         cases[name] = {"digest": digests[name], "trace": idx}
-    head = {"parent": a.parent or subprocess.run(["git", "rev-parse", "HEAD"], cwd=HERE, capture_output=True,
-                                                 text=True, check=True).stdout.strip(),
-            "note": "per case: the library calls of iteration 0 as indices into 'calls' ([name, args]; a pointer "
-                    "argument is 0 for null and 1 otherwise, a float is float.hex), and the sha256 of parameters, "
-                    "AdamW state and BatchNorm buffers after 2 iterations (null where two runs of the parent gave "
-                    "different bits)",
-            "masked": [list(m) for m in C.MASKED]}
-    with open(a.out, "w") as out:
-        out.write("{\n" + "".join(f" {json.dumps(k)}: {json.dumps(v)},\n" for k, v in head.items()))
-        out.write(' "cases": {\n' + ",\n".join(f"  {json.dumps(n)}: {json.dumps(c)}" for n, c in cases.items()))
-        out.write('\n },\n "calls": [\n' + ",\n".join("  " + c for c in table) + "\n ]\n}\n")
+    head = {"parent": parent or subprocess.run(["git", "rev-parse", "HEAD"], cwd=HERE, capture_output=True,
+                                               text=True, check=True).stdout.strip(),
+            "note": note, "masked": [list(m) for m in masked]}
+    with open(out, "w") as f:
+        f.write("{\n" + "".join(f" {json.dumps(k)}: {json.dumps(v)},\n" for k, v in head.items()))
+        f.write(' "cases": {\n' + ",\n".join(f"  {json.dumps(n)}: {json.dumps(c)}" for n, c in cases.items()))
+        f.write('\n },\n "calls": [\n' + ",\n".join("  " + c for c in table) + "\n ]\n}\n")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--merge", action="store_true")
+    ap.add_argument("--sharded", action="store_true")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--parent", default=None)
+    a = ap.parse_args()
+    build.build()
+    _lib.load()
+    gpu = torch.device("cuda:0")
+    record(C.SHARDED_CASES if a.sharded else C.CASES, lambda name: C.trace_and_digest(name, gpu, a.sharded),
+           a.out or (SHARDED_PATH if a.sharded else PATH), a.merge, a.parent,
+           "per case: the library calls of iteration 0 as indices into 'calls' ([name, args]; a pointer "
+           "argument is 0 for null and 1 otherwise, a float is float.hex), and the sha256 of parameters, "
+           "AdamW state and BatchNorm buffers after 2 iterations (null where two runs of the parent gave "
+           "different bits)", C.MASKED)
 
 
 if __name__ == "__main__":

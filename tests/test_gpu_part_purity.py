@@ -9,7 +9,7 @@ import torch
 from count_pipnet_amd import kernels as K
 from count_pipnet_amd.pipnet import set_hip_dtype
 from count_pipnet_amd.purity import part_purity
-from count_pipnet_amd.topk import _pipnet_batch
+from count_pipnet_amd.explain_forward import located_forward
 from golden_util import eval_loader_batches, load_golden
 from model_util import build_model
 from part_purity_util import (FIXTURES, annotations_table, assert_finish_matches, assert_matches_recording,
@@ -205,7 +205,7 @@ def test_recorded_reference_data_through_the_kernels(gpu, name, mode, tmp_path):
 def _own_forward(net, xs, gpu):
     """(raw pooled [N,P], loc [N,P]) of the batch-1 forwards, image by image."""
     with torch.no_grad():
-        outs = [_pipnet_batch(net, xs[i:i + 1].to(gpu), None, with_raw=True) for i in range(xs.shape[0])]
+        outs = [located_forward(net, xs[i:i + 1].to(gpu), None, with_raw=True) for i in range(xs.shape[0])]
     hw = outs[0][3]
     return (torch.cat([o[4] for o in outs]).cpu().numpy(), torch.cat([o[1] for o in outs]).cpu().numpy(), hw)
 

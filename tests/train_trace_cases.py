@@ -224,14 +224,15 @@ def prepare(name, gpu, sharded=False):
 
 
 @contextlib.contextmanager
-def record_calls():
-    """Within the context every ``_lib.call`` is appended to the yielded list as ``[name, args]``."""
+def record_calls(masked=MASKED):
+    """Within the context every ``_lib.call`` is appended to the yielded list as ``[name, args]``; a
+    ``(kernel name, argument position)`` of ``masked`` is kept as None."""
     calls, real = [], _lib.call
 
     def recording(name, *args):
         row = []
         for pos, (kind, a) in enumerate(zip(_lib.SIGNATURES[name], args)):
-            if (name, pos) in MASKED:
+            if (name, pos) in masked:
                 row.append(None)
             elif kind is _lib.P:
                 row.append(int(bool(a)))
