@@ -7,7 +7,7 @@ chunks of 16 through torch autograd, per prototype per image (interpret_idg.py:7
 ``attribute`` runs the same three methods with every step on the HIP kernels:
 
   path images (4-channel NHWC, one launch per chunk) -> eval-mode forward that keeps its activations
-  (train._forward_saving) -> add-on -> head (softmax + max-pool with arg-location / hard and soft
+  (convnext_train.train_forward) -> add-on -> head (softmax + max-pool with arg-location / hard and soft
   Gumbel-softmax on one noise draw / softmax + sum) -> per target: upstream vector u -> head backward
   -> dx-only backward through add-on and backbone -> stem input gradient, written straight into the
   path's gradient store -> per-step coefficients (LeftIG cutoff included) and the path reduction.
@@ -110,10 +110,10 @@ def _check_args(m: nn.Module, x: Tensor, targets, kind: str, method: str, steps:
 
 def _hip_supported(m: nn.Module) -> Optional[str]:
     """None when the HIP path serves this net, else what stands in the way."""
-    from .convnext_features import ConvNeXt, MidLayerConvNeXt
+    from . import convnext_train
     from .count_pipnet_utils import (BilinearIntermediate, IdentityIntermediate, LinearFull, LinearIntermediate,
                                      OneHotEncoder)
-    if not isinstance(getattr(m, "_net", None), (ConvNeXt, MidLayerConvNeXt)):
+    if not convnext_train.supported(getattr(m, "_net", None)):
         return f"a {type(getattr(m, '_net', None)).__name__} backbone (ConvNeXt only)"
     if getattr(m._net, "hip_precision", "fp32") != "fp32":
         return f"the {m._net.hip_precision} build"
@@ -307,7 +307,8 @@ def _chunk_forward(m, x, baseline, alpha: Tensor, noise: Optional[Tensor], seed:
     """Eval-mode forward of the path images at ``alpha`` (a chunk) keeping the activations."""
     from .count_pipnet_utils import GumbelSoftmax
     from .pipnet import add_on_activation, add_on_logits_hip
-    from .train import _count_tail, _forward_saving
+    from .convnext_train import train_forward
+    from .train import _count_tail
     ck = _Chunk()
     b = alpha.numel()
     images = K.attr_path_images(x, baseline, alpha)
@@ -315,7 +316,7 @@ def _chunk_forward(m, x, baseline, alpha: Tensor, noise: Optional[Tensor], seed:
     small = map_is_small(m, probe)
     # small maps: per-image GEMM plan, so that the bits do not depend on the chunk size (explain_forward.small_map)
     with K.per_image_gemm_plan(b if small is not False else 1):
-        ck.feats, ck.saved = _forward_saving(m, None, 0, {}, eval_mode=True, nhwc4=images)
+        ck.feats, ck.saved = train_forward(m._net, None, 0, {}, eval_mode=True, nhwc4=images)
         act = add_on_activation(m._add_on)
         gumbel = isinstance(act, GumbelSoftmax)
         logits = add_on_logits_hip(m._add_on, ck.feats, activation=GumbelSoftmax if gumbel else nn.Softmax)
@@ -368,9 +369,8 @@ def _upstream(m, ck: _Chunk, kind: str, t: int) -> Tensor:
 
 def _stem_dx(m, stem_saved, dy: Tensor, hw_image, out_rows: Tensor) -> None:
     """Stem LayerNorm backward, then the conv's input gradient into ``out_rows`` [B, ld]."""
-    _, mod, _, sv = stem_saved
-    conv, ln = mod[0], mod[1]
-    z = sv["z"]
+    conv, ln = stem_saved.mod[0], stem_saved.mod[1]
+    z = stem_saved.act["z"]
     b, h, w, c = z.shape
     scratch = torch.empty(2, c, device=z.device)
     dz = K.ln_backward(z.view(-1, c), dy.reshape(-1, c), ln.weight.detach(), scratch[0], scratch[1], want_dz=True)
@@ -378,10 +378,11 @@ def _stem_dx(m, stem_saved, dy: Tensor, hw_image, out_rows: Tensor) -> None:
 
 
 def _chunk_backward(m, ck: _Chunk, kind: str, t: int, hw_image, out_rows: Tensor) -> None:
-    from .train import _addon_suffix_backward
+    from . import convnext_train
+    from .train import _addon_backward
     u = _upstream(m, ck, kind, t)
     d_logits = K.attr_head_backward(ck.soft, u, ck.loc, ck.mode, ck.tau)
-    dy = _addon_suffix_backward(m, ck.feats, ck.saved, d_logits, param_grads=False)
+    dy = convnext_train.backward(m._net, ck.saved, _addon_backward(m, ck.feats, d_logits, False), param_grads=False)
     _stem_dx(m, ck.saved[0], dy, hw_image, out_rows)
 
 

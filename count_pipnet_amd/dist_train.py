@@ -45,6 +45,7 @@ from torch import Tensor
 from . import kernels as K
 from . import train as T
 from .dist import all_gather_rows
+from .resnet_features import ResNet_features
 
 PHASES = ("pretrain", "train", "finetune")
 _RESNET_REFUSAL = ("count_pipnet_amd.dist_train: a ResNet backbone trains with train-mode BatchNorm, which couples "
@@ -209,7 +210,7 @@ class ShardedTraining(nn.Module):
             raise ValueError(f"dist_train: every rank needs at least one row and rank {self.rank} holds {rows} "
                              f"(sizes {sizes})")
         m = self.module
-        if self.world > 1 and T._is_resnet(m):
+        if self.world > 1 and isinstance(getattr(m, "_net", None), ResNet_features):
             raise NotImplementedError(_RESNET_REFUSAL)
         _, supported, refusal = T._STEPS[hasattr(m, "_max_count"), phase == "finetune"]
         if not supported(m):

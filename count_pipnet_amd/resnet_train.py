@@ -57,6 +57,10 @@ def supported(model) -> bool:
     return not any(p.requires_grad for p in stem)
 
 
+def units(model) -> int:
+    return len(_blocks(model))
+
+
 def trainable_start(model) -> int:
     """Index (in ``_blocks`` order) of the first block with a trainable parameter; the block
     count when the backbone is frozen."""
@@ -65,6 +69,11 @@ def trainable_start(model) -> int:
         if any(p.requires_grad for p in blk.parameters()):
             return i
     return len(blocks)
+
+
+def sd_masks(model, batch: int, generator: Optional[torch.Generator]) -> Dict[int, Tensor]:
+    """A ResNet has no stochastic depth: no mask, and nothing drawn from ``generator``."""
+    return {}
 
 
 def _conv(cache: Dict, key: str, conv: nn.Conv2d, x: Tensor, cpad: Optional[int] = None) -> Tensor:
@@ -116,9 +125,9 @@ def _block_forward(cache: Dict, key: str, blk, x: Tensor, save: bool):
     return out, rec
 
 
-def train_forward(model, xs: Tensor, start: Optional[int]) -> Tuple[Tensor, list]:
+def train_forward(model, xs: Tensor, start: Optional[int], sd_keep=None) -> Tuple[Tensor, list]:
     """ResNet_features.forward in train mode on NHWC fp32 -> (features NHWC, saved): the
-    blocks from ``start`` on keep their activations (``start`` None: none kept)."""
+    blocks from ``start`` on keep their activations (``start`` None: none kept; ``sd_keep``: unused)."""
     K.require_device(xs, "network input")
     xs = xs.contiguous()
     if xs.shape[1] != 3:
@@ -222,9 +231,11 @@ def _block_backward(cache: Dict, key: str, blk, sv: dict, dout: Tensor, need_dx:
     return dx
 
 
-def backward(model, saved: list, dfeat: Tensor) -> None:
+def backward(model, saved: list, dfeat: Tensor, param_grads: bool = True) -> None:
     """Backward from d features (NHWC) through the saved blocks (last to first); every
     backbone parameter with requires_grad gets .grad."""
+    if not param_grads:
+        raise NotImplementedError("ResNet HIP training: no input-gradient-only backward")
     cache = model._hip_pack.setdefault("train", {})
     dy = dfeat.contiguous()
     for i in range(len(saved) - 1, -1, -1):

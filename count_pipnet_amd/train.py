@@ -24,9 +24,10 @@ the device RNG: same distribution, different stream -- RNG parity unpinned; the 
 inject the masks recorded from the reference).
 
 The pretrain / joint / "train everything" phases backpropagate into a trainable backbone
-suffix on the same kernels: ConvNeXt CNBlocks / downsamples / stem (``_forward_saving``,
-``_block_backward``) and the ResNet-50 Bottlenecks with train-mode BatchNorm
-(``resnet_train``; every BN of the backbone, frozen ones included, normalises with batch
+suffix on the same kernels.  A backbone's train-mode forward and backward live in its own module,
+both behind one surface (``train_forward``, ``backward``, ...; ``_backbone`` picks the module):
+``convnext_train`` (CNBlocks / downsamples / stem) and ``resnet_train`` (the ResNet-50 Bottlenecks
+with train-mode BatchNorm; every BN of the backbone, frozen ones included, normalises with batch
 statistics and updates its running statistics, as under the reference's ``net.train()``).
 
 Every phase of both models is the one ``_train_step``; the four public ``hip_*_step`` functions
@@ -40,9 +41,10 @@ import torch
 import torch.nn as nn
 from torch import Tensor
 
+from . import _lib, convnext_train, resnet_train
 from . import kernels as K
-from .backend import _set_grad, packed
-from .convnext_features import CNBlock, ConvNeXt, MidLayerConvNeXt, convnext_features_hip
+from .backend import _set_grad
+from .convnext_train import stochastic_depth_masks  # noqa: F401  (its callers know it from here)
 
 # (align, tanh, class) loss weights of the non-pretrain phases (train.py:56-61)
 FINETUNE_LOSS_WEIGHTS = (5.0, 2.0, 2.0)
@@ -53,56 +55,34 @@ def _inner(net: nn.Module) -> nn.Module:
     return getattr(net, "module", net)
 
 
-def _is_resnet(m: nn.Module) -> bool:
-    from .resnet_features import ResNet_features
-    return isinstance(getattr(m, "_net", None), ResNet_features)
-
-
-def _backbone_ok(m: nn.Module) -> bool:
-    """A backbone with a HIP train-mode forward: ConvNeXt (full or mid-layer) or a Bottleneck
-    ResNet with the stem frozen (resnet_train.supported)."""
-    if isinstance(getattr(m, "_net", None), (ConvNeXt, MidLayerConvNeXt)):
-        return True
-    if _is_resnet(m):
-        from . import resnet_train
-        return resnet_train.supported(m._net)
-    return False
+def _backbone(m: nn.Module):
+    """The module with the train-mode forward and backward of ``m``'s backbone: ``convnext_train``
+    (ConvNeXt, full or mid-layer), ``resnet_train`` (a Bottleneck ResNet with the stem frozen), or
+    None where neither supports it."""
+    net = getattr(m, "_net", None)
+    return next((b for b in (convnext_train, resnet_train) if b.supported(net)), None)
 
 
 def _sd_masks(m: nn.Module, batch: int, generator: Optional[torch.Generator]) -> Dict[int, Tensor]:
     """Stochastic-depth keep masks of the backbone (ResNets have none)."""
-    if _is_resnet(m):
-        return {}
-    return stochastic_depth_masks(m._net.features, batch, generator)
+    return _backbone(m).sd_masks(m._net, batch, generator)
 
 
-def _backbone_train_forward(m: nn.Module, xs: Tensor, sd_keep: Dict[int, Tensor]) -> Tensor:
-    """Train-mode backbone forward without kept activations -> NHWC features."""
-    if _is_resnet(m):
-        from . import resnet_train
-        return resnet_train.train_forward(m._net, xs, None)[0]
-    return convnext_features_hip(m._net.features, xs, m._net._hip_pack, sd_keep)
-
-
-def stochastic_depth_masks(features: nn.Sequential, batch: int,
-                           generator: Optional[torch.Generator] = None) -> Dict[int, Tensor]:
-    """Host keep masks (bool [batch]) for every CNBlock with p > 0, keyed by block id in
-    module order: StochasticDepth("row") keeps a sample's branch with probability 1 - p."""
-    masks: Dict[int, Tensor] = {}
-    blocks = [b for mod in features if isinstance(mod, nn.Sequential) for b in mod if isinstance(b, CNBlock)]
-    for bid, blk in enumerate(blocks):
-        if blk.stochastic_depth.p > 0.0:
-            masks[bid] = torch.rand(batch, generator=generator) >= blk.stochastic_depth.p
-    return masks
+def trainable_suffix_start(net: nn.Module) -> int:
+    """Index j of the first ``features`` entry (ConvNeXt) or residual block (ResNet) holding a
+    trainable parameter (their count when the backbone is frozen).  Gradients flow through
+    every entry from j on."""
+    m = _inner(net)
+    return _backbone(m).trainable_start(m._net)
 
 
 def _supported(net: nn.Module, count: bool, finetune: bool) -> bool:
     """True when the iteration runs on the HIP kernels: a PIP-Net (``count``: a CountPIPNet whose
     intermediate layer has a HIP backward) on a backbone with a HIP train-mode forward, fp32 on a
     ROCm device, whose trainable set fits the phase -- ``finetune``: within the classifier (and the
-    intermediate layer); otherwise a backbone suffix features[j:] (j = 0: the stem too)."""
+    intermediate layer); otherwise a backbone suffix from unit j on (a ConvNeXt's j = 0: the stem too)."""
     m = _inner(net)
-    if hasattr(m, "_max_count") != count or not hasattr(m, "_classification") or not _backbone_ok(m):
+    if hasattr(m, "_max_count") != count or not hasattr(m, "_classification") or _backbone(m) is None:
         return False
     if count:
         from .count_pipnet_utils import (BilinearIntermediate, IdentityIntermediate, LinearFull, LinearIntermediate,
@@ -113,37 +93,39 @@ def _supported(net: nn.Module, count: bool, finetune: bool) -> bool:
     if not all(p.is_cuda and p.dtype == torch.float32 for p in m.parameters()):
         return False
     if not finetune:
-        return trainable_suffix_start(m) < _backbone_units(m)
+        return trainable_suffix_start(m) < _backbone(m).units(m._net)
     cls = m._classification
     allowed = list(cls.parameters()) + list(m._intermediate.parameters()) if count else [cls.weight, cls.bias]
     return {id(p) for p in m.parameters() if p.requires_grad} <= {id(p) for p in allowed}
 
 
 def hip_finetune_supported(net: nn.Module) -> bool:
-    """True when the finetune iteration runs on the HIP kernels: a PIP-Net (not Count)
-    with a ConvNeXt backbone, fp32 on a ROCm device, only classifier parameters trainable."""
+    """True when the finetune iteration runs on the HIP kernels: a PIP-Net (not Count) on a
+    backbone ``_backbone`` knows (ConvNeXt, or a Bottleneck ResNet with the stem frozen), fp32 on
+    a ROCm device, only classifier parameters trainable."""
     return _supported(net, count=False, finetune=True)
 
 
 def hip_count_finetune_supported(net: nn.Module) -> bool:
-    """A ConvNeXt CountPIPNet (fp32, ROCm) whose trainable parameters are within the
+    """A CountPIPNet on such a backbone (fp32, ROCm) whose trainable parameters are within the
     classifier and an intermediate layer with a HIP backward (identity, one-hot, linear_full,
-    bilinear)."""
+    linear, bilinear)."""
     return _supported(net, count=True, finetune=True)
 
 
 def hip_train_supported(net: nn.Module) -> bool:
-    """A ConvNeXt PIP-Net (fp32, ROCm) whose trainable backbone part is a suffix features[j:]
-    (the reference's pretrain / "train + freeze params" phases; j = 0, the stem included: the
-    "train everything" epochs after freeze_epochs, main.py:362-373)."""
+    """A PIP-Net on such a backbone (fp32, ROCm) with a trainable backbone part: a ConvNeXt's
+    suffix features[j:] (the reference's pretrain / "train + freeze params" phases; j = 0, the
+    stem included: the "train everything" epochs after freeze_epochs, main.py:362-373), a
+    ResNet's residual blocks from the first trainable one on."""
     return _supported(net, count=False, finetune=False)
 
 
 def hip_count_train_supported(net: nn.Module) -> bool:
-    """A ConvNeXt CountPIPNet (fp32, ROCm) whose trainable backbone part is a suffix
-    features[j:] (j = 0: the stem too), with an intermediate layer that has a HIP backward
-    (the reference's pretrain, "train + freeze params" and "train everything" phases for
-    CountPIPNet, main.py:238-256, 360-390)."""
+    """A CountPIPNet on such a backbone (fp32, ROCm) with a trainable backbone part as for
+    ``hip_train_supported`` and an intermediate layer that has a HIP backward (the reference's
+    pretrain, "train + freeze params" and "train everything" phases for CountPIPNet,
+    main.py:238-256, 360-390)."""
     return _supported(net, count=True, finetune=False)
 
 
@@ -187,7 +169,7 @@ def train_forward_hip(net: nn.Module, xs: Tensor, sd_keep: Optional[Dict[int, Te
         saved = [(b, b.clone()) for b in m._net.buffers()]
     with torch.no_grad():
         try:
-            feats = _backbone_train_forward(m, xs, sd_keep)
+            feats = _backbone(m).train_forward(m._net, xs, None, sd_keep)[0]
         finally:
             for b, v in saved or ():
                 b.copy_(v)
@@ -232,7 +214,6 @@ def hip_adamw_step(optimizer: torch.optim.Optimizer, param: Tensor, grad: Tensor
 def _count_tail(m: nn.Module, clamped: Tensor):
     """Intermediate layer and classifier of a CountPIPNet on the clamped counts: (activations the
     bilinear backward needs, classifier input, logits)."""
-    from . import _lib
     from .count_pipnet import intermediate_hip
     from .count_pipnet_utils import BilinearIntermediate
     layer = m._intermediate
@@ -286,7 +267,7 @@ def _count_head(m: nn.Module, feats: Tensor, gumbel=None) -> _Head:
 def _count_train_forward(m: nn.Module, xs: Tensor, sd_keep: Dict[int, Tensor]):
     """CountPIPNet.forward(xs) in train mode on the HIP kernels: (proto NHWC, raw counts, clamped
     counts, the head's saved dict, classifier input, out)."""
-    hd = _count_head(m, _backbone_train_forward(m, xs, sd_keep))
+    hd = _count_head(m, _backbone(m).train_forward(m._net, xs, None, sd_keep)[0])
     return hd.proto, hd.pooled, hd.saved["clamped"], hd.saved, hd.cls_in, hd.out
 
 
@@ -296,7 +277,6 @@ def _intermediate_backward(layer: nn.Module, x: Tensor, saved: dict, d_inter: Te
     ``need_dx``, the gradient w.r.t. its input x (the clamped counts) -- None where no gradient
     flows (a OneHotEncoder without STE: create_modified_encoding is not differentiable).
     ``param_grads=False``: the input gradient only, no parameter's .grad is touched."""
-    from . import _lib
     from .count_pipnet_utils import (BilinearIntermediate, IdentityIntermediate, LinearFull, LinearIntermediate,
                                      OneHotEncoder)
     if isinstance(layer, IdentityIntermediate):
@@ -363,249 +343,23 @@ def _count_head_backward(m: nn.Module, hd: _Head, d_out: Optional[Tensor], w_ali
 # Pretrain / joint phases: a trainable backbone suffix + add-on (+ classifier) on the HIP
 # kernels (main.py:238-256 pretrain, :377-390 "train + freeze params")
 # ------------------------------------------------------------------------------------------
-def _cnblocks(seq) -> list:
-    return [b for mod in seq if isinstance(mod, nn.Sequential) for b in mod if isinstance(b, CNBlock)]
-
-
-def trainable_suffix_start(net: nn.Module) -> int:
-    """Index j of the first ``features`` entry (ConvNeXt) or residual block (ResNet) holding a
-    trainable parameter (their count when the backbone is frozen).  Gradients flow through
-    every entry from j on."""
-    m = _inner(net)
-    if _is_resnet(m):
-        from . import resnet_train
-        return resnet_train.trainable_start(m._net)
-    for j, mod in enumerate(m._net.features):
-        if any(p.requires_grad for p in mod.parameters()):
-            return j
-    return len(m._net.features)
-
-
-def _backbone_units(m: nn.Module) -> int:
-    if _is_resnet(m):
-        from . import resnet_train
-        return len(resnet_train._blocks(m._net))
-    return len(m._net.features)
-
-
-def _backbone_forward_saving(m: nn.Module, xs: Tensor, j: int, sd_keep: Dict[int, Tensor]):
-    """Train-mode backbone forward keeping the activations of the trainable suffix from j."""
-    if _is_resnet(m):
-        from . import resnet_train
-        feats, saved = resnet_train.train_forward(m._net, xs, j)
-        return feats, [("resnet", None, None, saved)]
-    return _forward_saving(m, xs, j, sd_keep)
-
-
-def _forward_saving(m: nn.Module, xs: Tensor, j: int, sd_keep: Dict[int, Tensor], eval_mode: bool = False,
-                    nhwc4: Optional[Tensor] = None):
-    """Train-mode forward; features[:j] on the inference executor, features[j:] with plain
-    (unfused) kernels whose intermediates are kept: per CNBlock the input x, the depthwise
-    output z, the LayerNorm output t, the Linear1 pre-activation h1, GELU output g and the
-    Linear2 output y2; per downsample its input and LayerNorm output.
-    ``eval_mode``: stochastic depth is the identity (no masks, no 1 / (1 - p) scale: every block
-    runs with rs = None), as under ``net.eval()``.  ``nhwc4`` (j = 0 only): the input already in
-    the stem conv's 4-channel NHWC form, in place of ``xs``."""
-    from . import _lib
-    from .convnext_features import LayerNorm2d, stochastic_depth_row_scales
-    feats, cache = m._net.features, m._net._hip_pack
-    saved = []
-    if j == 0:       # trainable stem (the "train everything" epochs): conv k4 s4 and LN unfused
-        conv, ln = feats[0][0], feats[0][1]
-        if conv.kernel_size != (4, 4) or conv.stride != (4, 4) or conv.in_channels != 3 or conv.padding != (0, 0):
-            raise RuntimeError(f"HIP training step: unsupported ConvNeXt stem {conv}")
-        xp = K.nchw_to_nhwc(xs.contiguous(), 4) if nhwc4 is None else nhwc4      # channels zero-padded 3 -> 4
-        wp = packed(cache, "0.conv.train", conv.weight,
-                    lambda w: torch.nn.functional.pad(w.permute(0, 2, 3, 1), (0, 1)))
-        z = K.conv2d_nhwc(xp, wp, conv.bias, 4, 0, _lib.EPI_BIAS)
-        h = K.layernorm(z, ln.weight, ln.bias)
-        saved.append(("stem", feats[0], "0", dict(x=xp, z=z)))
-        start = 1
-    else:
-        h = convnext_features_hip(feats[:j], xs, cache, sd_keep)
-        start = j
-    scales = {} if eval_mode else stochastic_depth_row_scales(feats, sd_keep, xs.shape[0], xs.device)
-    bid = len(_cnblocks(feats[:start]))
-    for idx in range(start, len(feats)):
-        mod = feats[idx]
-        if len(mod) > 0 and isinstance(mod[0], CNBlock):
-            for jb, blk in enumerate(mod):
-                dw, ln, l1, l2 = blk.block[0], blk.block[2], blk.block[3], blk.block[5]
-                b, hh, ww, c = h.shape
-                key = f"{idx}.{jb}"
-                wdw = packed(cache, key + ".dw", dw.weight, lambda w: w.reshape(c, 49).t())
-                z = K.dwconv7_plain(h, wdw, dw.bias)
-                t = K.layernorm(z, ln.weight, ln.bias)
-                h1 = K.linear(t.view(-1, c), l1.weight, l1.bias, _lib.EPI_BIAS)
-                g = K.gelu_fwd(h1)
-                y2 = K.linear(g, l2.weight, l2.bias, _lib.EPI_BIAS)
-                rs = scales.get(bid) if blk.stochastic_depth.p > 0.0 and not eval_mode else None
-                out = K.resid_scale(h.view(-1, c), y2, blk.layer_scale.view(-1), rs, hh * ww).view(b, hh, ww, c)
-                saved.append(("block", blk, key, dict(x=h, z=z, t=t, h1=h1, g=g, y2=y2, rs=rs, key=key)))
-                h = out
-                bid += 1
-        elif len(mod) == 2 and isinstance(mod[0], LayerNorm2d) and isinstance(mod[1], nn.Conv2d):
-            ln, conv = mod[0], mod[1]
-            t = K.layernorm(h, ln.weight, ln.bias)
-            wp = packed(cache, f"{idx}.conv", conv.weight, lambda w: w.permute(0, 2, 3, 1))
-            out = K.conv2x2(t, wp, conv.bias, conv.stride[0])
-            saved.append(("down", mod, f"{idx}.conv", dict(x=h, t=t)))
-            h = out
-        else:
-            raise RuntimeError(f"HIP training step: unsupported ConvNeXt features entry {idx}")
-    return h, saved
-
-
-def _block_backward(blk: CNBlock, sv: dict, dy: Tensor, param_grads: bool = True, cache: Optional[dict] = None) -> Tensor:
-    """Gradients of one CNBlock (written to the parameters' .grad); returns d input [B,H,W,C].
-    ``param_grads=False``: the input gradient only -- no weight-gradient kernel runs, no .grad is
-    touched, the reductions the kernels must write (d_ls, d_gamma, ...) go to scratch and the saved
-    activations are left as they are; ``cache`` then keeps the transposed / flipped weights."""
-    from . import _lib
-    dw, ln, l1, l2 = blk.block[0], blk.block[2], blk.block[3], blk.block[5]
-    x = sv["x"]
-    b, hh, ww, c = x.shape
-    dev = x.device
-    d_ls, d_b2 = torch.empty(c, device=dev), torch.empty(c, device=dev)
-    dyv = dy.reshape(-1, c)
-    dy2 = K.ls_backward(dyv, sv["y2"], blk.layer_scale.view(-1), sv["rs"], hh * ww, d_ls, d_b2)
-    d_lnw, d_lnb = torch.empty(c, device=dev), torch.empty(c, device=dev)
-    if param_grads:
-        _set_grad(blk.layer_scale, d_ls)
-        _set_grad(l2.bias, d_b2)
-        if l2.weight.requires_grad:
-            _set_grad(l2.weight, K.wgrad(dy2, sv["g"]))
-        dh1 = K.linear(dy2, l2.weight.t().contiguous(), None, _lib.EPI_GELU_BWD, r=sv["h1"])
-        if l1.weight.requires_grad:
-            _set_grad(l1.weight, K.wgrad(dh1, sv["t"].view(-1, c)))
-        if l1.bias.requires_grad:
-            _set_grad(l1.bias, K.colsum(dh1))
-        dt = K.linear(dh1, l1.weight.t().contiguous(), None, _lib.EPI_NONE)
-        dz = K.ln_backward(sv["z"].view(-1, c), dt, ln.weight, d_lnw, d_lnb, want_dz=True).view(b, hh, ww, c)
-        _set_grad(ln.weight, d_lnw)
-        _set_grad(ln.bias, d_lnb)
-        dwp, d_dwb = torch.empty(49, c, device=dev), torch.empty(c, device=dev)
-        K.dwconv7_wgrad(dz, x, dwp, d_dwb)
-        _set_grad(dw.weight, dwp.t())
-        _set_grad(dw.bias, d_dwb)
-        wflip = dw.weight.detach().flip(2, 3).reshape(c, 49).t().contiguous()
-    else:
-        cache = {} if cache is None else cache
-        key = sv["key"]
-        w2t = packed(cache, key + ".l2.t", l2.weight, lambda w: w.t())
-        w1t = packed(cache, key + ".l1.t", l1.weight, lambda w: w.t())
-        dh1 = K.linear(dy2, w2t, None, _lib.EPI_GELU_BWD, r=sv["h1"])
-        dt = K.linear(dh1, w1t, None, _lib.EPI_NONE)
-        dz = K.ln_backward(sv["z"].view(-1, c), dt, ln.weight.detach(), d_lnw, d_lnb, want_dz=True).view(b, hh, ww, c)
-        wflip = packed(cache, key + ".dw.flip", dw.weight, lambda w: w.flip(2, 3).reshape(c, 49).t())
-    dx = dy.reshape(b, hh, ww, c)                    # residual path; the branch's input grad adds in place
-    K.dwconv7_plain(dz, wflip, None, out=dx, accumulate=True)
-    return dx
-
-
-def _stem_backward(mod: nn.Sequential, sv: dict, dy: Tensor) -> None:
-    """Stem backward (Conv2d(3, 96, 4, 4) + LayerNorm2d): LN gradients, then the conv's
-    weight (stride-4 patch gather, MFMA) and bias gradients; the input images need none."""
-    conv, ln = mod[0], mod[1]
-    z = sv["z"]
-    b, h, w, c = z.shape
-    dev = z.device
-    d_lnw, d_lnb = torch.empty(c, device=dev), torch.empty(c, device=dev)
-    need_dz = conv.weight.requires_grad or (conv.bias is not None and conv.bias.requires_grad)
-    dz = K.ln_backward(z.view(-1, c), dy.reshape(-1, c), ln.weight, d_lnw, d_lnb, want_dz=need_dz)
-    _set_grad(ln.weight, d_lnw)
-    _set_grad(ln.bias, d_lnb)
-    if not need_dz:
-        return
-    if conv.weight.requires_grad:
-        gp = torch.empty(c, 4 * 4 * 4, device=dev)
-        K.wgrad_conv(dz.view(b, h, w, c), sv["x"], 4, 4, 4, gp)
-        _set_grad(conv.weight, gp.view(c, 4, 4, 4)[..., :3].permute(0, 3, 1, 2))
-    if conv.bias is not None and conv.bias.requires_grad:
-        _set_grad(conv.bias, K.colsum(dz))
-
-
-def _down_backward(mod: nn.Sequential, sv: dict, dy: Tensor, need_dx: bool, param_grads: bool = True) -> Optional[Tensor]:
-    """LayerNorm2d + Conv2d(k2, stride 1|2) backward; returns d input when ``need_dx``.
-    ``param_grads=False``: the input gradient only (no weight-gradient kernel, no .grad)."""
-    from . import _lib
-    ln, conv = mod[0], mod[1]
-    x, t = sv["x"], sv["t"]
-    b, h, w, cin = t.shape
-    cout, stride = conv.out_channels, conv.stride[0]
-    if param_grads and conv.weight.requires_grad:
-        gp = torch.empty(cout, 4 * cin, device=t.device)
-        K.wgrad_conv2x2(dy, t, stride, gp)
-        _set_grad(conv.weight, gp.view(cout, 2, 2, cin).permute(0, 3, 1, 2))
-    if param_grads and conv.bias is not None and conv.bias.requires_grad:
-        _set_grad(conv.bias, K.colsum(dy.reshape(-1, cout)))
-    if not (need_dx or (param_grads and (ln.weight.requires_grad or ln.bias.requires_grad))):
-        return None
-    wd = conv.weight.detach()
-    if stride == 1:        # transposed conv = conv of dy (pad 1) with the flipped, transposed taps
-        dt = K.conv2d_nhwc(dy.contiguous(), wd.permute(1, 2, 3, 0).flip(1, 2).contiguous(), None, 1, 1,
-                           _lib.EPI_NONE)
-    else:                  # stride 2: taps do not overlap -> one GEMM, then place the 2x2 blocks
-        oh, ow = dy.shape[1], dy.shape[2]
-        gm = K.linear(dy.reshape(-1, cout), wd.permute(2, 3, 1, 0).reshape(4 * cin, cout).contiguous(), None,
-                      _lib.EPI_NONE)
-        dt = torch.zeros(b, h, w, cin, device=t.device)
-        dt[:, :2 * oh, :2 * ow] = gm.view(b, oh, ow, 2, 2, cin).permute(0, 1, 3, 2, 4, 5).reshape(b, 2 * oh, 2 * ow, cin)
-    d_lnw, d_lnb = torch.empty(cin, device=t.device), torch.empty(cin, device=t.device)
-    dx = K.ln_backward(x.reshape(-1, cin), dt.reshape(-1, cin), ln.weight.detach(), d_lnw, d_lnb, want_dz=need_dx)
-    if param_grads:
-        _set_grad(ln.weight, d_lnw)
-        _set_grad(ln.bias, d_lnb)
-    return None if dx is None else dx.view(b, h, w, cin)
-
-
-def _addon_suffix_backward(m: nn.Module, feats: Tensor, saved: list, d_logits: Tensor,
-                           param_grads: bool = True) -> Optional[Tensor]:
+def _addon_backward(m: nn.Module, feats: Tensor, d_logits: Tensor, param_grads: bool = True) -> Tensor:
     """Backward from d logits (before the prototype softmax) through the add-on (1x1 conv when
-    present) and the saved backbone suffix; every parameter with requires_grad gets .grad.
-    ``param_grads=False``: the input-gradient chain only -- no weight-gradient kernel, no .grad,
-    ``saved`` is left intact (it serves several backward passes) -- and the gradient at the input of
-    the first saved entry comes back: for a saved stem that is d (stem LayerNorm output), the
-    caller's to take through the stem (attribution._stem_dx)."""
-    from . import _lib
+    present) -> d features, the backbone's ``backward`` to take on; the conv's weight and bias get
+    their .grad.  ``param_grads=False``: the input gradient only -- no weight-gradient kernel, no .grad."""
     mods = list(m._add_on) if isinstance(m._add_on, nn.Sequential) else [m._add_on]
-    if len(mods) == 2:                           # 1x1 prototype conv before the softmax
-        conv = mods[0]
-        bsz, hh, ww, cf = feats.shape
-        pn = conv.out_channels
-        dl = d_logits.view(-1, pn)
-        if param_grads and conv.weight.requires_grad:
-            _set_grad(conv.weight, K.wgrad(dl, feats.view(-1, cf)))
-        if param_grads and conv.bias is not None and conv.bias.requires_grad:
-            _set_grad(conv.bias, K.colsum(dl))
-        dy = K.linear(dl, conv.weight.detach().view(pn, cf).t().contiguous(), None, _lib.EPI_NONE)
-        dy = dy.view(bsz, hh, ww, cf)
-    else:
-        dy = d_logits
-    if saved and saved[0][0] == "resnet":
-        from . import resnet_train
-        resnet_train.backward(m._net, saved[0][3], dy)
-        saved.clear()
-        return
-    if not param_grads:
-        cache = m._net._hip_pack
-        for i in range(len(saved) - 1, -1, -1):
-            kind, mod, _, sv = saved[i]
-            if kind == "block":
-                dy = _block_backward(mod, sv, dy, param_grads=False, cache=cache)
-            elif kind == "down":
-                dy = _down_backward(mod, sv, dy, need_dx=True, param_grads=False)
-        return dy
-    for i in range(len(saved) - 1, -1, -1):
-        kind, mod, _, sv = saved[i]
-        if kind == "block":
-            dy = _block_backward(mod, sv, dy)
-        elif kind == "stem":
-            _stem_backward(mod, sv, dy)
-        else:
-            dy = _down_backward(mod, sv, dy, need_dx=i > 0)
-        saved[i] = None                          # free the activations as we go
-    return None
+    if len(mods) != 2:                           # no 1x1 prototype conv before the softmax
+        return d_logits
+    conv = mods[0]
+    bsz, hh, ww, cf = feats.shape
+    pn = conv.out_channels
+    dl = d_logits.view(-1, pn)
+    if param_grads and conv.weight.requires_grad:
+        _set_grad(conv.weight, K.wgrad(dl, feats.view(-1, cf)))
+    if param_grads and conv.bias is not None and conv.bias.requires_grad:
+        _set_grad(conv.bias, K.colsum(dl))
+    dy = K.linear(dl, conv.weight.detach().view(pn, cf).t().contiguous(), None, _lib.EPI_NONE)
+    return dy.view(bsz, hh, ww, cf)
 
 
 # ------------------------------------------------------------------------------------------
@@ -672,20 +426,18 @@ def _train_step(m: nn.Module, xs1: Tensor, xs2: Tensor, ys: Tensor, *, phase: st
     the global batch's; None: they are the whole batch.  It is asked in five places, marked (1) .. (5)."""
     count, finetune = hasattr(m, "_max_count"), phase == "finetune"
     head_backward = _count_head_backward if count else _pipnet_head_backward
-    cls = m._classification
+    cls, backbone = m._classification, _backbone(m)
     xs = torch.cat([xs1, xs2])
     if shard is not None:
         sd_keep = shard.masks(sd_keep)                                    # (1) the rank's rows of the global masks
     elif sd_keep is None:
-        sd_keep = _sd_masks(m, xs.shape[0], generator)
+        sd_keep = backbone.sd_masks(m._net, xs.shape[0], generator)
     w_align, w_tanh, w_class = w
     loss_args = (cls.normalization_multiplier, enforce_weight_sparsity, tanh_loss_coeff, w_align, w_tanh, w_class,
                  phase)
     with torch.no_grad():
-        if finetune:
-            feats, suffix = _backbone_train_forward(m, xs, sd_keep), None
-        else:
-            feats, suffix = _backbone_forward_saving(m, xs, trainable_suffix_start(m), sd_keep)
+        start = None if finetune else backbone.trainable_start(m._net)    # finetune keeps no activations
+        feats, suffix = backbone.train_forward(m._net, xs, start, sd_keep)
         if count:                                                         # (2) the draw of the rows' global place
             hd = _count_head(m, feats, None if shard is None else shard.gumbel())
         else:
@@ -699,7 +451,7 @@ def _train_step(m: nn.Module, xs1: Tensor, xs2: Tensor, ys: Tensor, *, phase: st
                                  pooled_all=pooled_all)                   # (4)
         del hd
         if not finetune:
-            _addon_suffix_backward(m, feats, suffix, d_logits)
+            backbone.backward(m._net, suffix, _addon_backward(m, feats, d_logits))
         if shard is not None:                                             # (5) the ranks' gradients, summed
             shard.reduce_gradients(phase, optimizer_classifier, optimizer_net)
         if step_optimizers:
@@ -745,7 +497,7 @@ def hip_train_step(net: nn.Module, xs1: Tensor, xs2: Tensor, ys: Tensor, optimiz
     and optimizer_net steps (AdamW on the device) and the sparsity clamps.  Returns the
     loss-kernel stats without synchronising."""
     m = _inner(net)
-    if trainable_suffix_start(m) >= _backbone_units(m):
+    if trainable_suffix_start(m) >= _backbone(m).units(m._net):
         raise NotImplementedError("HIP training step: no trainable backbone parameter (use the finetune step)")
     return _train_step(m, xs1, xs2, ys, phase="pretrain" if pretrain else "train", optimizer_net=optimizer_net,
                        optimizer_classifier=optimizer_classifier, w=_loss_weights(pretrain, epoch, nr_epochs),
@@ -766,7 +518,7 @@ def hip_count_train_step(net: nn.Module, xs1: Tensor, xs2: Tensor, ys: Tensor, o
     (+ the align term) -> soft-max backward scaled by 1/tau -> add-on -> suffix; AdamW steps
     and the sparsity clamps as ``hip_train_step``.  Returns the loss-kernel stats."""
     m = _inner(net)
-    if trainable_suffix_start(m) >= _backbone_units(m):
+    if trainable_suffix_start(m) >= _backbone(m).units(m._net):
         raise NotImplementedError("HIP count training step: no trainable backbone parameter (use the finetune step)")
     return _train_step(m, xs1, xs2, ys, phase="pretrain" if pretrain else "train", optimizer_net=optimizer_net,
                        optimizer_classifier=optimizer_classifier, w=_loss_weights(pretrain, epoch, nr_epochs),

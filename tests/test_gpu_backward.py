@@ -183,3 +183,46 @@ def test_head_backward_matches_autograd(gpu, bh, hw, p, k, mode):
     proto_n = proto.detach().float().permute(0, 2, 3, 1).contiguous().to(gpu)
     dl = K.head_backward(proto_n, pooled.detach().float().to(gpu), d_out, w.to(gpu), wa, wt_)
     torch.testing.assert_close(dl.cpu().double().permute(0, 3, 1, 2), ld.grad, rtol=2e-4, atol=1e-6)
+
+
+def test_cnblock_backward_dx_is_the_same_with_and_without_param_grads(gpu):
+    """One CNBlock (C = 96, B = 2, 8 x 8 map, stochastic depth dropping image 1) as convnext_train's
+    train_forward saves it: ``_block_backward`` returns bitwise the same d input with param_grads=True
+    (training: weight-gradient launches, temporaries for the transposed / flipped weights) and with
+    param_grads=False on a fresh cache (attribution) -- both issue the same dx launches on the same
+    operands, so this is equality, not a tolerance.  Without param_grads no .grad is set; neither
+    mode touches the saved activations.  The training mode adds into ``dy`` in place, hence the clones."""
+    import types
+
+    import torch.nn as nn
+
+    from count_pipnet_amd import convnext_train as CT
+    from count_pipnet_amd.convnext_features import CNBlock, Conv2dNormActivation
+    g = _g(96)
+    blk = CNBlock(96, layer_scale=0.5, stochastic_depth_prob=0.5)
+    model = types.SimpleNamespace(features=nn.Sequential(Conv2dNormActivation(3, 96, 4, 4), nn.Sequential(blk)).to(gpu),
+                                  _hip_pack={})
+    with torch.no_grad():
+        for p in model.features.parameters():
+            p.copy_(torch.randn(p.shape, generator=g) * (0.1 if p.dim() > 1 else 0.5))
+        xs = torch.randn(2, 3, 32, 32, generator=g).to(gpu)
+        feats, saved = CT.train_forward(model, xs, 1, {0: torch.tensor([True, False])})
+        assert tuple(feats.shape) == (2, 8, 8, 96) and len(saved) == 1
+        entry = saved[0]
+        assert entry.kind == "block" and entry.mod is blk and entry.key == "1.0"
+        assert entry.act["rs"].tolist() == [2.0, 0.0]                       # keep / (1 - p): image 1 is dropped
+        kept = {k: v.clone() for k, v in entry.act.items() if torch.is_tensor(v)}
+        assert sorted(kept) == ["g", "h1", "rs", "t", "x", "y2", "z"]
+        dy = torch.randn(2, 8, 8, 96, generator=g).to(gpu)
+        dx_train = CT._block_backward(blk, entry.act, dy.clone())
+        assert all(p.grad is not None and p.grad.shape == p.shape for p in blk.parameters())
+        for p in blk.parameters():
+            p.grad = None
+        cache = {}
+        dx_only = CT._block_backward(blk, entry.act, dy.clone(), param_grads=False, cache=cache, key=entry.key)
+    assert torch.equal(dx_train, dx_only)
+    assert all(p.grad is None for p in blk.parameters())
+    assert sorted(k for k, _ in cache) == ["1.0.dw.flip", "1.0.l1.t", "1.0.l2.t"]
+    assert all(torch.equal(entry.act[k], v) for k, v in kept.items())
+    # the dropped image's branch passes no gradient: its d input is the residual path's alone
+    assert torch.equal(dx_only[1], dy[1]) and not torch.equal(dx_only[0], dy[0])
