@@ -289,7 +289,26 @@ def _cnblock_s3(blk: CNBlock, h: Tensor, cache: Dict, key: str) -> Tensor:
     return h
 
 
-PRECISIONS = ("fp32", "bf16x3")
+def _cnblock_bf16(blk: CNBlock, h: Tensor, cache: Dict, key: str) -> Tensor:
+    """One CNBlock in place on NHWC fp32 ``h`` with plain bf16 GEMMs (precision "bf16"): dwconv+LN
+    rounds once to bf16, Linear1 (+GELU, fp32) rounds once to a bf16 hidden tensor, Linear2 adds
+    layer_scale * (.) into the fp32 residual stream -- one bf16 product per multiply, RNE-bf16
+    weights, fp32 accumulation.  Every stage runs this unfused pair (no fused bf16 MLP kernel)."""
+    dw, ln, l1, l2 = blk.block[0], blk.block[2], blk.block[3], blk.block[5]
+    b, hh, ww, c = h.shape
+    if dw.kernel_size != (7, 7) or dw.padding != (3, 3) or dw.groups != c or dw.stride != (1, 1):
+        raise RuntimeError(f"CNBlock {key}: unsupported depthwise conv {dw}")
+    hid = l1.out_features
+    wdw = packed(cache, key + ".dw", dw.weight, lambda w: w.reshape(c, 49).t())
+    w1 = packed(cache, key + ".fc1.bf16", l1.weight, lambda w: K.pack_conv_weight_bf16(w.view(hid, 1, 1, c)))
+    w2 = packed(cache, key + ".fc2.bf16", l2.weight, lambda w: K.pack_conv_weight_bf16(w.view(c, 1, 1, hid)))
+    t = K.dwconv7_ln_bf16(h, wdw, dw.bias, ln.weight, ln.bias)
+    u = K.conv_bf16_mix(t, w1, 1, 1, l1.bias, 1, 0, _lib.EPI_BIAS_GELU)
+    K.conv_bf16_mix(u, w2, 1, 1, l2.bias, 1, 0, _lib.EPI_F32_RESID, scale=blk.layer_scale.view(-1), r=h, out=h)
+    return h
+
+
+PRECISIONS = ("fp32", "bf16x3", "bf16")
 
 
 def stochastic_depth_row_scales(features: nn.Sequential, sd_keep: Dict[int, object], batch: int,
@@ -336,11 +355,14 @@ def convnext_features_hip_steps(features: nn.Sequential, x: Tensor, cache: Dict,
     ``sd_keep``: train-mode stochastic depth, block id (0..17 in module order) -> per-sample
     keep mask for every block with p > 0 (eval / None: no stochastic depth).
     ``precision``: "fp32" (exact fp32 MFMA GEMMs) or "bf16x3" (the CNBlock Linears and the
-    downsample convs as split-bf16 GEMMs, include/pipnet_amd.h; inference only -- train-mode
-    stochastic depth always runs fp32)."""
+    downsample convs as split-bf16 GEMMs, include/pipnet_amd.h) or "bf16" (the same layers as plain
+    bf16 GEMMs on bf16 activations: one product per multiply, fp32 accumulation and residual stream;
+    error budget in DESIGN.md section 4).  Both are inference only -- train-mode stochastic depth
+    always runs fp32."""
     if precision not in PRECISIONS:
         raise ValueError(f"unknown HIP precision {precision!r} (expected one of {PRECISIONS})")
     s3 = precision == "bf16x3" and sd_keep is None
+    bf = precision == "bf16" and sd_keep is None
     K.require_device(x, "network input")
     x = x.contiguous()
     h = None
@@ -358,6 +380,8 @@ def convnext_features_hip_steps(features: nn.Sequential, x: Tensor, cache: Dict,
             for j, blk in enumerate(mod):
                 if s3:
                     h = _cnblock_s3(blk, h, cache, f"{name}.{j}")
+                elif bf:
+                    h = _cnblock_bf16(blk, h, cache, f"{name}.{j}")
                 else:
                     h = _cnblock_hip(blk, h, cache, f"{name}.{j}", None if scales is None else scales.get(bid))
                 bid += 1
@@ -371,6 +395,11 @@ def convnext_features_hip_steps(features: nn.Sequential, x: Tensor, cache: Dict,
                 wp = packed(cache, name + ".conv.s3", conv.weight,
                             lambda w: K.split_planes_weight(w.permute(0, 2, 3, 1)))
                 h = K.conv_s3(t3, wp, 2, 2, conv.out_channels, conv.bias, conv.stride[0], 0, _lib.EPI_F32_BIAS)
+            elif bf and conv.in_channels % 32 == 0:
+                t = K.layernorm_bf16(h, ln.weight, ln.bias)
+                wp = packed(cache, name + ".conv.bf16", conv.weight,
+                            lambda w: K.pack_conv_weight_bf16(w.permute(0, 2, 3, 1)))
+                h = K.conv_bf16_mix(t, wp, 2, 2, conv.bias, conv.stride[0], 0, _lib.EPI_F32_BIAS)
             else:
                 t = K.layernorm(h, ln.weight, ln.bias)
                 wp = packed(cache, name + ".conv", conv.weight, lambda w: w.permute(0, 2, 3, 1))

@@ -255,7 +255,7 @@ def detect_output_channels(features: nn.Module) -> int:
 def get_count_network(num_classes: int, args: argparse.Namespace, max_count: int = 3, use_ste: bool = True,
                       device=None):
     """count_pipnet.py:324-436 -> (CountPIPNet, num_prototypes).  Optional ``args.hip_dtype``
-    ("fp32" | "bf16x3") selects the HIP compute dtype of the ConvNeXt backbone."""
+    ("fp32" | "bf16" | "bf16x3") selects the HIP compute dtype of the backbone (pipnet.set_hip_dtype)."""
     if args.net not in base_architecture_to_features:
         raise ValueError(f"Network '{args.net}' is not supported. "
                          f"Supported networks: {list(base_architecture_to_features)}")

@@ -70,6 +70,13 @@ int conv_variant(int M, int N, bool pp_ok, bool s3 = false, int Kv = 0) {
 bool is_s3_epi(int epi) {
   return epi == PIPNET_EPI_S3_GELU || epi == PIPNET_EPI_F32_BIAS || epi == PIPNET_EPI_F32_RESID;
 }
+// the ConvNeXt epilogues of the plain bf16 build (pipnet_conv2d_nhwc_bf16_mix): the two fp32-output
+// forms of the split GEMM and the one-rounding bf16 GELU
+bool is_mix_epi(int epi) {
+  return epi == PIPNET_EPI_BIAS_GELU || epi == PIPNET_EPI_F32_BIAS || epi == PIPNET_EPI_F32_RESID;
+}
+// either family: served by tiles 0 / 4 / 5 / 7 only
+bool is_cnx_epi(int epi) { return is_s3_epi(epi) || epi == PIPNET_EPI_BIAS_GELU; }
 
 // 3x3 / stride 1 / pad 1 convs with N >= 256 whose halo fits the kernel's 320 LDS rows
 // (256 + 2W + 2): the LDS-halo ping-pong kernel (tile 8) replaces tile 5 -- a per-layer
@@ -80,12 +87,12 @@ bool halo64_ok(const ConvParams& p, int epi) {
   const bool shape = (p.Cin == 64 && p.N == 64 && p.Wd <= hsm::Shape<64>::MAX_W) ||
                      (p.Cin == 128 && p.N == 128 && p.Wd <= hsm::Shape<128>::MAX_W);
   return p.KW == 3 && p.Kv == 9 * p.Cin && p.stride == 1 && p.pad == 1 && p.OH == p.H && p.OW == p.Wd &&
-         p.seg == 0 && shape && !is_s3_epi(epi);
+         p.seg == 0 && shape && !is_cnx_epi(epi);
 }
 
 bool halo_ok(const ConvParams& p, int epi) {
   return p.KW == 3 && p.Kv == 9 * p.Cin && p.stride == 1 && p.pad == 1 && p.OH == p.H && p.OW == p.Wd &&
-         p.seg == 0 && p.Cin % 64 == 0 && p.Wd <= 31 && p.N >= 256 && !is_s3_epi(epi) &&
+         p.seg == 0 && p.Cin % 64 == 0 && p.Wd <= 31 && p.N >= 256 && !is_cnx_epi(epi) &&
          (int64_t)p.M * p.Cin < ((int64_t)1 << 31);        // 32-bit halo source offsets
 }
 // B fragments of 16 columns per wave.  Only the 256-wide tile is dispatched: the 64 / 128-wide
@@ -113,20 +120,24 @@ int plan_conv(const ConvParams& p, int epi, int v) {
   const bool hk = ALOAD == ALOAD_CONV && halo_ok(p, epi);
   const bool h64 = ALOAD == ALOAD_CONV && halo64_ok(p, epi);
   // 1x1 convs with N % 256 == 0: the persistent ping-pong tile (9), same K order as tile 5
-  const bool pk = ALOAD == ALOAD_DENSE && pp_ok && p.N % 256 == 0 && !is_s3_epi(epi);
+  const bool pk = ALOAD == ALOAD_DENSE && pp_ok && p.N % 256 == 0 && !is_cnx_epi(epi);
   if (v < 0) {
-    v = conv_variant(p.M, p.N, pp_ok, is_s3_epi(epi), p.Kv > 0 ? p.Kv : p.K);
+    // the plain bf16 ConvNeXt GEMMs (no split planes: seg == 0) take the split GEMM's per-layer tile:
+    // its rule sees the layer's K as the split form carries it, three segments per tap
+    const int kv = p.Kv > 0 ? p.Kv : p.K;
+    v = conv_variant(p.M, p.N, pp_ok, is_cnx_epi(epi), is_cnx_epi(epi) && p.seg == 0 ? 3 * kv : kv);
     if (hk) v = 8;
     else if (h64 && H64_AUTO) v = 11;
     else if (v == 5 && pk) v = 9;
   }
+  if (is_cnx_epi(epi) && v != 0 && v != 4 && v != 5 && v != 7) return -1;
   if (v > 11 || v == 10 || (v == 11 && !h64) || ((v == 5 || v == 7) && !pp_ok) || (v == 8 && !hk) || (v == 9 && !pk)) return -1;
   return v;
 }
 
 using ConvRef = pipnet::KernelRef<ConvParams>;
 #define PIPNET_BF16_EPIS PIPNET_EPI_NONE, PIPNET_EPI_BIAS, PIPNET_EPI_BIAS_RELU, PIPNET_EPI_BIAS_RESID_RELU
-#define PIPNET_S3_EPIS PIPNET_EPI_S3_GELU, PIPNET_EPI_F32_BIAS, PIPNET_EPI_F32_RESID
+#define PIPNET_S3_EPIS PIPNET_EPI_S3_GELU, PIPNET_EPI_F32_BIAS, PIPNET_EPI_F32_RESID, PIPNET_EPI_BIAS_GELU
 
 // What a launch of requested tile v runs: v becomes plan_conv's answer, the result its instantiation for
 // epilogue epi -- empty when the tile cannot run this conv or has none for epi.
@@ -160,7 +171,7 @@ ConvRef select_conv(const ConvParams& p, int epi, int& v) {
     return for_value<ConvRef, PIPNET_BF16_EPIS, PIPNET_S3_EPIS>(epi, [](auto e) -> ConvRef {
       return PIPNET_KREF(pipnet_bf16::conv_bf16_pp_kernel, decltype(e)::value, ALOAD, 4, 0, 2);
     });
-  if (is_s3_epi(epi))     // split-bf16 epilogues: only the tiles the automatic choice picks for N < 256 (0 and 4)
+  if (is_cnx_epi(epi))    // split-bf16 / ConvNeXt bf16 epilogues: only the tiles the automatic choice picks for N < 256 (0 and 4)
     return for_value<ConvRef, PIPNET_S3_EPIS>(epi, [&](auto e) -> ConvRef {
       constexpr int E = decltype(e)::value;
       if (v == 4 && p.N % 128) return PIPNET_KREF_T(pipnet_bf16::conv_bf16_kernel, CfgM4, E, ALOAD, 2, true);
@@ -356,6 +367,33 @@ int conv_s3_shape(ConvParams& p, bool& dense, int B, int H, int W, int Cin, int 
   return PIPNET_OK;
 }
 
+// The same for pipnet_conv2d_nhwc_bf16_mix: plain bf16 A (no split planes), weights packed as
+// pipnet_pack_conv_weight_bf16 makes them (K padded to KPAD with zeros).  Cin % 32 == 0 keeps every
+// 32-deep K-tile inside one tap and the valid K a whole number of K-tiles (the ping-pong tiles re-read
+// the last valid K-tile against the zero weight padding).
+int conv_mix_shape(ConvParams& p, bool& dense, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
+                   int pad, int epilogue, int tile) {
+  if (B < 0 || H <= 0 || W <= 0 || Cin <= 0 || (Cin % 32) || Cout <= 0 || (Cout & 7) || KH <= 0 || KW <= 0 ||
+      stride <= 0 || pad < 0)
+    return PIPNET_ERR_ARG;
+  if (!is_mix_epi(epilogue)) return PIPNET_ERR_ARG;
+  if (tile != -1 && tile != 0 && tile != 4 && tile != 5 && tile != 7) return PIPNET_ERR_ARG;
+  const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
+  if (OH <= 0 || OW <= 0) return PIPNET_ERR_ARG;
+  if ((int64_t)B * OH * OW >= (int64_t)1 << 31 || (int64_t)KH * KW * Cin >= (int64_t)1 << 30) return PIPNET_ERR_ARG;
+  p.ldr = Cout;
+  p.ldc = Cout;
+  p.M = B * OH * OW; p.N = Cout;
+  p.Kv = KH * KW * Cin;
+  p.K = (p.Kv + KPAD - 1) / KPAD * KPAD;
+  p.H = H; p.Wd = W; p.Cin = Cin; p.OH = OH; p.OW = OW; p.stride = stride; p.KW = KW; p.pad = pad;
+  p.Cinp = Cin;
+  p.seg = 0;
+  dense = KH == 1 && KW == 1 && stride == 1 && pad == 0;
+  if (dense) p.lda = Cin;
+  return PIPNET_OK;
+}
+
 }  // namespace
 
 extern "C" int pipnet_conv2d_nhwc_bf16_tile(const void* x, int B, int H, int W, int Cin, const void* w_packed,
@@ -517,6 +555,40 @@ extern "C" int pipnet_conv2d_nhwc_s3_label(int B, int H, int W, int Cin, int Cou
   ConvParams p{};
   bool dense = false;
   if (conv_s3_shape(p, dense, B, H, W, Cin, Cout, KH, KW, stride, pad, epilogue, tile)) return -PIPNET_ERR_ARG;
+  return pipnet::write_label(dense ? select_conv<ALOAD_DENSE>(p, epilogue, tile)
+                                   : select_conv<ALOAD_CONV>(p, epilogue, tile), buf, cap);
+}
+
+// Plain bf16 conv / linear of the ConvNeXt backbone (include/pipnet_amd.h): one bf16 product per
+// multiply on the split GEMM's tiles, with its fp32-output epilogues or the one-rounding bf16 GELU.
+extern "C" int pipnet_conv2d_nhwc_bf16_mix(const void* x, int B, int H, int W, int Cin, const void* w_packed,
+                                           const float* bias, const float* scale, const float* R, int Cout, int KH,
+                                           int KW, int stride, int pad, int epilogue, void* y, int tile, void* stream) {
+  ConvParams p{};
+  bool dense = false;
+  if (const int st = conv_mix_shape(p, dense, B, H, W, Cin, Cout, KH, KW, stride, pad, epilogue, tile)) return st;
+  if (epilogue == PIPNET_EPI_F32_RESID && (!R || !scale)) return PIPNET_ERR_ARG;
+  if (!x || !w_packed || !y) return PIPNET_ERR_ARG;
+  if (!aligned16(x) || !aligned16(w_packed) || !aligned16(y) || (R && !aligned16(R)) || (bias && !aligned16(bias)) ||
+      (scale && !aligned16(scale)))
+    return PIPNET_ERR_ALIGN;
+  if (B == 0) return PIPNET_OK;
+  p.A = reinterpret_cast<const bf16*>(x);
+  p.W = reinterpret_cast<const bf16*>(w_packed);
+  p.bias = bias;
+  p.scale = scale;
+  p.R32 = R;
+  if (epilogue == PIPNET_EPI_BIAS_GELU) p.C = reinterpret_cast<bf16*>(y);
+  else p.Cf = reinterpret_cast<float*>(y);
+  return dense ? launch_conv<ALOAD_DENSE>(p, epilogue, tile, (hipStream_t)stream)
+               : launch_conv<ALOAD_CONV>(p, epilogue, tile, (hipStream_t)stream);
+}
+
+extern "C" int pipnet_conv2d_nhwc_bf16_mix_label(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
+                                                 int pad, int epilogue, int tile, char* buf, int cap) {
+  ConvParams p{};
+  bool dense = false;
+  if (conv_mix_shape(p, dense, B, H, W, Cin, Cout, KH, KW, stride, pad, epilogue, tile)) return -PIPNET_ERR_ARG;
   return pipnet::write_label(dense ? select_conv<ALOAD_DENSE>(p, epilogue, tile)
                                    : select_conv<ALOAD_CONV>(p, epilogue, tile), buf, cap);
 }

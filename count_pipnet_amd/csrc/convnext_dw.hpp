@@ -7,11 +7,18 @@ namespace pipnet_dw {
 constexpr float LN_EPS = 1e-6f;
 constexpr int DW_THREADS = 192;
 
+// Output form of the LayerNorm producers (the S3 template argument; false / true of the older
+// callers are OUT_F32 / OUT_S3): fp32, split-bf16 planes [hi | lo] (2C bf16 per pixel), or the
+// hi plane alone = RNE(fp32 result) to bf16 (C bf16 per pixel, the plain bf16 build).
+enum { OUT_F32 = 0, OUT_S3 = 1, OUT_BF16 = 2 };
+template <int S3>
+__device__ __forceinline__ constexpr int bf16_pitch(int C) { return S3 == OUT_S3 ? 2 * C : C; }
+
 // LayerNorm + store of npix buffered pixels (LDS, C floats each, row-major NP per output
 // row): C/12 lanes per pixel, each owning 3 float4 channel chunks (sl, sl + C/12, sl + C/6),
 // so one store instruction writes C/12 * 16 B contiguous of a pixel (a full 128 B line at
 // C = 96); gamma / beta stay in registers; two-pass mean / variance as torch.
-template <int C, bool S3, int ABL = 0>
+template <int C, int S3, int ABL = 0>
 __device__ __forceinline__ void ln_rows_vec(const float* tile, int npix, int NP, int b, int H, int W, int oy0,
                                             int xblk, const float* __restrict__ lnw, const float* __restrict__ lnb,
                                             void* __restrict__ yv) {
@@ -62,12 +69,12 @@ __device__ __forceinline__ void ln_rows_vec(const float* tile, int npix, int NP,
         if (!(r[0] + r[1] + r[2] + r[3] == -1234.5f)) continue;
       }
       if constexpr (S3) {
-        __bf16* dst = reinterpret_cast<__bf16*>(yv) + opix * 2 * C + c;
+        __bf16* dst = reinterpret_cast<__bf16*>(yv) + opix * bf16_pitch<S3>(C) + c;
         __bf16 hi[4], lo[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) split_bf16(r[e], hi[e], lo[e]);
         *reinterpret_cast<uint2*>(dst) = *reinterpret_cast<const uint2*>(hi);
-        *reinterpret_cast<uint2*>(dst + C) = *reinterpret_cast<const uint2*>(lo);
+        if constexpr (S3 == OUT_S3) *reinterpret_cast<uint2*>(dst + C) = *reinterpret_cast<const uint2*>(lo);
       } else {
         st4(reinterpret_cast<float*>(yv) + opix * C + c, r);
       }
@@ -86,7 +93,7 @@ __device__ __forceinline__ void ln_rows_vec(const float* tile, int npix, int NP,
 // 2 = one stencil FMA per input row instead of 7 x TX, 4 = no input loads (a lane-dependent constant),
 // 8 = no output stores, 16 = no weight loads, 32 = no LDS tile round trip (stale LDS): timing only.
 // (The body is a device function so that the product kernel's name carries no lab parameter.)
-template <int C, int TX, int TY, bool S3, int LPP, int ABL>
+template <int C, int TX, int TY, int S3, int LPP, int ABL>
 __device__ __forceinline__ void dwconv7_ln_body(const float* __restrict__ x, int H, int W,
                                                 const float* __restrict__ wp, const float* __restrict__ bias,
                                                 const float* __restrict__ lnw, const float* __restrict__ lnb,
@@ -218,7 +225,7 @@ __device__ __forceinline__ void dwconv7_ln_body(const float* __restrict__ x, int
     if (!ok) continue;
     const int64_t opix = ((int64_t)b * H + oy) * W + ox;
     if constexpr (S3) {
-      __bf16* dst = reinterpret_cast<__bf16*>(yv) + opix * 2 * C;
+      __bf16* dst = reinterpret_cast<__bf16*>(yv) + opix * bf16_pitch<S3>(C);
 #pragma unroll
       for (int j = 0; j < CJ; ++j) {
         const int c = sl + LPP * j;
@@ -226,7 +233,7 @@ __device__ __forceinline__ void dwconv7_ln_body(const float* __restrict__ x, int
           __bf16 hi, lo;
           split_bf16((vv[j] - mean) * rstd * lnw[c] + lnb[c], hi, lo);
           dst[c] = hi;
-          dst[C + c] = lo;
+          if constexpr (S3 == OUT_S3) dst[C + c] = lo;
         }
       }
     } else {
@@ -240,7 +247,7 @@ __device__ __forceinline__ void dwconv7_ln_body(const float* __restrict__ x, int
   }
 }
 
-template <int C, int TX, int TY, int MINB, bool S3 = false, int LPP = 64>
+template <int C, int TX, int TY, int MINB, int S3 = 0, int LPP = 64>
 __global__ __launch_bounds__(DW_THREADS, MINB) void dwconv7_ln_kernel(const float* __restrict__ x, int H, int W,
                                                                       const float* __restrict__ wp,
                                                                       const float* __restrict__ bias,
@@ -270,7 +277,7 @@ inline int launch_dw_abl(const float* x, int B, int H, int W, const float* wp, c
   return hipGetLastError() == hipSuccess ? PIPNET_OK : PIPNET_ERR_LAUNCH;
 }
 
-template <int C, int TX, int TY, int MINB, bool S3 = false, int LPP = 64>
+template <int C, int TX, int TY, int MINB, int S3 = 0, int LPP = 64>
 inline int launch_dw(const float* x, int B, int H, int W, const float* wp, const float* bias, const float* lnw,
                      const float* lnb, void* y, hipStream_t s) {
   constexpr int NP = (DW_THREADS / (C / 4)) * TX;

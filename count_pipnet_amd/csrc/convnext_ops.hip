@@ -134,7 +134,7 @@ __global__ __launch_bounds__(STEM_T) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 // ---------------------------------------------------------------------------------------
 // row LayerNorm: one wave per row of C channels.
 // ---------------------------------------------------------------------------------------
-template <int NJ, bool S3 = false>
+template <int NJ, int S3 = 0>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int64_t rows, int C,
                                                         const float* __restrict__ w, const float* __restrict__ b,
                                                         void* __restrict__ yv) {
@@ -159,8 +159,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     q = fmaf(d, d, q);
   }
   const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)C + LN_EPS);
-  if constexpr (S3) {                      // split-bf16 planes [hi | lo]
-    __bf16* dst = reinterpret_cast<__bf16*>(yv) + row * 2 * C;
+  if constexpr (S3) {                      // split-bf16 planes [hi | lo], or the hi plane alone
+    __bf16* dst = reinterpret_cast<__bf16*>(yv) + row * pipnet_dw::bf16_pitch<S3>(C);
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const int c = lane + 64 * j;
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
         __bf16 hi, lo;
         split_bf16((v[j] - mean) * rstd * w[c] + b[c], hi, lo);
         dst[c] = hi;
-        dst[C + c] = lo;
+        if constexpr (S3 == pipnet_dw::OUT_S3) dst[C + c] = lo;
       }
     }
   } else {
@@ -236,8 +236,12 @@ extern "C" int pipnet_dwconv7_ln_f32(const float* x, int B, int H, int W, int C,
   }
 }
 
-extern "C" int pipnet_dwconv7_ln_s3(const float* x, int B, int H, int W, int C, const float* w_packed,
-                                    const float* bias, const float* ln_w, const float* ln_b, void* y, void* stream) {
+namespace {
+
+// pipnet_dwconv7_ln_f32's tiles with a bf16 output form (convnext_dw.hpp: OUT_S3 / OUT_BF16).
+template <int OUT>
+int dwconv7_ln_planes(const float* x, int B, int H, int W, int C, const float* w_packed, const float* bias,
+                      const float* ln_w, const float* ln_b, void* y, void* stream) {
   if (B < 0 || H <= 0 || W <= 0) return PIPNET_ERR_ARG;
   if (!x || !w_packed || !bias || !ln_w || !ln_b || !y) return PIPNET_ERR_ARG;
   if (!aligned16(x) || !aligned16(w_packed) || !aligned16(bias) || !aligned16(ln_w) || !aligned16(ln_b) ||
@@ -247,33 +251,56 @@ extern "C" int pipnet_dwconv7_ln_s3(const float* x, int B, int H, int W, int C, 
   hipStream_t s = (hipStream_t)stream;
   switch (C) {
     case 96:
-      if (W > 16 && W <= 32) return pipnet_dw::launch_dw<96, 4, 4, 1, true, 8>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
-      if (W > 32) return pipnet_dw::launch_dw<96, 7, 2, 1, true, 8>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
-      return pipnet_dw::launch_dw<96, 7, 1, 1, true, 8>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
+      if (W > 16 && W <= 32) return pipnet_dw::launch_dw<96, 4, 4, 1, OUT, 8>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
+      if (W > 32) return pipnet_dw::launch_dw<96, 7, 2, 1, OUT, 8>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
+      return pipnet_dw::launch_dw<96, 7, 1, 1, OUT, 8>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
     case 192:
-      if (W > 8 && W <= 16) return pipnet_dw::launch_dw<192, 4, 2, 1, true, 16>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
-      if (W > 16) return pipnet_dw::launch_dw<192, 7, 2, 1, true, 16>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
-      return pipnet_dw::launch_dw<192, 7, 1, 1, true, 16>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
-    case 384: return pipnet_dw::launch_dw<384, 7, 3, 1, true, 32>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
-    case 768: return pipnet_dw::launch_dw<768, 13, 1, 1, true>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
+      if (W > 8 && W <= 16) return pipnet_dw::launch_dw<192, 4, 2, 1, OUT, 16>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
+      if (W > 16) return pipnet_dw::launch_dw<192, 7, 2, 1, OUT, 16>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
+      return pipnet_dw::launch_dw<192, 7, 1, 1, OUT, 16>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
+    case 384: return pipnet_dw::launch_dw<384, 7, 3, 1, OUT, 32>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
+    case 768: return pipnet_dw::launch_dw<768, 13, 1, 1, OUT>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
     default: return PIPNET_ERR_ARG;
   }
 }
 
-extern "C" int pipnet_layernorm_s3(const float* x, int64_t rows, int C, const float* w, const float* b, void* y,
-                                   void* stream) {
+// pipnet_layernorm_f32 with a bf16 output form.
+template <int OUT>
+int layernorm_planes(const float* x, int64_t rows, int C, const float* w, const float* b, void* y, void* stream) {
   if (rows < 0 || C <= 0 || C > 2048 || !x || !w || !b || !y) return PIPNET_ERR_ARG;
   if (rows == 0) return PIPNET_OK;
   const dim3 grid((unsigned)((rows + 3) / 4));
   hipStream_t s = (hipStream_t)stream;
   const int nj = (C + 63) / 64;
-  if (nj <= 2) hipLaunchKernelGGL((layernorm_kernel<2, true>), grid, dim3(256), 0, s, x, rows, C, w, b, y);
-  else if (nj <= 3) hipLaunchKernelGGL((layernorm_kernel<3, true>), grid, dim3(256), 0, s, x, rows, C, w, b, y);
-  else if (nj <= 6) hipLaunchKernelGGL((layernorm_kernel<6, true>), grid, dim3(256), 0, s, x, rows, C, w, b, y);
-  else if (nj <= 12) hipLaunchKernelGGL((layernorm_kernel<12, true>), grid, dim3(256), 0, s, x, rows, C, w, b, y);
-  else hipLaunchKernelGGL((layernorm_kernel<32, true>), grid, dim3(256), 0, s, x, rows, C, w, b, y);
+  if (nj <= 2) hipLaunchKernelGGL((layernorm_kernel<2, OUT>), grid, dim3(256), 0, s, x, rows, C, w, b, y);
+  else if (nj <= 3) hipLaunchKernelGGL((layernorm_kernel<3, OUT>), grid, dim3(256), 0, s, x, rows, C, w, b, y);
+  else if (nj <= 6) hipLaunchKernelGGL((layernorm_kernel<6, OUT>), grid, dim3(256), 0, s, x, rows, C, w, b, y);
+  else if (nj <= 12) hipLaunchKernelGGL((layernorm_kernel<12, OUT>), grid, dim3(256), 0, s, x, rows, C, w, b, y);
+  else hipLaunchKernelGGL((layernorm_kernel<32, OUT>), grid, dim3(256), 0, s, x, rows, C, w, b, y);
   PIPNET_CHECK_LAUNCH();
   return PIPNET_OK;
+}
+
+}  // namespace
+
+extern "C" int pipnet_dwconv7_ln_s3(const float* x, int B, int H, int W, int C, const float* w_packed,
+                                    const float* bias, const float* ln_w, const float* ln_b, void* y, void* stream) {
+  return dwconv7_ln_planes<pipnet_dw::OUT_S3>(x, B, H, W, C, w_packed, bias, ln_w, ln_b, y, stream);
+}
+
+extern "C" int pipnet_dwconv7_ln_bf16(const float* x, int B, int H, int W, int C, const float* w_packed,
+                                      const float* bias, const float* ln_w, const float* ln_b, void* y, void* stream) {
+  return dwconv7_ln_planes<pipnet_dw::OUT_BF16>(x, B, H, W, C, w_packed, bias, ln_w, ln_b, y, stream);
+}
+
+extern "C" int pipnet_layernorm_s3(const float* x, int64_t rows, int C, const float* w, const float* b, void* y,
+                                   void* stream) {
+  return layernorm_planes<pipnet_dw::OUT_S3>(x, rows, C, w, b, y, stream);
+}
+
+extern "C" int pipnet_layernorm_bf16(const float* x, int64_t rows, int C, const float* w, const float* b, void* y,
+                                     void* stream) {
+  return layernorm_planes<pipnet_dw::OUT_BF16>(x, rows, C, w, b, y, stream);
 }
 
 extern "C" int pipnet_layernorm_f32(const float* x, int64_t rows, int C, const float* w, const float* b, float* y,

@@ -247,6 +247,15 @@ PIPNET_DEV void finish_s3(const ConvParams& p, int m, int n, f32x4 x0, f32x4 x1,
   }
 }
 
+// PIPNET_EPI_BIAS_GELU of the plain bf16 ConvNeXt build (pipnet_conv2d_nhwc_bf16_mix): the hi
+// half of finish_s3's S3_GELU -- gelu(x) rounded once (RNE) to bf16, one 16-B store, pitch ldc.
+PIPNET_DEV void finish_gelu_bf16(const ConvParams& p, int m, int n, f32x4 x0, f32x4 x1) {
+  const f32x2 g0 = gelu_pk16(f32x2{x0[0], x0[1]}), g1 = gelu_pk16(f32x2{x0[2], x0[3]});
+  const f32x2 g2 = gelu_pk16(f32x2{x1[0], x1[1]}), g3 = gelu_pk16(f32x2{x1[2], x1[3]});
+  const bf16x8 o = to_bf16x8<false>(f32x4{g0[0], g0[1], g1[0], g1[1]}, f32x4{g2[0], g2[1], g3[0], g3[1]});
+  *reinterpret_cast<bf16x8*>(p.C + (int64_t)m * p.ldc + n) = o;
+}
+
 // Epilogue: each wave re-lays its 32 x (TN*32) fp32 accumulator slice through LDS (rows
 // padded by 4 floats: the 16-B reads of one row's lanes then cover all 64 banks), then every
 // lane finishes 8 consecutive channels of one pixel -- bias, residual (one 16-B bf16
@@ -299,6 +308,10 @@ PIPNET_DEV void epilogue(const ConvParams& p, const Acc<C>& acc, float* smem, in
       f32x4 x0 = ld4(wt + row * LD + 8 * c8), x1 = ld4(wt + row * LD + 8 * c8 + 4);
       x0 += b0;
       x1 += b1;
+      if constexpr (EPI == PIPNET_EPI_BIAS_GELU) {
+        if (m < p.M && nok) finish_gelu_bf16(p, m, n, x0, x1);
+        continue;
+      }
       if constexpr (EPI >= PIPNET_EPI_S3_GELU) {
         if (m < p.M && nok) finish_s3<EPI>(p, m, n, x0, x1, s0, s1);
         continue;
@@ -640,6 +653,10 @@ PIPNET_DEV void pp_epilogue(const ConvParams& p, const f32x4v (&acc)[8][NB], uns
       f32x4v x1 = *reinterpret_cast<const f32x4v*>(wt + row * EPI_LD + 8 * c8 + 4);
       x0 += b0;
       x1 += b1;
+      if constexpr (EPI == PIPNET_EPI_BIAS_GELU) {
+        if (m < p.M && nok) finish_gelu_bf16(p, m, n, x0, x1);
+        continue;
+      }
       if constexpr (EPI >= PIPNET_EPI_S3_GELU) {
         if (m < p.M && nok) finish_s3<EPI>(p, m, n, x0, x1, s0, s1);
         continue;

@@ -368,12 +368,15 @@ def bf16_conv_plan(b: int, h: int, w: int, cin: int, cout: int, kh: int, kw: int
 
 @functools.lru_cache(maxsize=4096)
 def bf16_conv_kernel_name(b: int, h: int, w: int, cin: int, cout: int, kh: int, kw: int, stride: int, pad: int,
-                          epilogue: int, tile: int = -1, s3: bool = False) -> str:
-    """rocprof name of the instantiation conv2d_nhwc_bf16 (``s3``: conv_s3, ``cin`` its fp32 channels)
-    launches for this conv and requested ``tile`` (pipnet_conv2d_nhwc_bf16_label / _s3_label);
-    RuntimeError when the library has none, as the launch would answer."""
-    return _lib.label("pipnet_conv2d_nhwc_s3_label" if s3 else "pipnet_conv2d_nhwc_bf16_label",
-                      b, h, w, cin, cout, kh, kw, stride, pad, epilogue, tile)
+                          epilogue: int, tile: int = -1, s3: bool = False, mix: bool = False) -> str:
+    """rocprof name of the instantiation conv2d_nhwc_bf16 (``s3``: conv_s3, ``cin`` its fp32 channels;
+    ``mix``: conv_bf16_mix) launches for this conv and requested ``tile`` (pipnet_conv2d_nhwc_bf16_label /
+    _s3_label / _bf16_mix_label); RuntimeError when the library has none, as the launch would answer."""
+    if s3 and mix:
+        raise ValueError("bf16_conv_kernel_name: s3 and mix name different entry points")
+    entry = "pipnet_conv2d_nhwc_s3_label" if s3 else \
+        "pipnet_conv2d_nhwc_bf16_mix_label" if mix else "pipnet_conv2d_nhwc_bf16_label"
+    return _lib.label(entry, b, h, w, cin, cout, kh, kw, stride, pad, epilogue, tile)
 
 
 def pack_conv_weight_bf16(w_ohwi: Tensor) -> Tensor:
@@ -661,6 +664,66 @@ def layernorm_s3(x: Tensor, w: Tensor, b: Tensor) -> Tensor:
     _lib.call("pipnet_layernorm_s3", x.data_ptr(), x.numel() // c, c, w.data_ptr(), b.data_ptr(), y.data_ptr(),
               _stream(x))
     return y
+
+
+# ---- plain bf16 ConvNeXt path (include/pipnet_amd.h, pipnet_conv2d_nhwc_bf16_mix) ----
+def dwconv7_ln_bf16(x_nhwc: Tensor, w_packed: Tensor, bias: Tensor, ln_w: Tensor, ln_b: Tensor) -> Tensor:
+    """pipnet_dwconv7_ln_f32 rounded once (RNE) to bf16 [B,H,W,C]: the hi plane of dwconv7_ln_s3."""
+    b, h, w, c = _chk_dwconv7_ln("dwconv7_ln_bf16", x_nhwc, w_packed, bias, ln_w, ln_b)
+    y = torch.empty((b, h, w, c), device=x_nhwc.device, dtype=torch.bfloat16)
+    _lib.call("pipnet_dwconv7_ln_bf16", x_nhwc.data_ptr(), b, h, w, c, w_packed.data_ptr(), bias.data_ptr(),
+              ln_w.data_ptr(), ln_b.data_ptr(), y.data_ptr(), _stream(x_nhwc))
+    return y
+
+
+def layernorm_bf16(x: Tensor, w: Tensor, b: Tensor) -> Tensor:
+    """Row LayerNorm rounded once (RNE) to bf16 [..., C]: the hi plane of layernorm_s3."""
+    _operand("layernorm_bf16", "input", x)
+    c = x.shape[-1]
+    _chk_vec("layernorm_bf16", x, c, w=w, b=b)
+    y = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16)
+    _lib.call("pipnet_layernorm_bf16", x.data_ptr(), x.numel() // c, c, w.data_ptr(), b.data_ptr(), y.data_ptr(),
+              _stream(x))
+    return y
+
+
+def conv_bf16_mix(x: Tensor, w_packed: Tensor, kh: int, kw: int, bias: Optional[Tensor], stride: int, pad: int,
+                  epilogue: int, scale: Optional[Tensor] = None, r: Optional[Tensor] = None,
+                  out: Optional[Tensor] = None, tile: int = -1) -> Tensor:
+    """Plain bf16 conv / linear with the ConvNeXt epilogues: x [B,H,W,Cin] bf16, w_packed from
+    pack_conv_weight_bf16, fp32 accumulation.  EPI_BIAS_GELU -> bf16 [B,OH,OW,Cout] of gelu(conv + b);
+    EPI_F32_BIAS -> fp32 conv + b; EPI_F32_RESID -> fp32 r + scale * (conv + b) (``out`` may be ``r``).
+    tile -1 = automatic, or 0 / 4 / 5 / 7 (the split GEMM's tiles)."""
+    fn = "conv_bf16_mix"
+    _chk_bf(x, "conv_bf16_mix input")
+    if x.dim() != 4:
+        raise RuntimeError(f"{fn}: input must be [B,H,W,Cin] (got shape {tuple(x.shape)})")
+    b, h, w, cin = x.shape
+    dev, k = x.device, kh * kw * cin
+    _operand(fn, "weight", w_packed, dtype=torch.bfloat16, device=dev)
+    if w_packed.dim() != 2 or w_packed.shape[1] != -(-k // BF16_KTILE) * BF16_KTILE:
+        raise RuntimeError(f"{fn}: packed weight {tuple(w_packed.shape)} does not match {kh}x{kw}x{cin} "
+                           f"(K padded to {BF16_KTILE})")
+    cout = w_packed.shape[0]
+    if epilogue not in (_lib.EPI_BIAS_GELU, _lib.EPI_F32_BIAS, _lib.EPI_F32_RESID):
+        raise RuntimeError(f"{fn}: epilogue {epilogue} is not one of EPI_BIAS_GELU / EPI_F32_BIAS / EPI_F32_RESID")
+    _chk_vec(fn, x, cout, bias=bias, scale=scale)
+    oh, ow = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
+    if epilogue == _lib.EPI_F32_RESID and scale is None:
+        raise RuntimeError(f"{fn}: EPI_F32_RESID needs r and scale")
+    _operand(fn, "residual", r, shape=b * oh * ow * cout, device=dev, optional=epilogue != _lib.EPI_F32_RESID)
+    dt = torch.bfloat16 if epilogue == _lib.EPI_BIAS_GELU else torch.float32
+    if out is None:
+        out = torch.empty((b, oh, ow, cout), device=dev, dtype=dt)
+    else:
+        _operand(fn, "out", out, dtype=dt, shape=b * oh * ow * cout, device=dev)
+    m = b * oh * ow
+    _launch(bf16_conv_kernel_name(b, h, w, cin, cout, kh, kw, stride, pad, epilogue, tile, mix=True),
+            2.0 * m * cout * k,
+            lambda: _lib.call("pipnet_conv2d_nhwc_bf16_mix", x.data_ptr(), b, h, w, cin, w_packed.data_ptr(),
+                              _ptr(bias), _ptr(scale), _ptr(r), cout, kh, kw, stride, pad, epilogue, out.data_ptr(),
+                              tile, _stream(x)))
+    return out
 
 
 def layernorm(x: Tensor, w: Tensor, b: Tensor, out: Optional[Tensor] = None) -> Tensor:

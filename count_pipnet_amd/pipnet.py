@@ -308,7 +308,11 @@ def get_pip_network(num_classes: int, args: argparse.Namespace):
 def set_hip_dtype(model: nn.Module, dtype) -> nn.Module:
     """Select the compute dtype of the HIP inference path:
       * torch.float32 / "fp32" (default): exact fp32 arithmetic, parity with the reference;
-      * torch.bfloat16 / "bf16": the BASELINE C3 ResNet build (bf16 activations);
+      * torch.bfloat16 / "bf16": ResNet backbones -- the BASELINE C3 build (bf16 activations);
+        ConvNeXt backbones -- the plain bf16 build: fp32 stem and residual stream, the CNBlock
+        Linears and downsample convs as bf16 GEMMs on bf16 activations (one product per multiply,
+        fp32 accumulation; error budget in DESIGN.md section 4).  Raises only when the model has
+        neither backbone kind;
       * "bf16x3": ConvNeXt backbones -- fp32 activations, the CNBlock Linears and downsample
         convs as split-bf16 GEMMs (x = hi + lo, three bf16 products, fp32 accumulation;
         ~1e-5 relative per product, include/pipnet_amd.h pipnet_conv2d_nhwc_s3)."""
@@ -330,10 +334,11 @@ def set_hip_dtype(model: nn.Module, dtype) -> nn.Module:
         if isinstance(m, ResNet_features):
             m.hip_dtype = dtype
             found = True
-        if dtype == torch.float32 and isinstance(m, (ConvNeXt, MidLayerConvNeXt)):
-            m.hip_precision = "fp32"
+        if isinstance(m, (ConvNeXt, MidLayerConvNeXt)):
+            m.hip_precision = "fp32" if dtype == torch.float32 else "bf16"
+            found = True
     if dtype == torch.bfloat16 and not found:
-        raise ValueError("the bf16 HIP path is implemented for ResNet backbones only")
+        raise ValueError("the bf16 HIP path is implemented for ResNet and ConvNeXt backbones only")
     return model
 
 

@@ -58,7 +58,9 @@ extern "C" {
  * explanation entry points (pipnet_softmax_pool_argmax_f32, pipnet_map_argmax_f32,
  * pipnet_topk_update) are additions as well, and so are pipnet_local_explain_f32 and the
  * attribution entry points (pipnet_attr_*).  4: the fused-MLP plan query is gone (its packed code had to be
- * decoded by the caller); the label queries (pipnet_*_label) are new. */
+ * decoded by the caller); the label queries (pipnet_*_label) are new.  The plain bf16 ConvNeXt
+ * entry points (pipnet_conv2d_nhwc_bf16_mix + _label, pipnet_dwconv7_ln_bf16, pipnet_layernorm_bf16)
+ * were added since; no signature changed. */
 #define PIPNET_AMD_ABI_VERSION 4
 int pipnet_amd_abi_version(void);
 const char* pipnet_amd_status_string(int status);
@@ -201,6 +203,27 @@ int pipnet_dwconv7_ln_s3(const float* x, int B, int H, int W, int C, const float
 /* pipnet_layernorm_f32 writing split planes [rows, 2C] bf16 (input of a split-bf16 downsample conv). */
 int pipnet_layernorm_s3(const float* x, int64_t rows, int C, const float* w, const float* b, void* y,
                         void* stream);
+
+/* ---- plain bf16 build of the ConvNeXt backbone ("bf16") ---------------------------------
+ * The CNBlock Linears and the downsample convs with ONE bf16 product per multiply (a third of the
+ * split GEMM's MFMA work): A is plain bf16 [B,H,W,Cin] (Cin % 32 == 0), w_packed what
+ * pipnet_pack_conv_weight_bf16 makes ([Cout][Kp], Kp = KH*KW*Cin rounded up to 64, zero beyond),
+ * fp32 accumulation on the split GEMM's tiles (tile: -1 automatic, 0, 4, 5, 7; any other tile is
+ * PIPNET_ERR_ARG; the choice is per layer, so per-image results do not depend on the batch size).
+ *   PIPNET_EPI_BIAS_GELU: y = bf16 [B,OH,OW,Cout], gelu_erf(conv + bias) rounded once (RNE);
+ *   PIPNET_EPI_F32_BIAS:  y = fp32 conv + bias;
+ *   PIPNET_EPI_F32_RESID: y = R + scale * (conv + bias), fp32 R [B,OH,OW,Cout] (may equal y).
+ * bias / scale [Cout] fp32 (bias may be NULL); the residual stream stays fp32. */
+int pipnet_conv2d_nhwc_bf16_mix(const void* x, int B, int H, int W, int Cin, const void* w_packed,
+                                const float* bias, const float* scale, const float* R, int Cout, int KH, int KW,
+                                int stride, int pad, int epilogue, void* y, int tile, void* stream);
+
+/* pipnet_dwconv7_ln_f32 / pipnet_layernorm_f32 with the result rounded once (RNE) to bf16
+ * ([B,H,W,C] / [rows,C]): bitwise the hi plane of the _s3 producers (one shared kernel body). */
+int pipnet_dwconv7_ln_bf16(const float* x, int B, int H, int W, int C, const float* w_packed,
+                           const float* bias, const float* ln_w, const float* ln_b, void* y, void* stream);
+int pipnet_layernorm_bf16(const float* x, int64_t rows, int C, const float* w, const float* b, void* y,
+                          void* stream);
 
 /* MaxPool2d(k, stride, pad) on NHWC bf16 (C % 8 == 0). */
 int pipnet_maxpool2d_nhwc_bf16(const void* x, int B, int H, int W, int C, int k, int stride, int pad,
@@ -422,7 +445,7 @@ int pipnet_conv2d_nhwc_bf16_plan(int B, int H, int W, int Cin, int Cout, int KH,
 /* Profiling labels: the name of the kernel a launch with these shape arguments runs, as rocprof and nm -C
  * print it (e.g. "pipnet_bf16::conv_bf16_pp_kernel<5, 0, 4, 0, 2>").  Each query runs the selection of its
  * launch (pipnet_linear_f32 and its rowscale / conv forms, splits > 1: the main kernel of the split-K
- * entries; pipnet_conv2d_nhwc_bf16_tile; pipnet_conv2d_nhwc_s3; pipnet_conv1x1_bf16_dual;
+ * entries; pipnet_conv2d_nhwc_bf16_tile; pipnet_conv2d_nhwc_s3; pipnet_conv2d_nhwc_bf16_mix; pipnet_conv1x1_bf16_dual;
  * pipnet_cnblock_mlp_hw_f32) on dense 16-B aligned operands, as the plan queries do, without a HIP call.
  * Writes the NUL-terminated label into buf[cap] and returns its length, or -PIPNET_ERR_ARG when the launch
  * would be refused or the label does not fit. */
@@ -431,6 +454,8 @@ int pipnet_conv2d_nhwc_bf16_label(int B, int H, int W, int Cin, int Cout, int KH
                                   int epilogue, int tile, char* buf, int cap);
 int pipnet_conv2d_nhwc_s3_label(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
                                 int epilogue, int tile, char* buf, int cap);
+int pipnet_conv2d_nhwc_bf16_mix_label(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                      int epilogue, int tile, char* buf, int cap);
 int pipnet_conv1x1_bf16_dual_label(int64_t M, int Cin, int N1, int N2, char* buf, int cap);
 int pipnet_cnblock_mlp_label(int64_t M, int C, int hw, char* buf, int cap);
 
