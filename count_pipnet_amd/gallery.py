@@ -1,0 +1,300 @@
+"""Prototype galleries and explanation patches, on the device -- the pixel half of ``util/vis_pipnet.py`` and
+``util/visualize_prediction.py``.
+
+``topk.prototype_topk`` and ``local.explain_predictions`` stop at dataset indices and patch coordinates.  The
+reference goes on, per entry and on the host: open the file, Pillow resize, ``ToTensor``, crop the window,
+``torchvision.utils.make_grid(..., nrow=k, padding=1, pad_value=40/255.)[:, 1:-1, :]``, ``ToPILImage``
+(vis_pipnet.py:298-319, :758-849), or crop and ``ImageDraw.rectangle`` (visualize_prediction.py:80-88).
+``ToTensor`` followed by ``mul(255).byte()`` returns every uint8 value unchanged and ``40/255.`` comes back as
+40, so all of it is integer copying of the resized uint8 frame, which ``pipnet_resize_normalize_rgb8`` writes
+bit-identically to Pillow:
+
+  prototype_gallery    selection of the shown entries (host, the tables are P * G * k small) -> the distinct
+                       images decoded once each, ``batch_size`` at a time -> resized on the device -> one
+                       ``pipnet_patch_compose_rgb8`` launch per chunk lays the windows into the grids
+  explanation_images   per stored entry the patch (same kernel) and the frame with the rectangle
+                       outlined (``pipnet_draw_rects_rgb8``)
+
+No model forward runs here.  The reference opens the files without ``.convert("RGB")``; for RGB and 8-bit
+grey files the pixels it crops are those of the loader's ``convert("RGB")`` (a grey file gives a grey grid in
+three equal bands instead of one), and that is the contract: palette and alpha files follow the loader's
+``convert("RGB")``, where the reference would resize palette indices or keep the alpha band.  The label strip,
+its text, ``grid_topk_all.png``, heatmaps, file names and PNG encoding stay with the caller.
+
+``make_grid``'s rule is restated from torchvision's published source (the package is not a dependency).
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+from torch import Tensor
+
+from . import kernels as K
+from .data import DeviceEvalTransform, pack_images
+from .explain_forward import PATCH_SIZE, HostCopy, unwrap
+from .local import LocalExplanation
+from .topk import PrototypeTopK
+
+GRID_PADDING = 1                # make_grid(padding=1)
+GRID_PAD_VALUE = 40             # pad_value=40/255. after ToPILImage
+
+
+@dataclass
+class PrototypeGallery(HostCopy):
+    """Result of ``prototype_gallery``.  ``Image.fromarray(g.grids[p, :g.height[p], :g.width[p]].cpu().numpy())``
+    is the patch part of the reference's ``grid_topk_{p}.png``.  The pixel tensors stay on the device until
+    ``.cpu()`` is asked for; the small tables are built on the host and stay there."""
+    grids: Tensor          # [P, 32, k * 33 + 1, 3] uint8 (device); outside [:height, :width]: pad_value
+    height: Tensor         # [P] int64 rows of the grid (32; 30 for a single patch; 0: no grid)
+    width: Tensor          # [P] int64 columns: cells * 33 + 1 (32 for a single patch; 0: no grid)
+    cells: Tensor          # [P] int64 patches in the grid; 0: the reference writes no file for p
+    ok: Tensor             # [P] bool; False: the windows differ in size, the reference's make_grid raises
+    entry_index: Tensor    # [P, k] int64 dataset index of the cell's image, in grid order; -1: empty
+    entry_group: Tensor    # [P, k] int64 group (position in res.groups) the entry comes from
+    entry_slot: Tensor     # [P, k] int64 its slot there: res.scores[p, entry_group, entry_slot]
+    entry_score: Tensor    # [P, k] float32
+    entry_coords: Tensor   # [P, k, 4] int64 (h_min, h_max, w_min, w_max)
+    frame_index: Tensor    # [F] int64 the distinct dataset indices of the drawn entries, ascending
+    frames: Optional[Tensor]      # [F, S, S, 3] uint8 (device) resized images of frame_index; None unless keep_frames
+
+
+@dataclass
+class ExplanationImages(HostCopy):
+    """Result of ``explanation_images``: one row per stored entry of a ``LocalExplanation``, in (b, r, j) order."""
+    entry: Tensor          # [N, 3] int64 (image b, class rank r, slot j)
+    patches: Tensor        # [N, 32, 32, 3] uint8 (device): the window coords[b, r, j] at the top left, 0 beyond patch_hw
+    patch_hw: Tensor       # [N, 2] int64 (rows, columns) of the window
+    rects: Tensor          # [N, S, S, 3] uint8 (device): the frame of image b with rect[b, r, j] outlined
+
+
+# ---- selection (host) -------------------------------------------------------------------------------
+
+def _pipnet_selection(index, selected, unused, p: int) -> List[Tuple[int, int]]:
+    """vis_pipnet.py:298-313: a used prototype shows its stored images in list order."""
+    if not selected[p] or unused[p]:
+        return []
+    return [(0, j) for j, i in enumerate(index[p][0]) if i >= 0]
+
+
+def _count_selection(scores, index, groups, selected, p: int, k: int) -> List[Tuple[int, int]]:
+    """vis_pipnet.py:758-838 over the per-group lists of prototype p; an entry is (group position, slot).
+    The statements are the reference's, its fill step included: by then ``extra_samples`` has been counted down
+    to 0, so a group that took ``samples_per_group + 1`` offers its last taken entry again."""
+    if not selected[p]:                                         # :656-661: no storage for the prototype
+        return []
+    images = [(g, j) for g in range(len(groups)) for j, i in enumerate(index[p][g]) if i >= 0]      # :760-764
+    if len(images) == 0:                                        # :768-770, :781
+        return []
+
+    def score(e):
+        return scores[p][e[0]][e[1]]
+
+    count_groups = {}
+    for e in images:                                            # :785-791
+        count_groups.setdefault(groups[e[0]], []).append(e)
+    samples_per_group = k // len(count_groups)                  # :797-798
+    extra_samples = k % len(count_groups)
+    uniform_samples = []
+    for _, count_images in sorted(count_groups.items()):        # :801-809
+        sorted_images = sorted(count_images, key=score, reverse=True)
+        samples_to_take = samples_per_group + (1 if extra_samples > 0 else 0)
+        extra_samples -= 1 if extra_samples > 0 else 0
+        uniform_samples.extend(sorted_images[:min(samples_to_take, len(sorted_images))])
+    if len(uniform_samples) < k:                                # :812-827
+        unused_images = []
+        for count, count_images in count_groups.items():
+            sorted_images = sorted(count_images, key=score, reverse=True)
+            samples_to_take = samples_per_group + (1 if count in list(sorted(count_groups.keys()))[:extra_samples] else 0)
+            if len(sorted_images) > samples_to_take:
+                unused_images.extend(sorted_images[samples_to_take:])
+        unused_images.sort(key=score, reverse=True)
+        uniform_samples.extend(unused_images[:min(k - len(uniform_samples), len(unused_images))])
+    uniform_samples = uniform_samples[:k]                       # :830
+    uniform_samples.sort(key=score, reverse=True)               # :833, stable: ties keep their order
+    return uniform_samples
+
+
+def select_entries(res: PrototypeTopK) -> List[List[Tuple[int, int]]]:
+    """Per prototype the (group position, slot) entries the reference's grid shows, in grid order; an empty list
+    where it writes no grid.  ``res`` on the host."""
+    k = int(res.scores.shape[2])
+    scores, index = res.scores.tolist(), res.index.tolist()
+    selected, unused = res.selected.tolist(), res.unused.tolist()
+    if res.groups == [None]:
+        return [_pipnet_selection(index, selected, unused, p) for p in range(len(index))]
+    return [_count_selection(scores, index, res.groups, selected, p, k) for p in range(len(index))]
+
+
+# ---- geometry -----------------------------------------------------------------------------------------
+
+def _window(coords: Sequence[int], size: int) -> Tuple[int, int, int, int]:
+    """(h0, h1, w0, w1) of ``img[:, h_min:h_max, w_min:w_max]`` on a size x size image, as Python slices it."""
+    h0, h1, _ = slice(coords[0], coords[1]).indices(size)
+    w0, w1, _ = slice(coords[2], coords[3]).indices(size)
+    return h0, max(h1, h0), w0, max(w1, w0)
+
+
+def grid_layout(windows: Sequence[Tuple[int, int, int, int]]):
+    """``make_grid(patches, nrow=k, padding=1)[:, 1:-1, :]`` of n <= k patches as copies: (height, width,
+    [(h0, h1, w0, w1, y, x) per patch]), or None where ``make_grid`` raises (the windows differ in size) or
+    nothing is left to show.  n >= 2: one row of cells, the canvas ``ph`` by ``n * (pw + 1) + 1``, patch j at
+    column ``j * (pw + 1) + 1``; n == 1: ``make_grid`` returns the image unpadded, so the crop takes the patch's
+    own first and last row."""
+    ph, pw = windows[0][1] - windows[0][0], windows[0][3] - windows[0][2]
+    if any((h1 - h0, w1 - w0) != (ph, pw) for h0, h1, w0, w1 in windows) or not (0 < ph <= PATCH_SIZE and
+                                                                              0 < pw <= PATCH_SIZE):
+        return None
+    if len(windows) == 1:
+        h0, h1, w0, w1 = windows[0]
+        return (ph - 2, pw, [(h0 + 1, h1 - 1, w0, w1, 0, 0)]) if ph > 2 else None
+    step = pw + GRID_PADDING
+    return ph, len(windows) * step + GRID_PADDING, [(h0, h1, w0, w1, 0, j * step + GRID_PADDING)
+                                                    for j, (h0, h1, w0, w1) in enumerate(windows)]
+
+
+# ---- frames ---------------------------------------------------------------------------------------------
+
+def _device(net, device) -> torch.device:
+    if device is not None:
+        dev = torch.device(device)
+    elif net is not None:
+        dev = next(unwrap(net, "prototype_gallery").parameters()).device
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if dev.type != "cuda":
+        raise RuntimeError(f"count_pipnet_amd.gallery runs on a ROCm device only (got {dev}); there is no CPU fallback")
+    return dev
+
+
+def _load_frames(dataset, indices: Sequence[int], image_size: int, dev) -> Tensor:
+    """[n, S, S, 3] uint8 on ``dev``: ``Resize((S, S))`` of ``dataset[i]`` for every i, Pillow's pixels."""
+    for i in indices:
+        if not 0 <= i < len(dataset):
+            raise ValueError(f"dataset index {i} lies outside the dataset of {len(dataset)} images")
+    packed = pack_images([dataset[i][0] for i in indices])
+    return DeviceEvalTransform(image_size)(packed, dev, want_u8=True)[1]
+
+
+# ---- public calls -----------------------------------------------------------------------------------------
+
+def prototype_gallery(net_or_none, dataset, res: PrototypeTopK, *, image_size: int, device=None, batch_size: int = 64,
+                      keep_frames: bool = False, pad_value: int = GRID_PAD_VALUE) -> PrototypeGallery:
+    """The patch grids of ``vizualize_network`` (the patch part of every ``grid_topk_{p}.png``) from a
+    ``prototype_topk`` result.
+
+    ``dataset``: the ``DecodedImageFolder`` the pass ran over (``dataset[i] -> (HxWx3 uint8, target)``, i the
+    index the pass recorded).  ``net_or_none`` only names the device (``device`` overrides it; neither: the
+    current ROCm device); no forward runs and the net is not touched.
+
+    Selection is the reference's: PIP-Net (vis_pipnet.py:278-313) shows, for every prototype with
+    ``selected & ~unused``, its stored images in slot order; CountPIPNet (:758-838) samples the count groups
+    uniformly, fills up from the rest by score and sorts by score (stable), a repeated image included where the
+    reference repeats one.  The distinct images are decoded once each, ``batch_size`` at a time, resized on the
+    device and their windows laid into the grids by one launch per chunk; the frames are dropped after their
+    chunk unless ``keep_frames``.  Pixels: see the module docstring (palette and alpha files follow the
+    loader's ``convert("RGB")``)."""
+    if batch_size < 1:
+        raise ValueError(f"prototype_gallery: batch_size must be at least 1, got {batch_size}")
+    if not 0 <= int(pad_value) <= 255:
+        raise ValueError(f"prototype_gallery: pad_value must be in 0..255, got {pad_value}")
+    dev = _device(net_or_none, device)
+    res = res.cpu()
+    pn, _, k = res.scores.shape
+    selection = select_entries(res)
+    coords = res.coords.tolist()
+    height, width, cells = (torch.zeros(pn, dtype=torch.int64) for _ in range(3))
+    ok = torch.ones(pn, dtype=torch.bool)
+    entry_index, entry_group, entry_slot = (torch.full((pn, k), -1, dtype=torch.int64) for _ in range(3))
+    entry_score = torch.zeros((pn, k), dtype=torch.float32)
+    entry_coords = torch.full((pn, k, 4), -1, dtype=torch.int64)
+    by_image = {}                 # dataset index -> [(h0, h1, w0, w1, canvas, y, x)]
+    for p, entries in enumerate(selection):
+        if not entries:
+            continue
+        for c, (g, j) in enumerate(entries):
+            entry_index[p, c], entry_group[p, c], entry_slot[p, c] = res.index[p, g, j], g, j
+            entry_score[p, c], entry_coords[p, c] = res.scores[p, g, j], res.coords[p, g, j]
+        layout = grid_layout([_window(coords[p][g][j], image_size) for g, j in entries])
+        if layout is None:
+            ok[p] = False
+            continue
+        height[p], width[p], cells[p] = layout[0], layout[1], len(entries)
+        for (g, j), (h0, h1, w0, w1, y, x) in zip(entries, layout[2]):
+            by_image.setdefault(int(res.index[p, g, j]), []).append((h0, h1, w0, w1, p, y, x))
+    distinct = sorted(by_image)
+    grids = torch.full((pn, PATCH_SIZE, k * (PATCH_SIZE + GRID_PADDING) + GRID_PADDING, 3), int(pad_value),
+                       dtype=torch.uint8, device=dev)
+    kept = []
+    for c0 in range(0, len(distinct), batch_size):
+        chunk = distinct[c0:c0 + batch_size]
+        frames = _load_frames(dataset, chunk, image_size, dev)
+        K.patch_compose_rgb8(frames, [(f,) + item for f, i in enumerate(chunk) for item in by_image[i]], grids)
+        if keep_frames:
+            kept.append(frames)
+    frames = None
+    if keep_frames:
+        frames = torch.cat(kept) if kept else torch.empty((0, image_size, image_size, 3), dtype=torch.uint8, device=dev)
+    return PrototypeGallery(grids=grids, height=height, width=width, cells=cells, ok=ok, entry_index=entry_index,
+                            entry_group=entry_group, entry_slot=entry_slot, entry_score=entry_score,
+                            entry_coords=entry_coords, frame_index=torch.tensor(distinct, dtype=torch.int64),
+                            frames=frames)
+
+
+def explanation_images(dataset_or_frames, res: LocalExplanation, *, image_size: int, indices=None,
+                       batch_size: int = 64, rect_width: int = 2) -> ExplanationImages:
+    """The ``*_patch.png`` and ``*_rect.png`` pixels of ``vis_pred`` (visualize_prediction.py:80-88) for every
+    stored entry of an ``explain_predictions`` result: ``j < min(count, max_entries)`` of every (image b, class
+    rank r), in that order.
+
+    ``dataset_or_frames``: either the resized uint8 frames [B, S, S, 3] of the batch on the device (S =
+    ``image_size``; ``DeviceEvalTransform(S)(packed, device, want_u8=True)[1]``), or a ``DecodedImageFolder``
+    with ``indices`` = the dataset index of each of ``res``'s B rows, which are then decoded and resized
+    ``batch_size`` at a time on ``res``'s device.  ``patches[n]`` holds the window ``coords[b, r, j]`` of the
+    frame (Python slice semantics), zero-padded to 32 x 32 only where the window was cut, ``patch_hw[n]`` its true
+    size; ``rects[n]`` is the frame with ``rect[b, r, j]`` outlined in yellow, ``rect_width`` wide, as
+    ``ImageDraw.rectangle`` draws it (one rectangle per image, as the reference reopens the file per entry),
+    produced ``batch_size`` entries at a time.  A rectangle narrower than ``2 * rect_width + 1`` raises
+    ValueError.  Pixels: see the module docstring.  File names and heatmaps stay with the caller."""
+    if batch_size < 1:
+        raise ValueError(f"explanation_images: batch_size must be at least 1, got {batch_size}")
+    dev_res = res.classes.device
+    res = res.cpu()
+    b, c, m = res.prototype.shape
+    if torch.is_tensor(dataset_or_frames):
+        frames = dataset_or_frames
+        if indices is not None:
+            raise ValueError("explanation_images: indices go with a dataset, not with frames")
+        if tuple(frames.shape) != (b, image_size, image_size, 3) or frames.dtype != torch.uint8:
+            raise ValueError(f"explanation_images: frames must be uint8 {(b, image_size, image_size, 3)}, got "
+                             f"{frames.dtype} {tuple(frames.shape)}")
+        if not frames.is_cuda:
+            raise RuntimeError("explanation_images: frames must be on a ROCm device; there is no CPU fallback")
+    else:
+        idx = [int(i) for i in (indices if indices is not None else [])]
+        if indices is None or len(idx) != b:
+            raise ValueError(f"explanation_images: a dataset needs indices, one per image of the result ({b})")
+        dev = _device(None, dev_res if dev_res.type == "cuda" else None)
+        chunks = [_load_frames(dataset_or_frames, idx[i:i + batch_size], image_size, dev)
+                  for i in range(0, b, batch_size)]
+        frames = torch.cat(chunks) if chunks else torch.empty((0, image_size, image_size, 3), dtype=torch.uint8,
+                                                              device=dev)
+    dev = frames.device
+    stored = torch.clamp(res.count, max=m).tolist()
+    entry = [(bi, r, j) for bi in range(b) for r in range(c) for j in range(stored[bi][r])]
+    n = len(entry)
+    coords, rect = res.coords.tolist(), res.rect.tolist()
+    windows = [_window(coords[bi][r][j], image_size) for bi, r, j in entry]
+    boxes = np.asarray([rect[bi][r][j] for bi, r, j in entry], dtype=np.int64).reshape(-1, 4)
+    K.rect_outline_check(boxes, rect_width)
+    patches = torch.zeros((n, PATCH_SIZE, PATCH_SIZE, 3), dtype=torch.uint8, device=dev)
+    K.patch_compose_rgb8(frames, [(e[0],) + w + (i, 0, 0) for i, (e, w) in enumerate(zip(entry, windows))], patches)
+    src = [e[0] for e in entry]
+    parts = [K.draw_rects_rgb8(frames, src[i:i + batch_size], boxes[i:i + batch_size], rect_width)
+             for i in range(0, n, batch_size)]
+    rects = torch.cat(parts) if parts else torch.empty((0, image_size, image_size, 3), dtype=torch.uint8, device=dev)
+    return ExplanationImages(entry=torch.tensor(entry, dtype=torch.int64).reshape(-1, 3), patches=patches,
+                             patch_hw=torch.tensor([(w[1] - w[0], w[3] - w[2]) for w in windows],
+                                                   dtype=torch.int64).reshape(-1, 2), rects=rects)

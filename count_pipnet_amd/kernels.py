@@ -1392,6 +1392,106 @@ def resize_normalize_rgb8(pixels: Tensor, offsets: Tensor, sizes: Tensor, sizes_
     return (out, out_u8) if want_u8 else out
 
 
+# ---- explanation images (csrc/gallery_ops.hip) --------------------------------------------------
+
+def _host_i32(fn: str, what: str, t, cols: Optional[int]):
+    """A host table of integers as a contiguous int32 numpy array ([N, cols], or [N] without ``cols``)."""
+    import numpy as np
+    a = np.asarray(t.cpu() if torch.is_tensor(t) else t)
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+        raise RuntimeError(f"{fn}: {what} must hold integers, got {a.dtype}")
+    a = a.astype(np.int64).reshape((-1, cols) if cols else (-1,))
+    if a.size and np.abs(a).max() >= 1 << 30:
+        raise RuntimeError(f"{fn}: {what} out of range")
+    return np.ascontiguousarray(a.astype(np.int32))
+
+
+def _frames(fn: str, what: str, t: Tensor, device=None) -> None:
+    _operand(fn, what, t, dtype=torch.uint8, device=device)
+    if t.dim() != 4 or t.shape[3] != 3 or t.shape[1] < 1 or t.shape[2] < 1:
+        raise RuntimeError(f"{fn}: {what} must be [N,H,W,3] uint8 with H, W >= 1, got {tuple(t.shape)}")
+
+
+def patch_compose_rgb8(frames: Tensor, items, canvases: Tensor) -> Tensor:
+    """``canvases[canvas, y:, x:] = frames[frame, h0:min(h1, fh), w0:min(w1, fw)]`` for every row
+    (frame, h0, h1, w0, w1, canvas, y, x) of the host integer table ``items`` [N,8], in one launch (none for
+    N == 0).  ``frames`` [F,fh,fw,3] and ``canvases`` [C,ch,cw,3] are uint8 on one device; the canvases are
+    written in place and returned.  A window that runs past the frame is cut short, as a Python slice is.  Every
+    row is held against both shapes first -- non-negative origins, frame < F, canvas < C, the cut window fits at
+    (y, x) -- and a row that fails raises RuntimeError before anything is launched."""
+    fn = "patch_compose_rgb8"
+    import numpy as np
+    _frames(fn, "frames", frames)
+    _frames(fn, "canvases", canvases, frames.device)
+    it = _host_i32(fn, "items", items, 8)
+    n = it.shape[0]
+    if n == 0:
+        return canvases
+    (f, fh, fw), (c, ch, cw) = frames.shape[:3], canvases.shape[:3]
+    rows = np.minimum(it[:, 2], fh) - it[:, 1]
+    cols = np.minimum(it[:, 4], fw) - it[:, 3]
+    bad = ((it[:, [0, 1, 3, 5, 6, 7]] < 0).any(axis=1) | (it[:, 0] >= f) | (it[:, 5] >= c) |
+           (it[:, 6] + np.maximum(rows, 0) > ch) | (it[:, 7] + np.maximum(cols, 0) > cw))
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise RuntimeError(f"{fn}: item {i} {tuple(int(v) for v in it[i])} leaves the frames {tuple(frames.shape)} "
+                           f"or the canvases {tuple(canvases.shape)}")
+    dev = frames.device
+    it_dev = torch.from_numpy(it).to(dev, non_blocking=True)
+    _lib.call("pipnet_patch_compose_rgb8", frames.data_ptr(), f, fh, fw, it_dev.data_ptr(), n, canvases.data_ptr(), c,
+              ch, cw, torch.cuda.current_stream(dev).cuda_stream)
+    return canvases
+
+
+YELLOW = (255, 255, 0)          # PIL's 'yellow'
+
+
+def rect_outline_check(rects, width: int) -> None:
+    """ValueError unless every (x0, y0, x1, y1) row spans at least ``2 * width + 1`` pixels each way: the
+    outline rule of ``draw_rects_rgb8`` is Pillow's from there on only."""
+    import numpy as np
+    r = np.asarray(rects, dtype=np.int64).reshape(-1, 4)
+    if width < 1:
+        raise ValueError(f"draw_rects_rgb8: the line width must be at least 1, got {width}")
+    small = (r[:, 2] - r[:, 0] + 1 < 2 * width + 1) | (r[:, 3] - r[:, 1] + 1 < 2 * width + 1)
+    if small.any():
+        i = int(np.argmax(small))
+        raise ValueError(f"draw_rects_rgb8: rectangle {i} {tuple(int(v) for v in r[i])} is narrower than "
+                         f"2 * width + 1 = {2 * width + 1} pixels; Pillow draws such a box otherwise")
+
+
+def draw_rects_rgb8(frames: Tensor, src, rects, width: int = 2, colour=YELLOW) -> Tensor:
+    """[N,fh,fw,3] uint8: ``out[n]`` is ``frames[src[n]]`` with the outline that Pillow's
+    ``ImageDraw.rectangle([(x0, y0), (x1, y1)], outline=colour, width=width)`` draws for
+    ``rects[n] = (x0, y0, x1, y1)``, clipped to the frame (``x1 == fw`` is legal).  ``src`` [N] and ``rects``
+    [N,4] are host integer tables.  A box narrower than ``2 * width + 1`` raises ValueError (Pillow's outline
+    follows another rule there), a frame index out of range RuntimeError; nothing is launched then."""
+    fn = "draw_rects_rgb8"
+    _frames(fn, "frames", frames)
+    s = _host_i32(fn, "src", src, None)
+    r = _host_i32(fn, "rects", rects, 4)
+    n = s.shape[0]
+    if r.shape[0] != n:
+        raise RuntimeError(f"{fn}: {n} frame indices but {r.shape[0]} rectangles")
+    width = int(width)
+    rect_outline_check(r, width)
+    col = tuple(int(v) for v in colour)
+    if len(col) != 3 or not all(0 <= v <= 255 for v in col) or width >= 1 << 30:
+        raise RuntimeError(f"{fn}: colour must be three values in 0..255 (got {colour}), width below 2^30")
+    f, fh, fw = frames.shape[:3]
+    if n and (int(s.min()) < 0 or int(s.max()) >= f):
+        raise RuntimeError(f"{fn}: a frame index lies outside the {f} frames")
+    dev = frames.device
+    out = torch.empty((n, fh, fw, 3), device=dev, dtype=torch.uint8)
+    if n == 0:
+        return out
+    s_dev = torch.from_numpy(s).to(dev, non_blocking=True)
+    r_dev = torch.from_numpy(r).to(dev, non_blocking=True)
+    _lib.call("pipnet_draw_rects_rgb8", frames.data_ptr(), f, fh, fw, s_dev.data_ptr(), r_dev.data_ptr(), n, width,
+              *col, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    return out
+
+
 # ---- two-view training augmentation (csrc/augment_ops.hip) ----------------------------------
 AUG_GEOM_PARAMS, AUG_VIEW_PARAMS = _lib.CONSTANTS["AUG_GEOM_PARAMS"], _lib.CONSTANTS["AUG_VIEW_PARAMS"]
 AUG_OP_SHARPNESS, AUG_OP_LAST = 4, 8

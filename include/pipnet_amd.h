@@ -60,7 +60,8 @@ extern "C" {
  * attribution entry points (pipnet_attr_*).  4: the fused-MLP plan query is gone (its packed code had to be
  * decoded by the caller); the label queries (pipnet_*_label) are new.  The plain bf16 ConvNeXt
  * entry points (pipnet_conv2d_nhwc_bf16_mix + _label, pipnet_dwconv7_ln_bf16, pipnet_layernorm_bf16)
- * were added since; no signature changed. */
+ * were added since, and so were the explanation-image entry points (pipnet_patch_compose_rgb8,
+ * pipnet_draw_rects_rgb8); no signature changed. */
 #define PIPNET_AMD_ABI_VERSION 4
 int pipnet_amd_abi_version(void);
 const char* pipnet_amd_status_string(int status);
@@ -838,6 +839,29 @@ int pipnet_part_purity_finish(const int64_t* n, const int64_t* hits, const uint6
                               int P, int M, uint8_t* in_csv, double* max_purity, int32_t* max_part, int64_t* max_sum,
                               int32_t* most_part, int64_t* most_sum, double* most_purity, double* purity,
                               void* stream);
+
+/* ---- explanation images (util/vis_pipnet.py:298-319 / :836-849 patch grids, util/visualize_prediction.py
+ * :80-88 patch and rectangle images; csrc/gallery_ops.hip) ----------------------------------------------
+ * Frames and canvases are dense uint8 HWC images on the device: frames [F,fh,fw,3] (the out_u8 of
+ * pipnet_resize_normalize_rgb8), canvases [C,ch,cw,3].
+ * pipnet_patch_compose_rgb8: items [N,8] int32 (device), one row (frame, h0, h1, w0, w1, canvas, y, x) per
+ *   item: canvases[canvas, y:, x:] = frames[frame, h0:min(h1,fh), w0:min(w1,fw)] (a window that runs past
+ *   the frame is cut short, as a Python slice is).  The kernel also cuts the window at the canvas edge and
+ *   passes over a row with a negative origin or a frame / canvas index out of range: it never reads outside
+ *   a frame or writes outside a canvas.  Items whose cells overlap are written in no defined order.
+ *   N == 0 launches nothing.
+ * pipnet_draw_rects_rgb8: out [N,fh,fw,3]; out[n] = frames[src[n]] with the outline of
+ *   rects[n] = (x0, y0, x1, y1) (both corners inclusive, PIL ImageDraw.rectangle(outline=, width=)) in the
+ *   colour (r, g, b): pixel (x, y) is coloured iff x0 <= x <= x1 and y0 <= y <= y1 and (x < x0 + width or
+ *   x > x1 - width or y < y0 + width or y > y1 - width), clipped to the frame.  That is Pillow's outline for
+ *   boxes at least 2 * width + 1 pixels wide and tall; the caller refuses narrower ones.  |coordinate| and
+ *   width below 2^30.  src [N] int32, rects [N,4] int32 (device).
+ * fh * fw and ch * cw below 2^29; byte offsets are 64-bit.  A violation or a NULL pointer returns
+ * PIPNET_ERR_ARG before any HIP call. */
+int pipnet_patch_compose_rgb8(const uint8_t* frames, int F, int fh, int fw, const int32_t* items, int N,
+                              uint8_t* canvases, int C, int ch, int cw, void* stream);
+int pipnet_draw_rects_rgb8(const uint8_t* frames, int F, int fh, int fw, const int32_t* src, const int32_t* rects,
+                           int N, int width, int r, int g, int b, uint8_t* out, void* stream);
 
 #ifdef __cplusplus
 }
