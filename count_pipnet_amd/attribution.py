@@ -16,7 +16,7 @@ The forward of a chunk runs once for all targets, only the backward repeats (IDG
 its own path per target).  IG and LeftIG never wait for the device; IDG reads the [T, S] scores of
 its first pass once to lay out the second (``idg_schedule``, host).  Under ``torch_backend()``, or
 for a CPU net, the same algorithm runs by torch autograd through the module's own forward.
-Percentile normalisation, colouring and plotting stay with the caller.
+Percentile normalisation and colouring of the maps: ``saliency.py``; plotting stays with the caller.
 """
 from __future__ import annotations
 

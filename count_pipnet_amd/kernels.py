@@ -2063,3 +2063,113 @@ def attr_path_reduce(grads: Tensor, weights: Tensor, x: Tensor, baseline, out: O
     _lib.call("pipnet_attr_path_reduce_f32", grads.data_ptr(), grads.stride(0), weights.data_ptr(), x.data_ptr(),
               _ptr(bt), bv, s, n, out.data_ptr(), _stream(x))
     return out
+
+
+# ---- attribution images (csrc/saliency_ops.hip) -----------------------------------------------
+
+def _saliency_maps(fn: str, what: str, t: Tensor, ndim: int, device=None) -> None:
+    """A dense float32 stack of maps: [T,3,H,W] (ndim 4) or [T,H,W] (ndim 3), H * W >= 1 and below 2^31."""
+    _operand(fn, what, t, device=device)
+    if t.dim() != ndim or (ndim == 4 and t.shape[1] != 3) or t.shape[-2] * t.shape[-1] < 1:
+        want = "[T,3,H,W]" if ndim == 4 else "[T,H,W]"
+        raise RuntimeError(f"{fn}: {what} must be {want} with H, W >= 1, got {tuple(t.shape)}")
+    if t.shape[-2] * t.shape[-1] >= 1 << 31:
+        raise RuntimeError(f"{fn}: {what} has {t.shape[-2] * t.shape[-1]} values per map; the counts are 32-bit")
+
+
+def _saliency_out(fn: str, what: str, out: Optional[Tensor], shape, dtype, ref: Tensor) -> Tensor:
+    if out is None:
+        return torch.empty(shape, device=ref.device, dtype=dtype)
+    _operand(fn, what, out, dtype=dtype, shape=torch.Size(shape), device=ref.device)
+    return out
+
+
+def saliency_abs_sum(maps: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """[T,3,H,W] -> [T,H,W]: ``(|a0| + |a1|) + |a2|`` over the channels, numpy's ``np.sum(np.abs(.), axis=2)`` of
+    the transposed map (interpret_idg.py:413-415), bit for bit."""
+    fn = "saliency_abs_sum"
+    _saliency_maps(fn, "maps", maps, 4)
+    t, _, h, w = maps.shape
+    out = _saliency_out(fn, "out", out, (t, h, w), torch.float32, maps)
+    _lib.call("pipnet_saliency_abs_sum_f32", maps.data_ptr(), t, h * w, out.data_ptr(), _stream(maps))
+    return out
+
+
+def saliency_order_stats(folded: Tensor, k: int, gamma: float, out=None):
+    """(vmin, vtop, lo, hi, vq), each [T]: per map of ``folded`` [T,H,W] the exact minimum and maximum, the k-th
+    and (k+1)-th smallest values (0-based; hi = lo past the last element) and numpy's interpolation between them
+    at weight ``gamma`` (a float32 value).  ``out``: five [T] tensors to write into."""
+    fn = "saliency_order_stats"
+    _saliency_maps(fn, "folded", folded, 3)
+    t, n = folded.shape[0], folded.shape[1] * folded.shape[2]
+    if not 0 <= int(k) < n:
+        raise RuntimeError(f"{fn}: rank {k} outside 0..{n - 1}")
+    names = ("vmin", "vtop", "lo", "hi", "vq")
+    if out is None:
+        out = (None,) * 5
+    if len(out) != 5:
+        raise RuntimeError(f"{fn}: out must be the five tensors {names}")
+    res = tuple(_saliency_out(fn, nm, o, (t,), torch.float32, folded) for nm, o in zip(names, out))
+    _lib.call("pipnet_saliency_order_stats_f32", folded.data_ptr(), t, n, int(k), float(gamma),
+              *(r.data_ptr() for r in res), _stream(folded))
+    return res
+
+
+def saliency_normalize(folded: Tensor, vmin: Tensor, vq: Tensor, vtop: Tensor, fallback: bool = True, out=None):
+    """(rule [T] int32, normalized [T,H,W]): ``clip((folded - vmin) / den, 0, 1)`` with the denominator chosen per
+    map on the device (rule 0: vq - vmin, 1: vtop - vmin, 2: a zero map; pipnet_saliency_normalize_f32).
+    ``out`` = (rule, normalized) to write into."""
+    fn = "saliency_normalize"
+    _saliency_maps(fn, "folded", folded, 3)
+    t = folded.shape[0]
+    for nm, v in (("vmin", vmin), ("vq", vq), ("vtop", vtop)):
+        _operand(fn, nm, v, shape=torch.Size((t,)), device=folded.device)
+    rule, norm = (None, None) if out is None else out
+    rule = _saliency_out(fn, "rule out", rule, (t,), torch.int32, folded)
+    norm = _saliency_out(fn, "out", norm, tuple(folded.shape), torch.float32, folded)
+    _lib.call("pipnet_saliency_normalize_f32", folded.data_ptr(), vmin.data_ptr(), vq.data_ptr(), vtop.data_ptr(), t,
+              folded.shape[1] * folded.shape[2], 1 if fallback else 0, rule.data_ptr(), norm.data_ptr(), _stream(folded))
+    return rule, norm
+
+
+def saliency_blend(normalized: Tensor, colours: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """[H,W,4] float64: RGB = clip(sum_t colours[t] * normalized[t], 0, 1) added in map order in float64, alpha =
+    the running maximum from 0 (interpret_idg.py:419-427, :454-457).  ``colours`` [T,3] float64."""
+    fn = "saliency_blend"
+    _saliency_maps(fn, "normalized", normalized, 3)
+    t, h, w = normalized.shape
+    _operand(fn, "colours", colours, dtype=torch.float64, shape=torch.Size((t, 3)), device=normalized.device)
+    out = _saliency_out(fn, "out", out, (h, w, 4), torch.float64, normalized)
+    _lib.call("pipnet_saliency_blend_f64", normalized.data_ptr(), colours.data_ptr(), t, h * w, out.data_ptr(),
+              _stream(normalized))
+    return out
+
+
+def saliency_unnormalize(x: Tensor, mean, std, out: Optional[Tensor] = None) -> Tensor:
+    """x [3,H,W] -> [H,W,3] float32 ``clip(x * std + mean, 0, 1)`` per channel, product and sum rounded separately
+    (interpret_idg.py:442-446).  ``mean`` / ``std``: three floats each (their float32 values are used)."""
+    fn = "saliency_unnormalize"
+    _operand(fn, "image", x)
+    if x.dim() != 3 or x.shape[0] != 3 or x.shape[1] * x.shape[2] < 1 or x.shape[1] * x.shape[2] >= 1 << 31:
+        raise RuntimeError(f"{fn}: image must be [3,H,W] with 1 <= H * W < 2^31, got {tuple(x.shape)}")
+    mean, std = [float(v) for v in mean], [float(v) for v in std]
+    if len(mean) != 3 or len(std) != 3:
+        raise RuntimeError(f"{fn}: mean and std must hold three values each")
+    _, h, w = x.shape
+    out = _saliency_out(fn, "out", out, (h, w, 3), torch.float32, x)
+    _lib.call("pipnet_saliency_unnormalize_f32", x.data_ptr(), h * w, *mean, *std, out.data_ptr(), _stream(x))
+    return out
+
+
+def saliency_colormap_rgba8(normalized: Tensor, lut: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """[..., 4] uint8: ``lut[min(int(v * 256), 255)]`` for every value v in [0, 1] of ``normalized`` (any shape),
+    ``lut`` [256,4] uint8 -- matplotlib's byte colour map of a map whose minimum is 0 and maximum is 1."""
+    fn = "saliency_colormap_rgba8"
+    _operand(fn, "normalized", normalized)
+    _operand(fn, "lut", lut, dtype=torch.uint8, shape=torch.Size((256, 4)), device=normalized.device)
+    out = _saliency_out(fn, "out", out, tuple(normalized.shape) + (4,), torch.uint8, normalized)
+    if out.data_ptr() % 4:
+        raise RuntimeError(f"{fn}: out must start 4-byte aligned (one 4-byte store per pixel)")
+    _lib.call("pipnet_saliency_colormap_rgba8", normalized.data_ptr(), lut.data_ptr(), normalized.numel(),
+              out.data_ptr(), _stream(normalized))
+    return out

@@ -61,7 +61,7 @@ extern "C" {
  * decoded by the caller); the label queries (pipnet_*_label) are new.  The plain bf16 ConvNeXt
  * entry points (pipnet_conv2d_nhwc_bf16_mix + _label, pipnet_dwconv7_ln_bf16, pipnet_layernorm_bf16)
  * were added since, and so were the explanation-image entry points (pipnet_patch_compose_rgb8,
- * pipnet_draw_rects_rgb8); no signature changed. */
+ * pipnet_draw_rects_rgb8) and the attribution-image entry points (pipnet_saliency_*); no signature changed. */
 #define PIPNET_AMD_ABI_VERSION 4
 int pipnet_amd_abi_version(void);
 const char* pipnet_amd_status_string(int status);
@@ -862,6 +862,44 @@ int pipnet_patch_compose_rgb8(const uint8_t* frames, int F, int fh, int fw, cons
                               uint8_t* canvases, int C, int ch, int cw, void* stream);
 int pipnet_draw_rects_rgb8(const uint8_t* frames, int F, int fh, int fw, const int32_t* src, const int32_t* rects,
                            int N, int width, int r, int g, int b, uint8_t* out, void* stream);
+
+/* ---- attribution images (util/interpret_idg.py:413-427 fold / normalise / blend, :183-204
+ * normalize_attribution_map, :442-446 un-normalised image, :626-641 logit mode; csrc/saliency_ops.hip) ----
+ * T maps of N = H * W float32 values each, dense; every result is bitwise what numpy / torch give on the
+ * host for finite inputs (no a * b + c is contracted).
+ * pipnet_saliency_abs_sum_f32: maps [T,3,N] -> folded [T,N] = (|a0| + |a1|) + |a2| (np.sum(np.abs(.), axis=2)).
+ *   16-byte loads when N % 4 == 0 and both pointers are 16-byte aligned, scalar otherwise; same bits.
+ * pipnet_saliency_order_stats_f32: per map the exact minimum vmin[t], maximum vtop[t], the k-th and (k+1)-th
+ *   smallest values lo[t], hi[t] (0-based; hi = lo where k + 1 == N) and numpy's linear interpolation
+ *   vq[t] = gamma >= 0.5 ? hi - (hi - lo) * (1 - gamma) : lo + (hi - lo) * gamma in float32.  k and gamma are the
+ *   caller's (np.percentile's virtual index, split on the host).  Exact selection, one workgroup per map: a
+ *   radix select over the order-preserving 32-bit key of the float, integer LDS atomics only, so the result
+ *   does not depend on any execution order.  -0.0 sorts below +0.0.  NaN inputs stay in bounds and terminate;
+ *   their result is unspecified.  0 <= k < N.
+ * pipnet_saliency_normalize_f32: out[t] = clip((folded[t] - vmin[t]) / den, 0, 1), den and rule[t] chosen per
+ *   map from the device-resident statistics.  fallback = 1: den = vq - vmin when that is > 1e-3f (rule 0), else
+ *   vtop - vmin when that is > 1e-5f (rule 1), else a zero map (rule 2).  fallback = 0 (logit mode): den =
+ *   vq - vmin (rule 0), a zero map where vq == vmin (rule 2; the reference divides by zero there).
+ * pipnet_saliency_blend_f64: out [N,4] float64: RGB = clip(sum_t colours[t] * normalized[t], 0, 1) added in
+ *   the order t = 0 .. T-1 (product and sum rounded separately), alpha = max_t normalized[t] from 0.
+ *   colours [T,3] float64.  T == 0 writes zeros.
+ * pipnet_saliency_unnormalize_f32: x [3,N] (NCHW) -> out [N,3] (HWC) = clip(x * s_c + m_c, 0, 1), the product
+ *   and the sum rounded separately.
+ * pipnet_saliency_colormap_rgba8: out [total,4] uint8 = lut[min((int)(v * 256), 255)] for v in [0, 1] (below 0
+ *   or NaN: entry 0; above 1: entry 255); lut [256,4] uint8; out 4-byte aligned (PIPNET_ERR_ALIGN).
+ * 1 <= N < 2^31 (32-bit counts); T >= 0 (T == 0 launches nothing, but for the blend); a violation or a NULL
+ * pointer returns PIPNET_ERR_ARG before any HIP call. */
+int pipnet_saliency_abs_sum_f32(const float* maps, int T, int64_t N, float* folded, void* stream);
+int pipnet_saliency_order_stats_f32(const float* folded, int T, int64_t N, int64_t k, float gamma, float* vmin,
+                                    float* vtop, float* lo, float* hi, float* vq, void* stream);
+int pipnet_saliency_normalize_f32(const float* folded, const float* vmin, const float* vq, const float* vtop, int T,
+                                  int64_t N, int fallback, int32_t* rule, float* out, void* stream);
+int pipnet_saliency_blend_f64(const float* normalized, const double* colours, int T, int64_t N, double* out,
+                              void* stream);
+int pipnet_saliency_unnormalize_f32(const float* x, int64_t N, float m0, float m1, float m2, float s0, float s1,
+                                    float s2, float* out, void* stream);
+int pipnet_saliency_colormap_rgba8(const float* normalized, const uint8_t* lut, int64_t total, uint8_t* out,
+                                   void* stream);
 
 #ifdef __cplusplus
 }
