@@ -271,10 +271,11 @@ def _cnblock_hip(blk: CNBlock, h: Tensor, cache: Dict, key: str, row_scale: Opti
     return h
 
 
-def _cnblock_s3(blk: CNBlock, h: Tensor, cache: Dict, key: str) -> Tensor:
+def _cnblock_s3(blk: CNBlock, h: Tensor, cache: Dict, key: str, row_scale: Optional[Tensor] = None) -> Tensor:
     """One CNBlock in place on NHWC fp32 ``h`` with split-bf16 GEMMs (precision "bf16x3"):
     dwconv+LN writes split planes [hi|lo], Linear1 (+GELU) reads them and writes its own
-    output as split planes, Linear2 adds layer_scale * (.) into the fp32 residual stream."""
+    output as split planes, Linear2 adds layer_scale * (.) into the fp32 residual stream --
+    times ``row_scale`` (_cnblock_hip) per sample under train-mode stochastic depth."""
     dw, ln, l1, l2 = blk.block[0], blk.block[2], blk.block[3], blk.block[5]
     b, hh, ww, c = h.shape
     if dw.kernel_size != (7, 7) or dw.padding != (3, 3) or dw.groups != c or dw.stride != (1, 1):
@@ -285,15 +286,19 @@ def _cnblock_s3(blk: CNBlock, h: Tensor, cache: Dict, key: str) -> Tensor:
     w2 = packed(cache, key + ".fc2.s3", l2.weight, lambda w: K.split_planes_weight(w.view(c, 1, 1, hid)))
     t3 = K.dwconv7_ln_s3(h, wdw, dw.bias, ln.weight, ln.bias)
     u3 = K.conv_s3(t3, w1, 1, 1, hid, l1.bias, 1, 0, _lib.EPI_S3_GELU)
-    K.conv_s3(u3, w2, 1, 1, c, l2.bias, 1, 0, _lib.EPI_F32_RESID, scale=blk.layer_scale.view(-1), r=h, out=h)
+    if row_scale is None:
+        K.conv_s3(u3, w2, 1, 1, c, l2.bias, 1, 0, _lib.EPI_F32_RESID, scale=blk.layer_scale.view(-1), r=h, out=h)
+    else:
+        K.linear_s3_rowscale(u3, w2, l2.bias, blk.layer_scale.view(-1), h, row_scale, hh * ww)
     return h
 
 
-def _cnblock_bf16(blk: CNBlock, h: Tensor, cache: Dict, key: str) -> Tensor:
+def _cnblock_bf16(blk: CNBlock, h: Tensor, cache: Dict, key: str, row_scale: Optional[Tensor] = None) -> Tensor:
     """One CNBlock in place on NHWC fp32 ``h`` with plain bf16 GEMMs (precision "bf16"): dwconv+LN
     rounds once to bf16, Linear1 (+GELU, fp32) rounds once to a bf16 hidden tensor, Linear2 adds
     layer_scale * (.) into the fp32 residual stream -- one bf16 product per multiply, RNE-bf16
-    weights, fp32 accumulation.  Every stage runs this unfused pair (no fused bf16 MLP kernel)."""
+    weights, fp32 accumulation.  Every stage runs this unfused pair (no fused bf16 MLP kernel).
+    ``row_scale`` as in _cnblock_hip: the branch times keep_b / (1 - p) in the Linear2 epilogue."""
     dw, ln, l1, l2 = blk.block[0], blk.block[2], blk.block[3], blk.block[5]
     b, hh, ww, c = h.shape
     if dw.kernel_size != (7, 7) or dw.padding != (3, 3) or dw.groups != c or dw.stride != (1, 1):
@@ -304,7 +309,10 @@ def _cnblock_bf16(blk: CNBlock, h: Tensor, cache: Dict, key: str) -> Tensor:
     w2 = packed(cache, key + ".fc2.bf16", l2.weight, lambda w: K.pack_conv_weight_bf16(w.view(c, 1, 1, hid)))
     t = K.dwconv7_ln_bf16(h, wdw, dw.bias, ln.weight, ln.bias)
     u = K.conv_bf16_mix(t, w1, 1, 1, l1.bias, 1, 0, _lib.EPI_BIAS_GELU)
-    K.conv_bf16_mix(u, w2, 1, 1, l2.bias, 1, 0, _lib.EPI_F32_RESID, scale=blk.layer_scale.view(-1), r=h, out=h)
+    if row_scale is None:
+        K.conv_bf16_mix(u, w2, 1, 1, l2.bias, 1, 0, _lib.EPI_F32_RESID, scale=blk.layer_scale.view(-1), r=h, out=h)
+    else:
+        K.linear_bf16_mix_rowscale(u, w2, l2.bias, blk.layer_scale.view(-1), h, row_scale, hh * ww)
     return h
 
 
@@ -357,12 +365,15 @@ def convnext_features_hip_steps(features: nn.Sequential, x: Tensor, cache: Dict,
     ``precision``: "fp32" (exact fp32 MFMA GEMMs) or "bf16x3" (the CNBlock Linears and the
     downsample convs as split-bf16 GEMMs, include/pipnet_amd.h) or "bf16" (the same layers as plain
     bf16 GEMMs on bf16 activations: one product per multiply, fp32 accumulation and residual stream;
-    error budget in DESIGN.md section 4).  Both are inference only -- train-mode stochastic depth
-    always runs fp32."""
+    error budget in DESIGN.md section 4).  Masks and a precision combine: a block with p > 0 then
+    scales its branch per sample in the low-precision Linear2's epilogue (K.linear_s3_rowscale /
+    K.linear_bf16_mix_rowscale), a block with p == 0 runs what it runs without masks.  These are
+    forward-only layers (no saved activations): the frozen part of a training step
+    (convnext_train.train_forward with set_hip_train_dtype), never its trainable suffix."""
     if precision not in PRECISIONS:
         raise ValueError(f"unknown HIP precision {precision!r} (expected one of {PRECISIONS})")
-    s3 = precision == "bf16x3" and sd_keep is None
-    bf = precision == "bf16" and sd_keep is None
+    s3 = precision == "bf16x3"
+    bf = precision == "bf16"
     K.require_device(x, "network input")
     x = x.contiguous()
     h = None
@@ -378,12 +389,13 @@ def convnext_features_hip_steps(features: nn.Sequential, x: Tensor, cache: Dict,
             yield
         elif len(mod) > 0 and isinstance(mod[0], CNBlock):
             for j, blk in enumerate(mod):
+                row_scale = None if scales is None else scales.get(bid)
                 if s3:
-                    h = _cnblock_s3(blk, h, cache, f"{name}.{j}")
+                    h = _cnblock_s3(blk, h, cache, f"{name}.{j}", row_scale)
                 elif bf:
-                    h = _cnblock_bf16(blk, h, cache, f"{name}.{j}")
+                    h = _cnblock_bf16(blk, h, cache, f"{name}.{j}", row_scale)
                 else:
-                    h = _cnblock_hip(blk, h, cache, f"{name}.{j}", None if scales is None else scales.get(bid))
+                    h = _cnblock_hip(blk, h, cache, f"{name}.{j}", row_scale)
                 bid += 1
                 yield
         elif len(mod) == 2 and isinstance(mod[0], LayerNorm2d) and isinstance(mod[1], nn.Conv2d):

@@ -74,10 +74,13 @@ def train_forward(model, xs: Tensor, start: Optional[int], sd_keep: Dict[int, Te
     output g and the Linear2 output y2; per downsample its input and LayerNorm output.
     ``eval_mode``: stochastic depth is the identity (no masks, no 1 / (1 - p) scale: every block
     runs with rs = None), as under ``net.eval()``.  ``nhwc4`` (start = 0 only): the input already in
-    the stem conv's 4-channel NHWC form, in place of ``xs``."""
+    the stem conv's 4-channel NHWC form, in place of ``xs``.
+    The executor part -- layers that run forward only -- takes the model's ``hip_train_precision``
+    (pipnet.set_hip_train_dtype; "fp32" unless set); the kept suffix is always fp32."""
     feats, cache = model.features, model._hip_pack
+    precision = getattr(model, "hip_train_precision", "fp32")
     if start is None:
-        return convnext_features_hip(feats, xs, cache, sd_keep), []
+        return convnext_features_hip(feats, xs, cache, sd_keep, precision), []
     saved = []
     if start == 0:   # trainable stem (the "train everything" epochs): conv k4 s4 and LN unfused
         conv, ln = feats[0][0], feats[0][1]
@@ -91,7 +94,7 @@ def train_forward(model, xs: Tensor, start: Optional[int], sd_keep: Dict[int, Te
         saved.append(Saved("stem", feats[0], "0", dict(x=xp, z=z)))
         start = 1
     else:
-        h = convnext_features_hip(feats[:start], xs, cache, sd_keep)
+        h = convnext_features_hip(feats[:start], xs, cache, sd_keep, precision)
     scales = {} if eval_mode else stochastic_depth_row_scales(feats, sd_keep, xs.shape[0], xs.device)
     bid = len(_cnblocks(feats[:start]))
     for idx in range(start, len(feats)):

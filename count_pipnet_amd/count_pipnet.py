@@ -255,7 +255,8 @@ def detect_output_channels(features: nn.Module) -> int:
 def get_count_network(num_classes: int, args: argparse.Namespace, max_count: int = 3, use_ste: bool = True,
                       device=None):
     """count_pipnet.py:324-436 -> (CountPIPNet, num_prototypes).  Optional ``args.hip_dtype``
-    ("fp32" | "bf16" | "bf16x3") selects the HIP compute dtype of the backbone (pipnet.set_hip_dtype)."""
+    ("fp32" | "bf16" | "bf16x3") selects the HIP compute dtype of the backbone (pipnet.set_hip_dtype),
+    optional ``args.hip_train_dtype`` that of a training step's frozen layers (pipnet.set_hip_train_dtype)."""
     if args.net not in base_architecture_to_features:
         raise ValueError(f"Network '{args.net}' is not supported. "
                          f"Supported networks: {list(base_architecture_to_features)}")
@@ -299,4 +300,7 @@ def get_count_network(num_classes: int, args: argparse.Namespace, max_count: int
     if getattr(args, "hip_dtype", None):          # optional HIP compute dtype (pipnet.set_hip_dtype)
         from .pipnet import set_hip_dtype
         set_hip_dtype(model, args.hip_dtype)
+    if getattr(args, "hip_train_dtype", None):    # ... and that of a training step's frozen layers
+        from .pipnet import set_hip_train_dtype
+        set_hip_train_dtype(model, args.hip_train_dtype)
     return model, num_prototypes

@@ -75,8 +75,10 @@ bool is_s3_epi(int epi) {
 bool is_mix_epi(int epi) {
   return epi == PIPNET_EPI_BIAS_GELU || epi == PIPNET_EPI_F32_BIAS || epi == PIPNET_EPI_F32_RESID;
 }
-// either family: served by tiles 0 / 4 / 5 / 7 only
-bool is_cnx_epi(int epi) { return is_s3_epi(epi) || epi == PIPNET_EPI_BIAS_GELU; }
+// either family, and the row-scaled residual of the two *_rowscale entries: served by tiles 0 / 4 / 5 / 7 only
+bool is_cnx_epi(int epi) {
+  return is_s3_epi(epi) || epi == PIPNET_EPI_BIAS_GELU || epi == PIPNET_EPI_F32_RESID_ROWSCALE;
+}
 
 // 3x3 / stride 1 / pad 1 convs with N >= 256 whose halo fits the kernel's 320 LDS rows
 // (256 + 2W + 2): the LDS-halo ping-pong kernel (tile 8) replaces tile 5 -- a per-layer
@@ -146,6 +148,17 @@ ConvRef select_conv(const ConvParams& p, int epi, int& v) {
   using pipnet::for_value;
   v = plan_conv<ALOAD>(p, epi, v);
   if (v < 0) return {};
+  if (epi == PIPNET_EPI_F32_RESID_ROWSCALE) {    // Linear2 under stochastic depth: F32_RESID's tiles, dense rows only
+    constexpr int E = PIPNET_EPI_F32_RESID_ROWSCALE;
+    if constexpr (ALOAD == ALOAD_DENSE) {
+      if (v == 7) return PIPNET_KREF(pipnet_bf16::conv_bf16_pp_kernel, E, ALOAD_DENSE, 3, 0, 2);
+      if (v == 5) return PIPNET_KREF(pipnet_bf16::conv_bf16_pp_kernel, E, ALOAD_DENSE, 4, 0, 2);
+      if (v == 4 && p.N % 128) return PIPNET_KREF_T(pipnet_bf16::conv_bf16_kernel, CfgM4, E, ALOAD_DENSE, 2, true);
+      if (v == 4) return PIPNET_KREF_T(pipnet_bf16::conv_bf16_kernel, CfgM4, E, ALOAD_DENSE, 2, false);
+      if (v == 0) return PIPNET_KREF_T(pipnet_bf16::conv_bf16_kernel, CfgS, E, ALOAD_DENSE, 3, false);
+    }
+    return {};
+  }
   if (v == 11)                                   // Cin = N = 64 / 128 3x3 on the LDS input halo
     return for_value<ConvRef, PIPNET_BF16_EPIS>(epi, [&](auto e) -> ConvRef {
       constexpr int E = decltype(e)::value;
@@ -591,4 +604,73 @@ extern "C" int pipnet_conv2d_nhwc_bf16_mix_label(int B, int H, int W, int Cin, i
   if (conv_mix_shape(p, dense, B, H, W, Cin, Cout, KH, KW, stride, pad, epilogue, tile)) return -PIPNET_ERR_ARG;
   return pipnet::write_label(dense ? select_conv<ALOAD_DENSE>(p, epilogue, tile)
                                    : select_conv<ALOAD_CONV>(p, epilogue, tile), buf, cap);
+}
+
+namespace {
+
+// Shape part of the two row-scaled Linear2 entries: the dense 1x1 form of the entry beside it (M rows as an
+// M x 1 image), epilogue PIPNET_EPI_F32_RESID's checks and tiles.
+int linear_rowscale_shape(ConvParams& p, bool s3, int64_t M, int Cin, int Cout, int tile) {
+  if (M < 0 || M >= (int64_t)1 << 31) return PIPNET_ERR_ARG;
+  bool dense = false;
+  const int h = M > 0 ? (int)M : 1;
+  const int st = s3 ? conv_s3_shape(p, dense, M > 0, h, 1, Cin, Cout, 1, 1, 1, 0, PIPNET_EPI_F32_RESID, tile)
+                    : conv_mix_shape(p, dense, M > 0, h, 1, Cin, Cout, 1, 1, 1, 0, PIPNET_EPI_F32_RESID, tile);
+  if (st) return st;
+  p.ldc = Cout;
+  return dense ? PIPNET_OK : PIPNET_ERR_ARG;
+}
+
+int linear_rowscale_launch(bool s3, const void* x, int64_t M, int Cin, const void* w_packed, const float* bias,
+                           const float* scale, const float* R, int Cout, const float* row_scale, int rows_per_scale,
+                           void* y, int tile, void* stream) {
+  ConvParams p{};
+  if (const int st = linear_rowscale_shape(p, s3, M, Cin, Cout, tile)) return st;
+  if (!R || !scale || !row_scale || rows_per_scale <= 0 || !x || !w_packed || !y) return PIPNET_ERR_ARG;
+  if (!aligned16(x) || !aligned16(w_packed) || !aligned16(y) || !aligned16(R) || (bias && !aligned16(bias)) ||
+      !aligned16(scale))
+    return PIPNET_ERR_ALIGN;
+  if (M == 0) return PIPNET_OK;
+  p.A = reinterpret_cast<const bf16*>(x);
+  p.W = reinterpret_cast<const bf16*>(w_packed);
+  p.bias = bias;
+  p.scale = scale;
+  p.R32 = R;
+  p.Cf = reinterpret_cast<float*>(y);
+  p.row_scale = row_scale;
+  p.rows_per_scale = rows_per_scale;
+  return launch_conv<ALOAD_DENSE>(p, PIPNET_EPI_F32_RESID_ROWSCALE, tile, (hipStream_t)stream);
+}
+
+int linear_rowscale_label(bool s3, int64_t M, int Cin, int Cout, int tile, char* buf, int cap) {
+  ConvParams p{};
+  if (M <= 0 || linear_rowscale_shape(p, s3, M, Cin, Cout, tile)) return -PIPNET_ERR_ARG;
+  return pipnet::write_label(select_conv<ALOAD_DENSE>(p, PIPNET_EPI_F32_RESID_ROWSCALE, tile), buf, cap);
+}
+
+}  // namespace
+
+// CNBlock Linear2 * layer_scale + residual under train-mode StochasticDepth("row") on the plain bf16 and the
+// split-bf16 operands (include/pipnet_amd.h): PIPNET_EPI_F32_RESID with one factor per rows_per_scale rows.
+extern "C" int pipnet_linear_bf16_mix_rowscale(const void* x, int64_t M, int Cin, const void* w_packed,
+                                               const float* bias, const float* scale, const float* R, int Cout,
+                                               const float* row_scale, int rows_per_scale, void* y, int tile,
+                                               void* stream) {
+  return linear_rowscale_launch(false, x, M, Cin, w_packed, bias, scale, R, Cout, row_scale, rows_per_scale, y, tile,
+                                stream);
+}
+
+extern "C" int pipnet_linear_s3_rowscale(const void* x, int64_t M, int Cin, const void* w_packed, const float* bias,
+                                         const float* scale, const float* R, int Cout, const float* row_scale,
+                                         int rows_per_scale, void* y, int tile, void* stream) {
+  return linear_rowscale_launch(true, x, M, Cin, w_packed, bias, scale, R, Cout, row_scale, rows_per_scale, y, tile,
+                                stream);
+}
+
+extern "C" int pipnet_linear_bf16_mix_rowscale_label(int64_t M, int Cin, int Cout, int tile, char* buf, int cap) {
+  return linear_rowscale_label(false, M, Cin, Cout, tile, buf, cap);
+}
+
+extern "C" int pipnet_linear_s3_rowscale_label(int64_t M, int Cin, int Cout, int tile, char* buf, int cap) {
+  return linear_rowscale_label(true, M, Cin, Cout, tile, buf, cap);
 }

@@ -58,6 +58,13 @@ PIPNET_DEV bf16x8 to_bf16x8(const f32x4& x0, const f32x4& x1) {
 
 constexpr int KPAD = 64;                      // packed weights: K rounded up to this
 
+// Epilogue 13, after the header's PIPNET_EPI_* codes: PIPNET_EPI_F32_RESID under train-mode stochastic depth,
+//   C = R + rs[min(m, M-1) / rows_per_scale] * (s * (A W^T + b)),   fp32 C and R (R may alias C)
+// -- the fp32 GEMM's PIPNET_EPI_RESID_ROWSCALE (gemm_f32_impl.hpp epi_math, same multiplication order) on the
+// bf16 tiles.  No entry point takes it as an `epilogue` argument (the launches that run it are
+// pipnet_linear_bf16_mix_rowscale / pipnet_linear_s3_rowscale), so it is defined here, not in the C header.
+#define PIPNET_EPI_F32_RESID_ROWSCALE 13
+
 struct ConvParams {
   const bf16* A;
   int64_t lda;         // dense rows (1x1 stride-1 convs): row pitch in elements
@@ -79,6 +86,8 @@ struct ConvParams {
   int seg;             // split planes [hi | lo] of seg channels read as K' = [hi | lo | hi]: a
                        // (virtual) channel c >= 2 seg is read at c - 2 seg; 0 = no remap
   int mt, nt, group_m;
+  const float* row_scale;  // EPI_F32_RESID_ROWSCALE: one factor per rows_per_scale rows (a sample's pixels)
+  int rows_per_scale;
 };
 
 enum { ALOAD_DENSE = 0, ALOAD_CONV = 2 };
@@ -217,9 +226,11 @@ PIPNET_DEV u32x4 as_u32x4(const bf16x8& v) { return __builtin_bit_cast(u32x4, v)
 // Epilogues of the split-bf16 ConvNeXt path (include/pipnet_amd.h, pipnet_conv2d_nhwc_s3):
 // x0 / x1 = accumulator + bias of channels n .. n+7 of row m.  S3_GELU writes GELU's output
 // as the next GEMM's A operand, split planes [hi | lo] (row pitch ldc = 2N); F32_BIAS /
-// F32_RESID write fp32 (the residual stream and the downsample outputs stay fp32).
+// F32_RESID write fp32 (the residual stream and the downsample outputs stay fp32); F32_RESID_ROWSCALE is
+// F32_RESID with the row's stochastic-depth factor rs (0 leaves the row equal to R: R + 0 * finite).
 template <int EPI>
-PIPNET_DEV void finish_s3(const ConvParams& p, int m, int n, f32x4 x0, f32x4 x1, f32x4 s0, f32x4 s1) {
+PIPNET_DEV void finish_s3(const ConvParams& p, int m, int n, f32x4 x0, f32x4 x1, f32x4 s0, f32x4 s1,
+                          float rs = 1.f) {
   if constexpr (EPI == PIPNET_EPI_S3_GELU) {
     const f32x2 g0 = gelu_pk16(f32x2{x0[0], x0[1]}), g1 = gelu_pk16(f32x2{x0[2], x0[3]});
     const f32x2 g2 = gelu_pk16(f32x2{x1[0], x1[1]}), g3 = gelu_pk16(f32x2{x1[2], x1[3]});
@@ -240,6 +251,11 @@ PIPNET_DEV void finish_s3(const ConvParams& p, int m, int n, f32x4 x0, f32x4 x1,
       const float* r = p.R32 + (int64_t)m * p.ldr + n;
       x0 = ld4(r) + s0 * x0;
       x1 = ld4(r + 4) + s1 * x1;
+    }
+    if constexpr (EPI == PIPNET_EPI_F32_RESID_ROWSCALE) {
+      const float* r = p.R32 + (int64_t)m * p.ldr + n;
+      x0 = ld4(r) + rs * (s0 * x0);       // (ls * y) * (mask / keep) + x, the fp32 GEMM's order
+      x1 = ld4(r + 4) + rs * (s1 * x1);
     }
     float* dst = p.Cf + (int64_t)m * p.ldc + n;
     st4(dst, x0);
@@ -278,9 +294,22 @@ PIPNET_DEV void epilogue(const ConvParams& p, const Acc<C>& acc, float* smem, in
     b0 = ld4(p.bias + n);
     b1 = ld4(p.bias + n + 4);
   }
-  if (EPI == PIPNET_EPI_F32_RESID && nok) {
+  if ((EPI == PIPNET_EPI_F32_RESID || EPI == PIPNET_EPI_F32_RESID_ROWSCALE) && nok) {
     s0 = ld4(p.scale + n);
     s1 = ld4(p.scale + n + 4);
+  }
+  // the rows' stochastic-depth factors, loaded with the other preloads (before vm_drain): the store loop
+  // then issues what F32_RESID's does, the residual loads and the stores
+  constexpr bool HAS_RS = EPI == PIPNET_EPI_F32_RESID_ROWSCALE;
+  float rsv[HAS_RS ? TM : 1][HAS_RS ? NIT : 1];
+  if constexpr (HAS_RS) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) {
+        const int m = min(m0 + wm * 32 * TM + i * 32 + it * RPI + lane / CPR, p.M - 1);
+        rsv[i][it] = p.row_scale[m / p.rows_per_scale];
+      }
   }
   bf16x8 r[TM][NIT];
   if (HAS_R) {
@@ -310,6 +339,10 @@ PIPNET_DEV void epilogue(const ConvParams& p, const Acc<C>& acc, float* smem, in
       x1 += b1;
       if constexpr (EPI == PIPNET_EPI_BIAS_GELU) {
         if (m < p.M && nok) finish_gelu_bf16(p, m, n, x0, x1);
+        continue;
+      }
+      if constexpr (HAS_RS) {
+        if (m < p.M && nok) finish_s3<EPI>(p, m, n, x0, x1, s0, s1, rsv[i][it]);
         continue;
       }
       if constexpr (EPI >= PIPNET_EPI_S3_GELU) {
@@ -611,7 +644,7 @@ PIPNET_DEV void pp_epilogue(const ConvParams& p, const f32x4v (&acc)[8][NB], uns
     b0 = *reinterpret_cast<const f32x4v*>(p.bias + n);
     b1 = *reinterpret_cast<const f32x4v*>(p.bias + n + 4);
   }
-  if (EPI == PIPNET_EPI_F32_RESID && nok) {
+  if ((EPI == PIPNET_EPI_F32_RESID || EPI == PIPNET_EPI_F32_RESID_ROWSCALE) && nok) {
     s0 = *reinterpret_cast<const f32x4v*>(p.scale + n);
     s1 = *reinterpret_cast<const f32x4v*>(p.scale + n + 4);
   }
@@ -630,6 +663,16 @@ PIPNET_DEV void pp_epilogue(const ConvParams& p, const f32x4v (&acc)[8][NB], uns
         if (nok) rrs[half][it] = *reinterpret_cast<const bf16x8v*>(src);
         rp += 8 * p.ldr;
       }
+  }
+  // the rows' stochastic-depth factors of both halves, with the other preloads (before vm_drain)
+  constexpr bool HAS_RS = EPI == PIPNET_EPI_F32_RESID_ROWSCALE;
+  float rsv[HAS_RS ? 2 : 1][HAS_RS ? 8 : 1];
+  if constexpr (HAS_RS) {
+#pragma unroll
+    for (int half = 0; half < 2; ++half)
+#pragma unroll
+      for (int it = 0; it < 2 * (half ? RB - 4 : 4); ++it)
+        rsv[half][it] = p.row_scale[min(mrow0 + half * 64 + it * 8, p.M - 1) / p.rows_per_scale];
   }
   bf16* op = p.C + (int64_t)mrow0 * p.ldc + n;
 #pragma unroll
@@ -655,6 +698,10 @@ PIPNET_DEV void pp_epilogue(const ConvParams& p, const f32x4v (&acc)[8][NB], uns
       x1 += b1;
       if constexpr (EPI == PIPNET_EPI_BIAS_GELU) {
         if (m < p.M && nok) finish_gelu_bf16(p, m, n, x0, x1);
+        continue;
+      }
+      if constexpr (HAS_RS) {
+        if (m < p.M && nok) finish_s3<EPI>(p, m, n, x0, x1, s0, s1, rsv[half][it]);
         continue;
       }
       if constexpr (EPI >= PIPNET_EPI_S3_GELU) {

@@ -726,6 +726,69 @@ def conv_bf16_mix(x: Tensor, w_packed: Tensor, kh: int, kw: int, bias: Optional[
     return out
 
 
+# ---- CNBlock Linear2 under train-mode stochastic depth on the low-precision operands ----
+LOWP_ROWSCALE_TILES = (-1, 0, 4, 5, 7)      # what EPI_F32_RESID takes on either operand format
+
+
+@functools.lru_cache(maxsize=4096)
+def linear_lowp_rowscale_kernel_name(m: int, cin: int, cout: int, tile: int = -1, s3: bool = False) -> str:
+    """rocprof name of the instantiation linear_bf16_mix_rowscale (``s3``: linear_s3_rowscale, ``cin`` its fp32
+    channels) launches (pipnet_linear_bf16_mix_rowscale_label / pipnet_linear_s3_rowscale_label)."""
+    entry = "pipnet_linear_s3_rowscale_label" if s3 else "pipnet_linear_bf16_mix_rowscale_label"
+    return _lib.label(entry, m, cin, cout, tile)
+
+
+def _linear_lowp_rowscale(fn: str, s3: bool, a: Tensor, w_packed: Tensor, bias: Optional[Tensor], scale: Tensor,
+                          r: Tensor, row_scale: Tensor, rows_per_scale: int, out: Optional[Tensor], tile: int) -> Tensor:
+    _operand(fn, "input", a, dtype=torch.bfloat16)
+    if a.dim() < 2 or (s3 and a.shape[-1] % 2):
+        raise RuntimeError(f"{fn}: input must be rows of {'split planes [..., 2 Cin]' if s3 else '[..., Cin]'} "
+                           f"(got shape {tuple(a.shape)})")
+    width = a.shape[-1]
+    cin, m = (width // 2 if s3 else width), a.numel() // width
+    kp = -(-3 * cin // S3_KTILE) * S3_KTILE if s3 else -(-cin // BF16_KTILE) * BF16_KTILE
+    _operand(fn, "weight", w_packed, dtype=torch.bfloat16, device=a.device)
+    if w_packed.dim() != 2 or w_packed.shape[1] != kp:
+        raise RuntimeError(f"{fn}: packed weight {tuple(w_packed.shape)} does not match {cin} input channels "
+                           f"(packed K {kp})")
+    cout = w_packed.shape[0]
+    if tile not in LOWP_ROWSCALE_TILES:
+        raise RuntimeError(f"{fn}: tile {tile} is not one of {LOWP_ROWSCALE_TILES}")
+    _chk_vec(fn, a, cout, bias=bias)
+    _operand(fn, "scale", scale, shape=cout, device=a.device)
+    _operand(fn, "residual", r, shape=m * cout, device=a.device)
+    _operand(fn, "row_scale", row_scale, device=a.device)
+    _chk_row_scale(fn, a, m, row_scale, rows_per_scale)
+    if out is None:
+        out = r
+    else:
+        _operand(fn, "out", out, shape=m * cout, device=a.device)
+    k = 3 * cin if s3 else cin
+    _launch(linear_lowp_rowscale_kernel_name(m, cin, cout, tile, s3), 2.0 * m * cout * k / (3.0 if s3 else 1.0),
+            lambda: _lib.call("pipnet_linear_s3_rowscale" if s3 else "pipnet_linear_bf16_mix_rowscale", a.data_ptr(), m,
+                              cin, w_packed.data_ptr(), _ptr(bias), scale.data_ptr(), r.data_ptr(), cout,
+                              row_scale.data_ptr(), rows_per_scale, out.data_ptr(), tile, _stream(a)))
+    return out
+
+
+def linear_bf16_mix_rowscale(a: Tensor, w_packed: Tensor, bias: Optional[Tensor], scale: Tensor, r: Tensor,
+                             row_scale: Tensor, rows_per_scale: int, out: Optional[Tensor] = None,
+                             tile: int = -1) -> Tensor:
+    """fp32 r + row_scale[m // rows_per_scale] * (scale * (a w^T + bias)) on plain bf16 rows ``a`` [..., Cin]
+    and a pack_conv_weight_bf16 weight: conv_bf16_mix's EPI_F32_RESID with one stochastic-depth factor per
+    sample (same tile, same K order).  In place on ``r`` unless ``out`` is given; tile -1 / 0 / 4 / 5 / 7."""
+    return _linear_lowp_rowscale("linear_bf16_mix_rowscale", False, a, w_packed, bias, scale, r, row_scale,
+                                 rows_per_scale, out, tile)
+
+
+def linear_s3_rowscale(a2: Tensor, w_packed: Tensor, bias: Optional[Tensor], scale: Tensor, r: Tensor,
+                       row_scale: Tensor, rows_per_scale: int, out: Optional[Tensor] = None, tile: int = -1) -> Tensor:
+    """The same on split planes ``a2`` [..., 2 Cin] and a split_planes_weight weight: conv_s3's EPI_F32_RESID
+    with one stochastic-depth factor per sample."""
+    return _linear_lowp_rowscale("linear_s3_rowscale", True, a2, w_packed, bias, scale, r, row_scale,
+                                 rows_per_scale, out, tile)
+
+
 def layernorm(x: Tensor, w: Tensor, b: Tensor, out: Optional[Tensor] = None) -> Tensor:
     _operand("layernorm", "input", x)
     c = x.shape[-1]

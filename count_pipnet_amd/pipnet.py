@@ -342,12 +342,41 @@ def set_hip_dtype(model: nn.Module, dtype) -> nn.Module:
     return model
 
 
+HIP_TRAIN_DTYPES = ("fp32", "bf16x3", "bf16")
+
+
+def set_hip_train_dtype(model: nn.Module, dtype: str) -> nn.Module:
+    """Select the arithmetic of the FROZEN backbone layers of a HIP training step (train.hip_*_step,
+    train.train_forward_hip): the whole backbone in the finetune phase, ``features[:trainable_start]``
+    in the pretrain / joint phases -- the layers that run forward only, with train-mode stochastic depth.
+      * "fp32" (default): the exact fp32 GEMMs, parity with the reference;
+      * "bf16x3": the split-bf16 GEMMs of ``set_hip_dtype(model, "bf16x3")``, held to the fp32 bars;
+      * "bf16": the plain bf16 GEMMs of ``set_hip_dtype(model, "bf16")`` under their error budget.
+    The trainable suffix, every backward, the heads, the loss and AdamW stay fp32 whatever is set.
+    ConvNeXt backbones only: a ResNet takes "fp32" alone (its train-mode BatchNorm has no bf16 form).
+    Independent of ``set_hip_dtype``, which selects the inference forward."""
+    from .convnext_features import MidLayerConvNeXt
+    if dtype not in HIP_TRAIN_DTYPES:
+        raise ValueError(f"unsupported HIP training dtype {dtype!r} (expected one of {HIP_TRAIN_DTYPES})")
+    convnexts = [m for m in model.modules() if isinstance(m, (ConvNeXt, MidLayerConvNeXt))]
+    if dtype != "fp32" and not convnexts:
+        kind = "a ResNet backbone trains in fp32 only (train-mode BatchNorm has no bf16 form)" \
+            if any(isinstance(m, ResNet_features) for m in model.modules()) else "the model has no ConvNeXt backbone"
+        raise ValueError(f"set_hip_train_dtype({dtype!r}): {kind}")
+    for m in convnexts:
+        m.hip_train_precision = dtype
+    return model
+
+
 def get_pipnet(num_classes: int, args: argparse.Namespace):
     """pipnet.py:117-139 -> (PIPNet, num_prototypes).  Optional ``args.hip_dtype``
-    ("fp32" | "bf16" | "bf16x3") selects the HIP compute dtype (see set_hip_dtype)."""
+    ("fp32" | "bf16" | "bf16x3") selects the HIP compute dtype (see set_hip_dtype), optional
+    ``args.hip_train_dtype`` that of a training step's frozen layers (set_hip_train_dtype)."""
     feature_net, add_on, pool, classification, num_prototypes = get_pip_network(num_classes, args)
     model = PIPNet(num_classes=num_classes, num_prototypes=num_prototypes, feature_net=feature_net, args=args,
                    add_on_layers=add_on, pool_layer=pool, classification_layer=classification)
     if getattr(args, "hip_dtype", None):
         set_hip_dtype(model, args.hip_dtype)
+    if getattr(args, "hip_train_dtype", None):
+        set_hip_train_dtype(model, args.hip_train_dtype)
     return model, num_prototypes

@@ -61,7 +61,8 @@ extern "C" {
  * decoded by the caller); the label queries (pipnet_*_label) are new.  The plain bf16 ConvNeXt
  * entry points (pipnet_conv2d_nhwc_bf16_mix + _label, pipnet_dwconv7_ln_bf16, pipnet_layernorm_bf16)
  * were added since, and so were the explanation-image entry points (pipnet_patch_compose_rgb8,
- * pipnet_draw_rects_rgb8) and the attribution-image entry points (pipnet_saliency_*); no signature changed. */
+ * pipnet_draw_rects_rgb8) and the attribution-image entry points (pipnet_saliency_*), and the row-scaled
+ * low-precision Linear2 (pipnet_linear_bf16_mix_rowscale, pipnet_linear_s3_rowscale + _label); no signature changed. */
 #define PIPNET_AMD_ABI_VERSION 4
 int pipnet_amd_abi_version(void);
 const char* pipnet_amd_status_string(int status);
@@ -218,6 +219,25 @@ int pipnet_layernorm_s3(const float* x, int64_t rows, int C, const float* w, con
 int pipnet_conv2d_nhwc_bf16_mix(const void* x, int B, int H, int W, int Cin, const void* w_packed,
                                 const float* bias, const float* scale, const float* R, int Cout, int KH, int KW,
                                 int stride, int pad, int epilogue, void* y, int tile, void* stream);
+
+/* The CNBlock's Linear2 * layer_scale + residual under torchvision's StochasticDepth("row") in train mode,
+ * on the low-precision operands -- what pipnet_linear_rowscale_f32 is to pipnet_linear_f32:
+ *   y[M,Cout] = R + row_scale[min(m, M-1) / rows_per_scale] * (scale * (x W^T + bias)),   fp32 y and R,
+ * R may equal y; rows_per_scale = H*W (one factor per sample), row_scale[b] = keep_b / (1 - p) -- 0 leaves a
+ * dropped sample's rows equal to R (bit for bit); the multiplication order is the fp32 entry's.  The dense
+ * 1x1 form only: x = [M,Cin] plain bf16 rows against a pipnet_pack_conv_weight_bf16 weight (_bf16_mix_), or
+ * [M,2 Cin] split planes against a split weight (_s3_), operands and tiles (-1, 0, 4, 5, 7) exactly as
+ * PIPNET_EPI_F32_RESID of pipnet_conv2d_nhwc_bf16_mix / pipnet_conv2d_nhwc_s3 takes them, so a block with
+ * p = 0 and a block with p > 0 share their tile and their K order.  scale, R and row_scale are required
+ * (row_scale: at least ceil(M / rows_per_scale) floats, not checked here); rows_per_scale > 0.  The kernels
+ * carry epilogue code 13 (PIPNET_EPI_F32_RESID_ROWSCALE, csrc/gemm_bf16_impl.hpp): no `epilogue` argument
+ * of this header accepts it. */
+int pipnet_linear_bf16_mix_rowscale(const void* x, int64_t M, int Cin, const void* w_packed, const float* bias,
+                                    const float* scale, const float* R, int Cout, const float* row_scale,
+                                    int rows_per_scale, void* y, int tile, void* stream);
+int pipnet_linear_s3_rowscale(const void* x, int64_t M, int Cin, const void* w_packed, const float* bias,
+                              const float* scale, const float* R, int Cout, const float* row_scale,
+                              int rows_per_scale, void* y, int tile, void* stream);
 
 /* pipnet_dwconv7_ln_f32 / pipnet_layernorm_f32 with the result rounded once (RNE) to bf16
  * ([B,H,W,C] / [rows,C]): bitwise the hi plane of the _s3 producers (one shared kernel body). */
@@ -446,7 +466,8 @@ int pipnet_conv2d_nhwc_bf16_plan(int B, int H, int W, int Cin, int Cout, int KH,
 /* Profiling labels: the name of the kernel a launch with these shape arguments runs, as rocprof and nm -C
  * print it (e.g. "pipnet_bf16::conv_bf16_pp_kernel<5, 0, 4, 0, 2>").  Each query runs the selection of its
  * launch (pipnet_linear_f32 and its rowscale / conv forms, splits > 1: the main kernel of the split-K
- * entries; pipnet_conv2d_nhwc_bf16_tile; pipnet_conv2d_nhwc_s3; pipnet_conv2d_nhwc_bf16_mix; pipnet_conv1x1_bf16_dual;
+ * entries; pipnet_conv2d_nhwc_bf16_tile; pipnet_conv2d_nhwc_s3; pipnet_conv2d_nhwc_bf16_mix;
+ * pipnet_linear_bf16_mix_rowscale; pipnet_linear_s3_rowscale; pipnet_conv1x1_bf16_dual;
  * pipnet_cnblock_mlp_hw_f32) on dense 16-B aligned operands, as the plan queries do, without a HIP call.
  * Writes the NUL-terminated label into buf[cap] and returns its length, or -PIPNET_ERR_ARG when the launch
  * would be refused or the label does not fit. */
@@ -457,6 +478,8 @@ int pipnet_conv2d_nhwc_s3_label(int B, int H, int W, int Cin, int Cout, int KH, 
                                 int epilogue, int tile, char* buf, int cap);
 int pipnet_conv2d_nhwc_bf16_mix_label(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
                                       int epilogue, int tile, char* buf, int cap);
+int pipnet_linear_bf16_mix_rowscale_label(int64_t M, int Cin, int Cout, int tile, char* buf, int cap);
+int pipnet_linear_s3_rowscale_label(int64_t M, int Cin, int Cout, int tile, char* buf, int cap);
 int pipnet_conv1x1_bf16_dual_label(int64_t M, int Cin, int N1, int N2, char* buf, int cap);
 int pipnet_cnblock_mlp_label(int64_t M, int C, int hw, char* buf, int cap);
 

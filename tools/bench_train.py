@@ -17,6 +17,10 @@ keeping the suffix activations, head / CNBlock / downsample backward kernels, Ad
 trainable tensor); torch = autograd through the same modules.
 
 Prints one JSON line per phase: images/s and ms per iteration for both.
+
+``--train-dtype fp32 bf16x3 bf16`` instead times the HIP step of both phases with its frozen layers in each of the
+given arithmetics (pipnet.set_hip_train_dtype: the whole backbone in finetune, features[:6] in joint), the arms
+alternated ``--repeats`` times in this process (tools/train_dtype_arms.py), and prints one JSON line per phase.
 """
 from __future__ import annotations
 
@@ -36,6 +40,7 @@ from count_pipnet_amd import train as T  # noqa: E402
 from count_pipnet_amd.backend import torch_backend  # noqa: E402
 from count_pipnet_amd.pipnet import get_pipnet  # noqa: E402
 from count_pipnet_amd.synthetic import fill_module_  # noqa: E402
+from train_dtype_arms import compare  # noqa: E402
 
 
 def build(dev, num_classes=200, joint=False):
@@ -120,14 +125,38 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--torch-steps", type=int, default=3)
+    ap.add_argument("--train-dtype", nargs="+", choices=("fp32", "bf16x3", "bf16"), default=None,
+                    help="time the HIP steps with their frozen layers in each of these, alternated in one process")
+    ap.add_argument("--phase", choices=("finetune", "joint", "both"), default="both",
+                    help="--train-dtype: the phase(s) this process times")
+    ap.add_argument("--repeats", type=int, default=3, help="--train-dtype: alternations of the arms")
+    ap.add_argument("--min-seconds", type=float, default=1.0, help="--train-dtype: device time of one timed run")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)
     xs1 = torch.randn(a.batch, 3, 224, 224, generator=g).to(dev)
     xs2 = torch.randn(a.batch, 3, 224, 224, generator=g).to(dev)
     ys = torch.randint(0, 200, (a.batch,), generator=g).to(dev)
-    net, opt = build(dev)
     sdg = torch.Generator().manual_seed(1)
+    if a.train_dtype:
+        for joint in [j for j in (False, True) if a.phase in ("both", "joint" if j else "finetune")]:
+            if joint:
+                net, opt, opt_net = build(dev, joint=True)
+                step = lambda: T.hip_train_step(net, xs1, xs2, ys, opt_net, opt, False, 1, 1, True, generator=sdg)  # noqa: E731
+            else:
+                net, opt = build(dev)
+                step = lambda: T.hip_finetune_step(net, xs1, xs2, ys, opt, True, generator=sdg)  # noqa: E731
+            arms = compare(net, step, a.train_dtype, 2 * a.batch, a.repeats, a.warmup, a.min_seconds)
+            print(json.dumps({
+                "metric": ("joint-phase (features.6-7 + classifier train, features[:6] frozen)" if joint else
+                           "finetune (classifier-only, whole backbone frozen)") +
+                          " iteration by frozen-layer dtype (ConvNeXt-tiny-26 PIP-Net, 224x224)",
+                "images_per_iteration": 2 * a.batch, "repeats": a.repeats, "min_seconds": a.min_seconds,
+                "frozen_units": T.trainable_suffix_start(net), "arms": arms}), flush=True)
+            del net, opt, step
+            torch.cuda.empty_cache()
+        return
+    net, opt = build(dev)
     hip_s = timed(lambda: T.hip_finetune_step(net, xs1, xs2, ys, opt, True, generator=sdg), a.steps, a.warmup)
     xs = torch.cat([xs1, xs2])
     fwd_s = timed(lambda: T.train_forward_hip(net, xs, T.stochastic_depth_masks(net._net.features, xs.shape[0], sdg)),

@@ -15,6 +15,10 @@ weights, fresh Philox Gumbel noise per forward.
   written inline here (same math, not the reference's code).
 
 Prints one JSON line per phase: images/s and ms per iteration for both.
+
+``--train-dtype fp32 bf16x3 bf16`` instead times the HIP step of both phases with its frozen layers in each of the
+given arithmetics (pipnet.set_hip_train_dtype: the whole backbone in finetune, the stem and stage 1 in joint), the
+arms alternated ``--repeats`` times in this process (tools/train_dtype_arms.py), and prints one JSON line per phase.
 """
 from __future__ import annotations
 
@@ -34,6 +38,7 @@ from count_pipnet_amd import train as T  # noqa: E402
 from count_pipnet_amd.backend import torch_backend  # noqa: E402
 from count_pipnet_amd.count_pipnet import get_count_network  # noqa: E402
 from count_pipnet_amd.synthetic import fill_module_  # noqa: E402
+from train_dtype_arms import compare  # noqa: E402
 
 NUM_CLASSES = 9
 
@@ -113,6 +118,12 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--torch-steps", type=int, default=3)
+    ap.add_argument("--train-dtype", nargs="+", choices=("fp32", "bf16x3", "bf16"), default=None,
+                    help="time the HIP steps with their frozen layers in each of these, alternated in one process")
+    ap.add_argument("--phase", choices=("finetune", "joint", "both"), default="both",
+                    help="--train-dtype: the phase(s) this process times")
+    ap.add_argument("--repeats", type=int, default=3, help="--train-dtype: alternations of the arms")
+    ap.add_argument("--min-seconds", type=float, default=1.0, help="--train-dtype: device time of one timed run")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)
@@ -121,7 +132,23 @@ def main():
     ys = torch.randint(0, NUM_CLASSES, (a.batch,), generator=g).to(dev)
     imgs = 2 * a.batch
     sdg = torch.Generator().manual_seed(1)
-    for joint in (False, True):
+    for joint in [j for j in (False, True) if a.train_dtype and a.phase in ("both", "joint" if j else "finetune")]:
+        net, opt_cls, opt_net = build(dev, joint)
+        if joint:
+            step = lambda: T.hip_count_train_step(net, xs1, xs2, ys, opt_net, opt_cls, False, 1, 1, True, 1.0,  # noqa: E731
+                                                  generator=sdg)
+        else:
+            step = lambda: T.hip_count_finetune_step(net, xs1, xs2, ys, opt_cls, True, 1.0, generator=sdg)  # noqa: E731
+        arms = compare(net, step, a.train_dtype, imgs, a.repeats, a.warmup, a.min_seconds)
+        print(json.dumps({
+            "metric": "CountPIPNet " + ("joint-phase (stages 2-3 + add-on + heads train, stem + stage 1 frozen)" if joint
+                                        else "finetune (classifier + bilinear intermediate, whole backbone frozen)") +
+                      f" iteration by frozen-layer dtype (C5: bilinear, P=2048, {a.size}x{a.size})",
+            "images_per_iteration": imgs, "repeats": a.repeats, "min_seconds": a.min_seconds,
+            "frozen_units": T.trainable_suffix_start(net), "arms": arms}), flush=True)
+        del net, opt_cls, opt_net, step
+        torch.cuda.empty_cache()
+    for joint in () if a.train_dtype else (False, True):
         net, opt_cls, opt_net = build(dev, joint)
         if joint:
             assert T.hip_count_train_supported(net)
