@@ -29,7 +29,8 @@ the reference (``net.module._classification``, ``net.module._num_classes`` in
 """
 from __future__ import annotations
 
-from typing import List, Optional, Tuple
+import contextlib
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
@@ -50,6 +51,16 @@ def shard_sizes(batch: int, world: int) -> List[int]:
         sizes.append(s)
         left -= s
     return sizes
+
+
+def dataset_shard(n: int, world: int, rank: int) -> Tuple[int, int]:
+    """(lo, hi) of rank ``rank``'s contiguous block of a dataset of ``n`` images under the ``shard_sizes`` rule
+    (``torch.chunk``); the last blocks may be empty (n = 5, world = 4: 2, 2, 1, 0)."""
+    if world < 1 or not 0 <= rank < world or n < 0:
+        raise ValueError(f"dataset_shard: rank {rank} of world {world}, {n} images")
+    sizes = shard_sizes(n, world)
+    lo = sum(sizes[:rank])
+    return lo, lo + sizes[rank]
 
 
 def _pad_rows(x: Tensor, rows: int) -> Tensor:
@@ -186,6 +197,112 @@ def gather_proto_features(proto: Tensor, sizes: List[int], group=None, to_root: 
         g = gather(proto.permute(0, 2, 3, 1), sizes, group)
         return g.permute(0, 3, 1, 2)
     return gather(proto.contiguous(), sizes, group)
+
+
+HEADER_PARAMS = 8                 # shape parameters a pass may put in its header
+_NAME_WORDS = 4                   # the failing exception's class name, 32 bytes of it
+_FIXED_WORDS = 6                  # first index, images seen, map height, map width, error code, flag
+_HEADER_WORDS = _FIXED_WORDS + HEADER_PARAMS + _NAME_WORDS
+
+
+class ShardedPass:
+    """The exchange of one dataset pass (``topk.prototype_topk``, ``stats.class_prototype_stats`` /
+    ``mean_intermediate_features``, ``purity.part_purity``) sharded over the ranks of ``group``: every rank
+    streams its own contiguous block of the dataset into a small state, then all ranks issue the same fixed
+    sequence of collectives -- never one per batch:
+
+      1. ``header``: ONE all-gather of a small int64 header per rank (first dataset index, images seen, latent
+         map size, the shape parameters the merge depends on, an error code);
+      2. ``gather_state``: ONE all-gather of the state packed into one byte buffer (``PackedState.pack``: fields
+         in descending element size, so every view into the gathered buffer stays aligned);
+      3. part purity in mode "all" only: ``gather_rows``, the kept rows through ``all_gather_rows``.
+
+    No rank may skip a collective the others enter: an exception inside a rank's batch loop (``guard``) is kept
+    and carried in the header; after the header exchange the failing rank re-raises it, every other rank raises
+    RuntimeError naming that rank and the exception's class, and nobody enters the state exchange.  The header
+    checks -- equal shape parameters, blocks contiguous and in rank order, one map size, at least one image in
+    total -- raise the same ValueError on every rank.  At world 1 nothing here issues a collective."""
+
+    def __init__(self, what: str, group, world: int, rank: int, device):
+        self.what, self.group, self.world, self.rank, self.device = what, group, world, rank, device
+        self.error: Optional[BaseException] = None
+        self.first: List[int] = []
+        self.seen: List[int] = []
+        self.total = 0
+        self.hw: Optional[Tuple[int, int]] = None
+        self.flag = False
+
+    @property
+    def sharded(self) -> bool:
+        return self.world > 1
+
+    @contextlib.contextmanager
+    def guard(self):
+        """Around a rank's batch loop: in sharded mode an exception is kept for the header instead of leaving
+        the other ranks alone in the next collective."""
+        try:
+            yield
+        except Exception as e:
+            if not self.sharded:
+                raise
+            self.error = e
+
+    def header(self, first_index: int, seen: int, hw: Optional[Tuple[int, int]], params: Sequence[int],
+               limit: Optional[int] = None, flag: bool = False) -> None:
+        """Exchange and check the headers; sets ``first`` / ``seen`` (per rank), ``total`` and ``hw`` (the map
+        size of the ranks that saw an image, None when the pass has none).  ``limit``: the global index the pass
+        cuts at (``max_images``); blocks behind it need not touch.  ``flag``: a device-side error flag of this
+        rank's pass (a label outside the mapping); ``self.flag`` is its OR over the ranks."""
+        if len(params) > HEADER_PARAMS:
+            raise RuntimeError(f"{self.what}: {len(params)} header parameters, at most {HEADER_PARAMS}")
+        name = b"" if self.error is None else type(self.error).__name__.encode()[:8 * _NAME_WORDS]
+        words = [int(first_index), int(seen), *((0, 0) if hw is None else map(int, hw)), int(self.error is not None),
+                 int(bool(flag)), *map(int, params), *([0] * (HEADER_PARAMS - len(params))),
+                 *[int.from_bytes(name[8 * i:8 * i + 8].ljust(8, b"\0"), "little", signed=True)
+                   for i in range(_NAME_WORDS)]]
+        mine = torch.tensor(words, dtype=torch.int64, device=self.device)
+        every = torch.empty((self.world * _HEADER_WORDS,), dtype=torch.int64, device=self.device)
+        dist.all_gather_into_tensor(every, mine, group=self.group)
+        rows = every.view(self.world, _HEADER_WORDS).tolist()
+        failed = [r for r, row in enumerate(rows) if row[4]]
+        if self.error is not None:
+            raise self.error
+        if failed:
+            r = failed[0]
+            cls = b"".join(int(v).to_bytes(8, "little", signed=True) for v in rows[r][_FIXED_WORDS + HEADER_PARAMS:])
+            raise RuntimeError(f"{self.what}: rank {r} failed inside its batch loop with "
+                               f"{cls.rstrip(bytes(1)).decode(errors='replace')}; no state was exchanged")
+        shapes = [tuple(row[_FIXED_WORDS:_FIXED_WORDS + HEADER_PARAMS]) for row in rows]
+        if any(s != shapes[0] for s in shapes):
+            raise ValueError(f"{self.what}: the ranks disagree on the shape parameters of the pass: {shapes}")
+        self.first, self.seen = [row[0] for row in rows], [row[1] for row in rows]
+        for r in range(self.world - 1):
+            end = self.first[r] + self.seen[r]
+            cut = limit is not None and end >= limit and self.first[r + 1] >= end
+            if self.first[r + 1] != end and not cut:
+                raise ValueError(f"{self.what}: the ranks' blocks are not contiguous in rank order: rank {r} saw "
+                                 f"images [{self.first[r]}, {end}), rank {r + 1} starts at {self.first[r + 1]}")
+        maps = sorted({(row[2], row[3]) for row in rows if row[1] > 0 and (row[2], row[3]) != (0, 0)})
+        if len(maps) > 1:
+            raise ValueError(f"{self.what}: the ranks disagree on the latent map size: {maps}")
+        self.hw = maps[0] if maps else None
+        self.total = sum(self.seen)
+        self.flag = any(row[5] for row in rows)
+
+    def gather_tensor(self, x: Tensor) -> Tensor:
+        """[world, ...]: every rank's ``x`` (one shape and dtype on all ranks) in rank order, ONE all-gather."""
+        x = x.contiguous()
+        every = torch.empty((self.world * x.numel(),), dtype=x.dtype, device=x.device)
+        dist.all_gather_into_tensor(every, x.view(-1), group=self.group)
+        return every.view((self.world,) + tuple(x.shape))
+
+    def gather_state(self, state) -> list:
+        """Every rank's ``state`` (a ``kernels.PackedState``), as views into ONE gathered buffer, in rank order."""
+        return [state.unpack(row) for row in self.gather_tensor(state.pack())]
+
+    def gather_rows(self, x: Tensor) -> Tensor:
+        """Every rank's rows (``seen[r]`` of them on rank r) concatenated in rank order."""
+        return all_gather_rows(x, self.seen, self.group)
 
 
 def init_from_env(backend: Optional[str] = None, device_index: Optional[int] = None) -> Tuple[int, int, torch.device]:

@@ -4,6 +4,7 @@ each prototype fires, the image patch of a latent location, and the ``.cpu()`` o
 from __future__ import annotations
 
 import argparse
+import numbers
 from collections import namedtuple
 from dataclasses import fields, replace
 from typing import Optional, Tuple
@@ -34,6 +35,33 @@ def unwrap(net, what: str):
                                "(the dataset index is the running image count of one pass)")
         net = net.module
     return net
+
+
+def unwrap_sharded(net, process_group, what: str):
+    """(bare module, group, world, rank) for the passes that stream the whole dataset and shard over ranks
+    (``prototype_topk``, ``class_prototype_stats``, ``mean_intermediate_features``, ``part_purity``): the group
+    is ``process_group`` when given, else that of the ShardedInference around the net; world 1, rank 0 without
+    either (or without an initialised process group)."""
+    import torch.distributed as dist
+    from .dist import ShardedInference
+    group, wrapped = process_group, False
+    while hasattr(net, "module"):
+        if isinstance(net, ShardedInference):
+            wrapped = True
+            if group is None:
+                group = net.process_group
+        net = net.module
+    if not (wrapped or process_group is not None) or not (dist.is_available() and dist.is_initialized()):
+        return net, None, 1, 0
+    return net, group, dist.get_world_size(group), dist.get_rank(group)
+
+
+def check_first_index(first_index, what: str) -> int:
+    """``first_index`` of a dataset pass as an int: the dataset index of the first image its loader yields."""
+    if isinstance(first_index, bool) or not isinstance(first_index, numbers.Integral) or first_index < 0:
+        raise ValueError(f"{what}: first_index must be a non-negative integer (the dataset index of the loader's "
+                         f"first image), got {first_index!r}")
+    return int(first_index)
 
 
 def is_count(net) -> bool:

@@ -8,6 +8,7 @@ here computes on the host.
 from __future__ import annotations
 
 import contextlib
+import copy
 import ctypes
 import functools
 import threading
@@ -851,11 +852,79 @@ def map_argmax(map_nhwc: Tensor, out=None) -> Tuple[Tensor, Tensor]:
 
 
 TOPK_MAX_K = _lib.CONSTANTS["TOPK_MAX_K"]
+STATE_MERGE_MAX_RANKS = _lib.CONSTANTS["STATE_MERGE_MAX_RANKS"]
 
 
-class TopkState:
+class PackedState:
+    """What the states of the dataset passes share when ranks exchange them: ``PACK`` names the tensors in
+    descending element size, so that in ``pack()``'s byte buffer (padded to a multiple of 8) every field stays
+    aligned, and ``unpack`` reads a state of this one's dimensions back out of such a buffer as views."""
+    PACK: Tuple[str, ...] = ()
+
+    def packed_bytes(self) -> int:
+        n = sum(getattr(self, f).numel() * getattr(self, f).element_size() for f in self.PACK)
+        return -(-n // 8) * 8
+
+    def pack(self) -> Tensor:
+        parts = [getattr(self, f).contiguous().view(-1).view(torch.uint8) for f in self.PACK]
+        pad = self.packed_bytes() - sum(p.numel() for p in parts)
+        if pad:
+            parts.append(torch.zeros(pad, dtype=torch.uint8, device=parts[0].device))
+        return torch.cat(parts)
+
+    def unpack(self, buf: Tensor):
+        if buf.dtype != torch.uint8 or buf.dim() != 1 or buf.numel() != self.packed_bytes() or not buf.is_contiguous():
+            raise RuntimeError(f"{type(self).__name__}.unpack: needs {self.packed_bytes()} contiguous uint8 bytes "
+                               f"(got {buf.dtype} {tuple(buf.shape)})")
+        out = copy.copy(self)
+        at = 0
+        for f in self.PACK:
+            t = getattr(self, f)
+            n = t.numel() * t.element_size()
+            setattr(out, f, buf[at:at + n].view(t.dtype).view(t.shape))
+            at += n
+        return out
+
+
+def _merge_operands(fn: str, states, cls, dims: Tuple[str, ...]):
+    """The checked inputs of a state merge: ``states`` is a non-empty sequence of ``cls`` states of equal ``dims``
+    on one device.  Returns (states, byte stride between consecutive ranks, common to every field): states that
+    already are views into one gathered buffer are taken as they lie, anything else is packed into one first."""
+    states = list(states)
+    if not states:
+        raise RuntimeError(f"{fn}: needs at least one state (W = 0)")
+    if len(states) > STATE_MERGE_MAX_RANKS:
+        raise RuntimeError(f"{fn}: {len(states)} states, at most {STATE_MERGE_MAX_RANKS} are merged in one call")
+    s0 = states[0]
+    dev = getattr(s0, cls.PACK[0]).device
+    for r, s in enumerate(states):
+        if not isinstance(s, cls):
+            raise RuntimeError(f"{fn}: state {r} is a {type(s).__name__}, expected {cls.__name__}")
+        if any(getattr(s, d) != getattr(s0, d) for d in dims):
+            raise RuntimeError(f"{fn}: state {r} has {[(d, getattr(s, d)) for d in dims]}, state 0 "
+                               f"{[(d, getattr(s0, d)) for d in dims]}")
+        for f in cls.PACK:
+            t, t0 = getattr(s, f), getattr(s0, f)
+            if t.device != dev or t.dtype != t0.dtype or t.shape != t0.shape or not t.is_contiguous():
+                raise RuntimeError(f"{fn}: {f} of state {r} is {t.dtype} {tuple(t.shape)} (stride {t.stride()}) on "
+                                   f"{t.device}, state 0 holds contiguous {t0.dtype} {tuple(t0.shape)} on {dev}")
+    if len(states) == 1 or dev.type != "cuda":
+        return states, 0
+    live = [f for f in cls.PACK if getattr(s0, f).numel()]
+    d = getattr(states[1], live[0]).data_ptr() - getattr(s0, live[0]).data_ptr()
+    lie = d > 0 and d % 8 == 0 and all(
+        getattr(s, f).is_contiguous() and getattr(s, f).data_ptr() - getattr(s0, f).data_ptr() == r * d
+        for r, s in enumerate(states) for f in live)
+    if not lie:
+        buf = torch.stack([s.pack() for s in states])
+        states, d = [s0.unpack(row) for row in buf], buf.stride(0)
+    return states, d
+
+
+class TopkState(PackedState):
     """Device state of the streaming top-k (pipnet_topk_update): per (group, prototype) the k best
     (score, dataset index, loc) so far, the fill counts and the abstain counter."""
+    PACK = ("index", "abstained", "score", "loc", "fill")
 
     def __init__(self, groups: int, prototypes: int, k: int, device):
         if not 1 <= k <= TOPK_MAX_K:
@@ -894,14 +963,55 @@ def topk_update(state: TopkState, score: Tensor, loc: Tensor, i0: int, group: Op
     return state
 
 
+def _torch_topk_merge(states, out: TopkState) -> TopkState:
+    """pipnet_topk_merge with torch ops: the union's entries by (score descending, index ascending), empty
+    slots last -- three stable sorts, least significant key first."""
+    k = out.k
+    score = torch.cat([s.score for s in states], dim=2)
+    index = torch.cat([s.index for s in states], dim=2)
+    loc = torch.cat([s.loc for s in states], dim=2)
+    slot = torch.arange(k, device=score.device)
+    empty = torch.cat([slot >= s.fill.clamp(0, k)[:, :, None] for s in states], dim=2)
+    order = torch.sort(index, dim=2, stable=True).indices
+    order = order.gather(2, torch.sort(score.gather(2, order), dim=2, descending=True, stable=True).indices)
+    order = order.gather(2, torch.sort(empty.gather(2, order).to(torch.uint8), dim=2, stable=True).indices)[:, :, :k]
+    fill = torch.stack([s.fill.clamp(0, k) for s in states]).sum(dim=0).clamp(max=k).to(torch.int32)
+    unused = slot >= fill[:, :, None]
+    out.score.copy_(score.gather(2, order).masked_fill(unused, 0.0))
+    out.index.copy_(index.gather(2, order).masked_fill(unused, -1))
+    out.loc.copy_(loc.gather(2, order).masked_fill(unused, -1))
+    out.fill.copy_(fill)
+    out.abstained.copy_(torch.stack([s.abstained for s in states]).sum(dim=0))
+    return out
+
+
+def topk_merge(states) -> TopkState:
+    """The top-k state of the whole dataset from the states of its blocks (``states``: a sequence of TopkState
+    of equal groups / prototypes / k on one device, one per rank, each updated with its block's dataset
+    indices): per (group, prototype) the k best of the union by (score descending, dataset index ascending),
+    fill = min(k, sum of fills), the abstain counters added.  Bit for bit the state of one pass over all blocks.
+    States that are views into one gathered buffer are read where they lie; one kernel, no host sync.  CPU
+    states: the same rule by torch ops."""
+    states, stride = _merge_operands("topk_merge", states, TopkState, ("groups", "prototypes", "k"))
+    s0 = states[0]
+    out = TopkState(s0.groups, s0.prototypes, s0.k, s0.score.device)
+    if not s0.score.is_cuda:
+        return _torch_topk_merge(states, out)
+    _lib.call("pipnet_topk_merge", s0.score.data_ptr(), s0.index.data_ptr(), s0.loc.data_ptr(), s0.fill.data_ptr(),
+              s0.abstained.data_ptr(), stride, len(states), s0.groups, s0.prototypes, s0.k, out.score.data_ptr(),
+              out.index.data_ptr(), out.loc.data_ptr(), out.fill.data_ptr(), out.abstained.data_ptr(), _stream(s0.score))
+    return out
+
+
 PROTO_STATS_MAX_BINS = _lib.CONSTANTS["PROTO_STATS_MAX_BINS"]
 
 
-class ProtoStatsState:
+class ProtoStatsState(PackedState):
     """Device state of the streaming class-conditional statistics (pipnet_proto_stats_update_f32):
     per (class, prototype) the counters, fp64 sums, maximum and histogram so far, the images per
     class and the count of labels outside [0, classes).  ``edges``: ascending fp32 [NB + 1], or
     None for no histogram."""
+    PACK = ("n_class", "n_ge", "n_gt", "total", "total_gt", "bad", "vmax", "hist")
 
     def __init__(self, classes: int, prototypes: int, threshold: float, edges: Optional[Tensor], device):
         if classes < 1 or prototypes < 1:
@@ -960,14 +1070,62 @@ def colsum_accum_f64(acc: Tensor, x: Tensor) -> Tensor:
     return acc
 
 
+def proto_stats_merge(states) -> ProtoStatsState:
+    """The statistics of the whole dataset from the states of its blocks (``states``: a sequence of
+    ProtoStatsState of equal classes / prototypes / bins on one device, one per rank in rank order; threshold
+    and edges are state 0's): the counters, the histogram and ``bad`` are integer sums, ``vmax`` the maximum,
+    ``total`` / ``total_gt`` the ranks' fp64 sums added in rank order by one owner thread per entry -- bitwise
+    the one-pass sums when the addends are integers, else within 2 (n + W) 2^-53 of them (relative to the sum
+    of |x|): they depend on the partition in the last bits.  One kernel, no host sync; CPU states: the same
+    rule by torch ops in the same order."""
+    states, stride = _merge_operands("proto_stats_merge", states, ProtoStatsState, ("classes", "prototypes", "bins"))
+    s0 = states[0]
+    out = ProtoStatsState(s0.classes, s0.prototypes, s0.threshold, s0.edges, s0.n_ge.device)
+    if not s0.n_ge.is_cuda:
+        for f in ("n_class", "n_ge", "n_gt", "total", "total_gt", "hist", "bad"):
+            acc = getattr(s0, f).clone()
+            for s in states[1:]:                    # rank order: the kernel's chain of fp64 adds
+                acc += getattr(s, f)
+            getattr(out, f).copy_(acc)
+        for s in states:
+            torch.fmax(out.vmax, s.vmax, out=out.vmax)
+        return out
+    _lib.call("pipnet_proto_stats_merge", *[t.data_ptr() for t in s0.tensors()], stride, len(states), s0.classes,
+              s0.prototypes, s0.bins, *[t.data_ptr() for t in out.tensors()], _stream(s0.n_ge))
+    return out
+
+
+def colsum_merge_f64(accs: Tensor) -> Tensor:
+    """[D] float64 = accs [W,D] float64 (the ranks' ``colsum_accum_f64`` accumulators, any row stride that is a
+    multiple of 8 bytes) added in rank order by one owner thread per column.  One kernel, no host sync; a CPU
+    tensor: the same chain by torch ops."""
+    if accs.dim() != 2 or accs.dtype != torch.float64 or accs.shape[0] < 1 or accs.shape[1] < 1:
+        raise RuntimeError(f"colsum_merge_f64: needs a [W >= 1, D >= 1] float64 tensor, got {accs.dtype} "
+                           f"{tuple(accs.shape)}")
+    w, d = accs.shape
+    if w > STATE_MERGE_MAX_RANKS:
+        raise RuntimeError(f"colsum_merge_f64: {w} rows, at most {STATE_MERGE_MAX_RANKS} are merged in one call")
+    if not accs.is_cuda:
+        out = accs[0].clone()
+        for r in range(1, w):
+            out += accs[r]
+        return out
+    _operand("colsum_merge_f64", "accs", accs, dtype=torch.float64, layout="rows")
+    out = torch.empty((d,), device=accs.device, dtype=torch.float64)
+    _lib.call("pipnet_colsum_merge_f64", accs.data_ptr(), accs.stride(0) * 8 if w > 1 else 0, w, d, out.data_ptr(),
+              _stream(accs))
+    return out
+
+
 PART_PURITY_MAX_PARTS = _lib.CONSTANTS["PART_PURITY_MAX_PARTS"]
 
 
-class PartPurityState:
+class PartPurityState(PackedState):
     """Device state of the part-purity evaluation (pipnet_part_purity_update / _rows): per
     (prototype, merged part) the rows in which the part is visible, those in which it lies in the
     patch and the key of its first appearance; the rows per prototype; the count of dataset indices
     outside the annotation table.  All integer."""
+    PACK = ("n", "hits", "first_key", "rows", "bad")
 
     def __init__(self, prototypes: int, merged_parts: int, device):
         if prototypes < 1 or not 1 <= merged_parts <= PART_PURITY_MAX_PARTS:
@@ -1038,6 +1196,27 @@ def part_purity_rows(state: PartPurityState, index: Tensor, loc: Tensor, relevan
             lambda: _lib.call("pipnet_part_purity_rows", index.data_ptr(), loc.data_ptr(), relevant.data_ptr(),
                               state.prototypes, index.shape[1], *tail, _stream(index)))
     return state
+
+
+def part_purity_merge(states) -> PartPurityState:
+    """The mode-"all" part-purity state of the whole dataset from the states of its blocks (``states``: a
+    sequence of PartPurityState of equal prototypes / merged parts on one device, one per rank, each updated
+    with its block's dataset indices): ``n`` / ``hits`` / ``rows`` / ``bad`` are integer sums, ``first_key`` the
+    unsigned minimum (keys hold the global row ordinal; all ones: never inserted).  All integer: bitwise the
+    state of one pass.  One kernel, no host sync; CPU states: the same rule by torch ops."""
+    states, stride = _merge_operands("part_purity_merge", states, PartPurityState, ("prototypes", "merged_parts"))
+    s0 = states[0]
+    out = PartPurityState(s0.prototypes, s0.merged_parts, s0.n.device)
+    if not s0.n.is_cuda:
+        flip = torch.iinfo(torch.int64).min                 # x ^ flip orders int64 bits as uint64
+        for f in ("n", "hits", "rows", "bad"):
+            getattr(out, f).copy_(torch.stack([getattr(s, f) for s in states]).sum(dim=0))
+        out.first_key.copy_(torch.stack([s.first_key ^ flip for s in states]).amin(dim=0) ^ flip)
+        return out
+    _launch("part_purity_merge_kernel", 0.0,
+            lambda: _lib.call("pipnet_part_purity_merge", *[t.data_ptr() for t in s0.tensors()], stride, len(states),
+                              s0.prototypes, s0.merged_parts, *[t.data_ptr() for t in out.tensors()], _stream(s0.n)))
+    return out
 
 
 def part_purity_finish(state: PartPurityState):

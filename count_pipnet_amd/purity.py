@@ -29,8 +29,9 @@ import torch
 from torch import Tensor
 
 from . import kernels as K
-from .explain_forward import (PATCH_SIZE, HostCopy, img_coordinates, is_count, located_forward, patch_skip, small_map,
-                              unwrap)
+from .dist import ShardedPass
+from .explain_forward import (PATCH_SIZE, HostCopy, check_first_index, img_coordinates, is_count, located_forward,
+                              patch_skip, small_map, unwrap_sharded)
 
 CSV_HEADER = ["prototype", "img name", "h_min_224", "h_max_224", "w_min_224", "w_max_224"]
 
@@ -236,7 +237,8 @@ def _geometry(h: int, w: int, image_size: int):
 
 
 def part_purity(net, loader, annotations: PartAnnotations, *, image_size: int, mode: str = "all",
-                threshold: float = 0.5, k: int = 10, relevance_threshold: float = 1e-5) -> PartPurity:
+                threshold: float = 0.5, k: int = 10, relevance_threshold: float = 1e-5, first_index: int = 0,
+                process_group=None) -> PartPurity:
     """One pass over ``loader`` ((images, labels) batches of any size, in dataset order; image n of
     the pass is image n of ``annotations``): the part purity of every relevant prototype as
     util/eval_cub_csv.py evaluates it -- mode "all" over the rows of ``get_proto_patches_cub`` (raw
@@ -244,12 +246,23 @@ def part_purity(net, loader, annotations: PartAnnotations, *, image_size: int, m
     of largest raw pooled score, earlier image first among equals).
 
     ``net``: a PIPNet on a ROCm device (fp32 or bf16 build), bare, under a ``.module`` wrapper, or
-    in a world-size-1 ShardedInference; it is put in eval mode.  A CountPIPNet raises
-    NotImplementedError.  Every image gets the bits of its batch-1 forward, so the result does not
-    depend on the batch size.  Nothing inside the batch loop waits for the device."""
+    in a ShardedInference; it is put in eval mode.  A CountPIPNet raises NotImplementedError.  Every
+    image gets the bits of its batch-1 forward, so the result does not depend on the batch size.
+    Nothing inside the batch loop waits for the device.
+
+    ``first_index``: the dataset index of the first image this loader yields (image n of the pass is
+    image ``first_index + n`` of ``annotations``, which always cover the whole dataset).  In a
+    ShardedInference of more than one rank (or with ``process_group`` naming such a group around a bare
+    net) the pass is sharded: every rank passes the loader of its own contiguous block
+    (``dist.dataset_shard``, a block may be empty) and that block's ``first_index``.  Mode "topk"
+    merges the ranks' top-k lists (``kernels.topk_merge``) and evaluates their rows on every rank; mode
+    "all" merges the integer purity states (``kernels.part_purity_merge``) and gathers the kept rows in
+    rank order.  Every rank returns the result of one process over the whole dataset, bit for bit;
+    ``images`` is the total, which must equal ``annotations.images``."""
     if mode not in ("all", "topk"):
         raise ValueError(f"part_purity: mode must be 'all' or 'topk', got {mode!r}")
-    net = unwrap(net, "part_purity")
+    net, pgroup, world, rank = unwrap_sharded(net, process_group, "part_purity")
+    first_index = check_first_index(first_index, "part_purity")
     if is_count(net):
         raise NotImplementedError("part_purity: CountPIPNet is not supported (the reference's evaluation reads "
                                   "PIP-Net's pooled softmax scores); pass a PIPNet")
@@ -257,10 +270,11 @@ def part_purity(net, loader, annotations: PartAnnotations, *, image_size: int, m
         raise ValueError(f"part_purity: image_size {image_size} is smaller than the {PATCH_SIZE}-pixel patch")
     net.eval()
     n_img = annotations.images
-    ds = getattr(loader, "dataset", None)
-    if ds is not None and hasattr(ds, "__len__") and len(ds) != n_img:
-        raise ValueError(f"part_purity: the loader's dataset has {len(ds)} images, the annotations {n_img}")
     dev = next(net.parameters()).device
+    ex = ShardedPass("part_purity", pgroup, world, rank, dev)
+    ds = getattr(loader, "dataset", None)
+    if not ex.sharded and first_index == 0 and ds is not None and hasattr(ds, "__len__") and len(ds) != n_img:
+        raise ValueError(f"part_purity: the loader's dataset has {len(ds)} images, the annotations {n_img}")
     pn = net._num_prototypes
     ann = annotations.to(dev)
     state = K.PartPurityState(pn, len(annotations.merged_names), dev)
@@ -270,18 +284,31 @@ def part_purity(net, loader, annotations: PartAnnotations, *, image_size: int, m
         relevant_b = net._classification.weight.max(dim=0).values > relevance_threshold
         relevant = relevant_b.to(torch.uint8).contiguous()
         seen, hw, geo = 0, None, None
-        for xs, _ in loader:
-            xs = xs.to(dev, non_blocking=True)
-            K.require_device(xs, "input images")
-            _, loc, _, hw, raw = located_forward(net, xs, small_map(hw), with_raw=True)
-            if geo is None:
-                geo = _geometry(hw[0], hw[1], image_size)
-            if mode == "all":
-                K.part_purity_update(state, raw, loc, relevant, seen, threshold, geo, ann.table())
-                kept.append(torch.where((raw.double() > threshold) & relevant_b, loc, torch.full_like(loc, -1)))
-            else:
-                K.topk_update(tstate, raw, loc, seen)
-            seen += xs.shape[0]
+        with ex.guard():
+            for xs, _ in loader:
+                xs = xs.to(dev, non_blocking=True)
+                K.require_device(xs, "input images")
+                _, loc, _, hw, raw = located_forward(net, xs, small_map(hw), with_raw=True)
+                if geo is None:
+                    geo = _geometry(hw[0], hw[1], image_size)
+                if mode == "all":
+                    K.part_purity_update(state, raw, loc, relevant, first_index + seen, threshold, geo, ann.table())
+                    kept.append(torch.where((raw.double() > threshold) & relevant_b, loc, torch.full_like(loc, -1)))
+                else:
+                    K.topk_update(tstate, raw, loc, first_index + seen)
+                seen += xs.shape[0]
+        if ex.sharded:          # one header exchange, one state exchange ("all": and the kept rows)
+            ex.header(first_index, seen, hw, (pn, state.merged_parts, k if mode == "topk" else 0, int(mode == "topk")))
+            hw = ex.hw
+            if hw is not None:
+                geo = _geometry(hw[0], hw[1], image_size)           # an empty rank learns the map size here
+                if mode == "topk":
+                    tstate = K.topk_merge(ex.gather_state(tstate))
+                else:
+                    state = K.part_purity_merge(ex.gather_state(state))
+                    kept = [ex.gather_rows(torch.cat(kept) if kept else
+                                           torch.empty((0, pn), device=dev, dtype=torch.int32))]
+                seen = ex.total
         if hw is None:
             raise ValueError("part_purity: the loader yielded no batch")
         if mode == "topk":
@@ -290,8 +317,9 @@ def part_purity(net, loader, annotations: PartAnnotations, *, image_size: int, m
         else:
             row_index, row_loc = None, torch.cat(kept)
         res = K.part_purity_finish(state)
-    if seen != n_img or int(state.bad) != 0:
-        raise ValueError(f"part_purity: the pass saw {seen} images, the annotations hold {n_img}")
+    first = ex.first[0] if ex.sharded else first_index      # the pass must end where the annotations end
+    if first + seen != n_img or int(state.bad) != 0:
+        raise ValueError(f"part_purity: the pass saw {seen} images from index {first}, the annotations hold {n_img}")
     in_csv, max_purity, max_part, max_sum, most_part, most_sum, most_purity, purity = res
     return PartPurity(mode=mode, n=state.n, hits=state.hits, first_key=state.first_key, rows=state.rows, in_csv=in_csv,
                       max_purity=max_purity, max_part=max_part, max_sum=max_sum, most_part=most_part,

@@ -26,7 +26,8 @@ from torch import Tensor
 
 from . import kernels as K
 from .backend import use_hip
-from .explain_forward import HostCopy, is_count, unwrap
+from .dist import ShardedPass
+from .explain_forward import HostCopy, check_first_index, is_count, unwrap_sharded
 
 NEAR_ZERO_THRESHOLD = 0.01      # histograms.py:395
 PIPNET_BINS = 50                # histograms.py:397 num_bins_continuous
@@ -162,13 +163,23 @@ def _pass(net, loader, max_images: Optional[int], inference: bool, consume, what
 
 def class_prototype_stats(net, loader, *, num_classes: Optional[int] = None, max_images: Optional[int] = 10000,
                           continuous: bool = False, near_zero_threshold: float = NEAR_ZERO_THRESHOLD,
-                          edges=None) -> PrototypeClassStats:
+                          edges=None, first_index: int = 0, process_group=None) -> PrototypeClassStats:
     """One pass over ``loader`` ((images, labels) batches of any size, in dataset order): per
     (class, prototype) the counters, sums, maximum and histogram every figure and report of
     util/histograms.py is computed from.
 
-    ``net``: a PIPNet / CountPIPNet, bare, under a ``.module`` wrapper, or in a world-size-1
-    ShardedInference; it is put in eval mode, as the reference does.  The forward mode is
+    ``net``: a PIPNet / CountPIPNet, bare, under a ``.module`` wrapper, or in a ShardedInference; it
+    is put in eval mode, as the reference does.  ``first_index`` is the dataset index of the first
+    image this loader yields; ``max_images`` cuts at that global index.  In a ShardedInference of more
+    than one rank (or with ``process_group`` naming such a group around a bare net) the pass is
+    sharded: every rank passes the loader of its own contiguous block (``dist.dataset_shard``, a block
+    may be empty) and that block's ``first_index``; the states are exchanged once and merged
+    (``kernels.proto_stats_merge``) and every rank returns the statistics of the whole dataset, with
+    ``images`` the total.  Every integer field, ``hist`` and ``vmax`` are then bitwise those of one
+    process; ``total`` / ``total_gt`` are the ranks' fp64 sums added in rank order, bitwise the
+    one-process sums for integer-valued activations (discrete counts) and otherwise within
+    2 (n + W) 2^-53 of them, relative (n images of the class, W ranks): the sharded sums depend on the
+    partition in their last bits, the one-process sums never on the batching.  The forward mode is
     ``histograms.net_forward``'s (:50-60): PIP-Net and discrete CountPIPNet run with
     ``inference=True``; ``continuous=True`` reads a CountPIPNet's raw counts (``inference=False``,
     the reference's ``plot_always_histograms``).  ``max_images`` cuts the last batch (None: no limit).
@@ -178,7 +189,8 @@ def class_prototype_stats(net, loader, *, num_classes: Optional[int] = None, max
     the result carries ``vmax`` for a second pass).  A label outside [0, num_classes) raises
     ValueError after the pass.  On a ROCm device the statistics are accumulated by one HIP kernel
     per batch; under ``torch_backend()`` or for a CPU net by torch ops in the same order."""
-    net = unwrap(net, "class_prototype_stats")
+    net, pgroup, world, rank = unwrap_sharded(net, process_group, "class_prototype_stats")
+    first_index = check_first_index(first_index, "class_prototype_stats")
     net.eval()
     count = is_count(net)
     if continuous and not count:
@@ -197,8 +209,17 @@ def class_prototype_stats(net, loader, *, num_classes: Optional[int] = None, max
         else:
             _torch_update(state, pooled, ys)
 
-    with torch.no_grad():
-        seen = _pass(net, loader, max_images, not (count and continuous), consume, "class_prototype_stats")
+    ex = ShardedPass("class_prototype_stats", pgroup, world, rank, dev)
+    seen = 0
+    with torch.no_grad(), ex.guard():
+        seen = _pass(net, loader, None if max_images is None else max(0, max_images - first_index),
+                     not (count and continuous), consume, "class_prototype_stats")
+    if ex.sharded:              # one header exchange, one state exchange; every rank holds the merged state
+        ex.header(first_index, seen, None, (kc, net._num_prototypes, state.bins, int(count), int(continuous),
+                                            -1 if max_images is None else max_images), limit=max_images)
+        seen = ex.total
+        if seen:
+            state = K.proto_stats_merge(ex.gather_state(state))
     if seen == 0:
         raise ValueError("class_prototype_stats: the loader yielded no image")
     bad = int(state.bad)
@@ -209,13 +230,17 @@ def class_prototype_stats(net, loader, *, num_classes: Optional[int] = None, max
                                threshold=state.threshold, images=seen)
 
 
-def mean_intermediate_features(net, loader) -> Tensor:
+def mean_intermediate_features(net, loader, *, first_index: int = 0, process_group=None) -> Tensor:
     """[D] float32 mean of ``net._intermediate(clamped_counts)`` over the dataset
     (count_pipnet.py:226-281), streamed: per batch the fp64 column sums are added in image order
     (pipnet_colsum_accum_f64), so no batch's counts are kept and the result does not depend on
-    the batching."""
+    the batching.  ``first_index`` / ``process_group``: as in ``class_prototype_stats``; sharded,
+    the ranks' [D] fp64 accumulators are added in rank order (``kernels.colsum_merge_f64``) and
+    divided by the total: bitwise the one-process mean where the layer's outputs are integers (one-hot
+    codes), else within 2 (n + W) 2^-53 * sum|x| / n of it."""
     from .count_pipnet import intermediate_hip
-    net = unwrap(net, "mean_intermediate_features")
+    net, pgroup, world, rank = unwrap_sharded(net, process_group, "mean_intermediate_features")
+    first_index = check_first_index(first_index, "mean_intermediate_features")
     net.eval()
     if not is_count(net):
         raise ValueError("mean_intermediate_features: needs a CountPIPNet")
@@ -231,25 +256,36 @@ def mean_intermediate_features(net, loader) -> Tensor:
             for row in inter.double():
                 acc[0] += row
 
-    with torch.no_grad():
+    dev = next(net.parameters()).device
+    ex = ShardedPass("mean_intermediate_features", pgroup, world, rank, dev)
+    seen = 0
+    with torch.no_grad(), ex.guard():
         seen = _pass(net, loader, None, True, consume, "mean_intermediate_features")
+    if ex.sharded:              # the width D travels in the header's map slot: an empty rank learns it there
+        ex.header(first_index, seen, (1, acc[0].numel()) if acc else None, (net._num_prototypes,))
+        seen = ex.total
+        if seen:
+            mine = acc[0] if acc else torch.zeros(ex.hw[1], device=dev, dtype=torch.float64)
+            acc = [K.colsum_merge_f64(ex.gather_tensor(mine))]
     if seen == 0:
         raise ValueError("mean_intermediate_features: the loader yielded no image")
     return (acc[0] / seen).float()
 
 
-def virtual_weights(net, loader=None, custom_onehot_scale: bool = False) -> Tensor:
+def virtual_weights(net, loader=None, custom_onehot_scale: bool = False, *, first_index: int = 0,
+                    process_group=None) -> Tensor:
     """[K, P] virtual classification matrix of a CountPIPNet (count_pipnet.py:283-321): column p is
     ``get_prototype_importance_per_class(p, scalars)``; ``scalars`` are the dataset's mean
     intermediate features for a one-hot intermediate layer with ``custom_onehot_scale`` (that
-    needs ``loader``), else None."""
+    needs ``loader``), else None.  ``first_index`` / ``process_group`` go to ``mean_intermediate_features``."""
     from .count_pipnet_utils import OneHotEncoder
     from .local import count_importance_matrix
-    net = unwrap(net, "virtual_weights")
+    wrapped = net
+    net = unwrap_sharded(net, process_group, "virtual_weights")[0]
     scalars = None
     if custom_onehot_scale and isinstance(net._intermediate, OneHotEncoder):
         if loader is None:
             raise ValueError("virtual_weights: custom_onehot_scale needs a loader for the dataset mean")
-        scalars = mean_intermediate_features(net, loader)
+        scalars = mean_intermediate_features(wrapped, loader, first_index=first_index, process_group=process_group)
     with torch.no_grad():
         return count_importance_matrix(net, scalars)

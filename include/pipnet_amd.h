@@ -62,7 +62,9 @@ extern "C" {
  * entry points (pipnet_conv2d_nhwc_bf16_mix + _label, pipnet_dwconv7_ln_bf16, pipnet_layernorm_bf16)
  * were added since, and so were the explanation-image entry points (pipnet_patch_compose_rgb8,
  * pipnet_draw_rects_rgb8) and the attribution-image entry points (pipnet_saliency_*), and the row-scaled
- * low-precision Linear2 (pipnet_linear_bf16_mix_rowscale, pipnet_linear_s3_rowscale + _label); no signature changed. */
+ * low-precision Linear2 (pipnet_linear_bf16_mix_rowscale, pipnet_linear_s3_rowscale + _label), and the state
+ * merges of the sharded dataset passes (pipnet_topk_merge, pipnet_proto_stats_merge, pipnet_colsum_merge_f64,
+ * pipnet_part_purity_merge); no signature changed. */
 #define PIPNET_AMD_ABI_VERSION 4
 int pipnet_amd_abi_version(void);
 const char* pipnet_amd_status_string(int status);
@@ -862,6 +864,41 @@ int pipnet_part_purity_finish(const int64_t* n, const int64_t* hits, const uint6
                               int P, int M, uint8_t* in_csv, double* max_purity, int32_t* max_part, int64_t* max_sum,
                               int32_t* most_part, int64_t* most_sum, double* most_purity, double* purity,
                               void* stream);
+
+/* ---- merges of the per-rank states of the dataset passes (csrc/state_merge.hip) --------------------
+ * When the top-k, statistics and part-purity passes are sharded over ranks (contiguous blocks of the
+ * dataset in rank order), each rank's state is all-gathered once and merged into the state one process
+ * reaches over the whole dataset.  Every input pointer is rank 0's field; field f of rank r lies
+ * rank_stride BYTES further per rank (one stride for all fields: a gathered buffer of W packed states;
+ * a multiple of 8, not read at W == 1).  The out_* state is separate memory of one state's shapes.
+ * One owner thread per output entry, plain loads in rank order r = 0 .. W-1 and one store; no atomic.
+ * pipnet_topk_merge: per (group, prototype) the k best of the union of the ranks' lists by (score
+ *   descending, dataset index ascending) -- a W-way merge of the sorted lists, heads in LDS --
+ *   out_fill = min(k, sum of fill), empty slots score 0 / index -1 / loc -1, out_abstained the sum.
+ *   This is the one-pass list bit for bit (each list is the k best of its block in that order).
+ * pipnet_proto_stats_merge: n_class / n_ge / n_gt / hist / bad integer sums, vmax the maximum, total
+ *   and total_gt the fp64 chain ((s_0 + s_1) + s_2) + ...: bitwise the one-pass sums when the addends
+ *   are integers, else within 2 (n + W) 2^-53 * sum|x| of them.  NB == 0: hist / out_hist not read.
+ * pipnet_colsum_merge_f64: out[d] = the same chain over acc [W][D] (pipnet_colsum_accum_f64's state).
+ * pipnet_part_purity_merge: n / hits / rows / bad integer sums, first_key the UNSIGNED minimum (all
+ *   ones: never inserted; keys hold the global row ordinal): bitwise the one-pass state.
+ * 1 <= W <= PIPNET_STATE_MERGE_MAX_RANKS; 1 <= G, P, K, D; 1 <= k <= PIPNET_TOPK_MAX_K; 0 <= NB <=
+ * PIPNET_PROTO_STATS_MAX_BINS; 1 <= M <= PIPNET_PART_PURITY_MAX_PARTS; a violation or a NULL pointer
+ * returns PIPNET_ERR_ARG before any HIP call. */
+#define PIPNET_STATE_MERGE_MAX_RANKS 16
+int pipnet_topk_merge(const float* score, const int64_t* index, const int32_t* loc, const int32_t* fill,
+                      const int64_t* abstained, int64_t rank_stride, int W, int G, int P, int k, float* out_score,
+                      int64_t* out_index, int32_t* out_loc, int32_t* out_fill, int64_t* out_abstained, void* stream);
+int pipnet_proto_stats_merge(const int64_t* n_class, const int64_t* n_ge, const int64_t* n_gt, const double* total,
+                             const double* total_gt, const float* vmax, const int32_t* hist, const int64_t* bad,
+                             int64_t rank_stride, int W, int K, int P, int NB, int64_t* out_n_class, int64_t* out_n_ge,
+                             int64_t* out_n_gt, double* out_total, double* out_total_gt, float* out_vmax,
+                             int32_t* out_hist, int64_t* out_bad, void* stream);
+int pipnet_colsum_merge_f64(const double* acc, int64_t rank_stride, int W, int D, double* out, void* stream);
+int pipnet_part_purity_merge(const int64_t* n, const int64_t* hits, const uint64_t* first_key, const int64_t* rows,
+                             const int64_t* bad, int64_t rank_stride, int W, int P, int M, int64_t* out_n,
+                             int64_t* out_hits, uint64_t* out_first_key, int64_t* out_rows, int64_t* out_bad,
+                             void* stream);
 
 /* ---- explanation images (util/vis_pipnet.py:298-319 / :836-849 patch grids, util/visualize_prediction.py
  * :80-88 patch and rectangle images; csrc/gallery_ops.hip) ----------------------------------------------
