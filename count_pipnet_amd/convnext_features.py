@@ -244,75 +244,55 @@ FUSED_MLP = True      # tools / A-B runs may switch the fused narrow-stage MLP o
 MLP_FUSED_MIN_PIXELS = {96: 512, 192: 256}
 
 
-def _cnblock_hip(blk: CNBlock, h: Tensor, cache: Dict, key: str, row_scale: Optional[Tensor] = None) -> Tensor:
-    """One CNBlock in place on NHWC ``h``.  ``row_scale`` (train mode, StochasticDepth "row"):
+def _conv_lowp(fmt, x: Tensor, w_packed: Tensor, kh: int, kw: int, cout: int, *args, **kwargs) -> Tensor:
+    """``fmt``'s public conv wrapper (K.conv_s3 / K.conv_bf16_mix), looked up by name at call time -- a tool may have
+    swapped a tile rule in (tools/ab/ab_s3_rule.py); ``args``: bias, stride, pad, epilogue."""
+    lead = (cout,) if fmt.conv_takes_cout else ()
+    return getattr(K, fmt.conv_fn)(x, w_packed, kh, kw, *lead, *args, **kwargs)
+
+
+def _cnblock(blk: CNBlock, h: Tensor, cache: Dict, key: str, row_scale: Optional[Tensor],
+             precision: str = "fp32") -> Tensor:
+    """One CNBlock in place on NHWC fp32 ``h``.  ``row_scale`` (train mode, StochasticDepth "row"):
     device [B] = keep_b / (1 - p); the Linear2 epilogue scales each sample's branch by it
     (0 leaves a dropped sample's rows equal to the residual), so the batch stays one
     full-size GEMM (splitting it into kept runs measured slower: small-M grids underfill
-    the 256 CUs)."""
+    the 256 CUs).
+    A low ``precision`` (K.LOWP_FORMATS) runs the two Linears on that operand format: dwconv+LN writes
+    the format's A operand (split planes [hi | lo], or one RNE rounding to bf16), Linear1 (+GELU, fp32)
+    writes its own output in the same form, Linear2 adds layer_scale * (.) into the fp32 residual stream
+    -- RNE-packed weights, fp32 accumulation.  Every stage runs this unfused pair (no fused
+    low-precision MLP kernel)."""
     dw, ln, l1, l2 = blk.block[0], blk.block[2], blk.block[3], blk.block[5]
     b, hh, ww, c = h.shape
     if dw.kernel_size != (7, 7) or dw.padding != (3, 3) or dw.groups != c or dw.stride != (1, 1):
         raise RuntimeError(f"CNBlock {key}: unsupported depthwise conv {dw}")
     wdw = packed(cache, key + ".dw", dw.weight, lambda w: w.reshape(c, 49).t())
-    t = K.dwconv7_ln(h, wdw, dw.bias, ln.weight, ln.bias)
-    hv = h.view(-1, c)
-    if row_scale is None and c in K.MLP_FUSED_CHANNELS and FUSED_MLP \
-            and hh * ww >= MLP_FUSED_MIN_PIXELS[c]:
-        # narrow stages: Linear1 + GELU + Linear2 + layer_scale + residual in one kernel
-        K.cnblock_mlp(t.view(-1, c), l1.weight, l1.bias, l2.weight, l2.bias, blk.layer_scale.view(-1), hv, hw=hh * ww)
+    gamma = blk.layer_scale.view(-1)
+    fmt = K.LOWP_FORMATS.get(precision)
+    if fmt is None:
+        t = K.dwconv7_ln(h, wdw, dw.bias, ln.weight, ln.bias)
+        hv = h.view(-1, c)
+        if row_scale is None and c in K.MLP_FUSED_CHANNELS and FUSED_MLP \
+                and hh * ww >= MLP_FUSED_MIN_PIXELS[c]:
+            # narrow stages: Linear1 + GELU + Linear2 + layer_scale + residual in one kernel
+            K.cnblock_mlp(t.view(-1, c), l1.weight, l1.bias, l2.weight, l2.bias, gamma, hv, hw=hh * ww)
+            return h
+        u = K.linear(t.view(-1, c), l1.weight, l1.bias, _lib.EPI_BIAS_GELU)
+        if row_scale is None:
+            K.linear(u, l2.weight, l2.bias, _lib.EPI_RESID, scale=gamma, r=hv, out=hv)
+        else:
+            K.linear_rowscale(u, l2.weight, l2.bias, gamma, hv, row_scale, hh * ww)
         return h
-    m, hid = hv.shape[0], l1.weight.shape[0]
-    u = K.linear(t.view(-1, c), l1.weight, l1.bias, _lib.EPI_BIAS_GELU)
-    if row_scale is None:
-        K.linear(u, l2.weight, l2.bias, _lib.EPI_RESID, scale=blk.layer_scale.view(-1), r=hv, out=hv)
-    else:
-        K.linear_rowscale(u, l2.weight, l2.bias, blk.layer_scale.view(-1), hv, row_scale, hh * ww)
-    return h
-
-
-def _cnblock_s3(blk: CNBlock, h: Tensor, cache: Dict, key: str, row_scale: Optional[Tensor] = None) -> Tensor:
-    """One CNBlock in place on NHWC fp32 ``h`` with split-bf16 GEMMs (precision "bf16x3"):
-    dwconv+LN writes split planes [hi|lo], Linear1 (+GELU) reads them and writes its own
-    output as split planes, Linear2 adds layer_scale * (.) into the fp32 residual stream --
-    times ``row_scale`` (_cnblock_hip) per sample under train-mode stochastic depth."""
-    dw, ln, l1, l2 = blk.block[0], blk.block[2], blk.block[3], blk.block[5]
-    b, hh, ww, c = h.shape
-    if dw.kernel_size != (7, 7) or dw.padding != (3, 3) or dw.groups != c or dw.stride != (1, 1):
-        raise RuntimeError(f"CNBlock {key}: unsupported depthwise conv {dw}")
     hid = l1.out_features
-    wdw = packed(cache, key + ".dw", dw.weight, lambda w: w.reshape(c, 49).t())
-    w1 = packed(cache, key + ".fc1.s3", l1.weight, lambda w: K.split_planes_weight(w.view(hid, 1, 1, c)))
-    w2 = packed(cache, key + ".fc2.s3", l2.weight, lambda w: K.split_planes_weight(w.view(c, 1, 1, hid)))
-    t3 = K.dwconv7_ln_s3(h, wdw, dw.bias, ln.weight, ln.bias)
-    u3 = K.conv_s3(t3, w1, 1, 1, hid, l1.bias, 1, 0, _lib.EPI_S3_GELU)
+    w1 = packed(cache, key + ".fc1" + fmt.cache_suffix, l1.weight, lambda w: fmt.pack(w.view(hid, 1, 1, c)))
+    w2 = packed(cache, key + ".fc2" + fmt.cache_suffix, l2.weight, lambda w: fmt.pack(w.view(c, 1, 1, hid)))
+    t = getattr(K, fmt.dwconv7_ln_fn)(h, wdw, dw.bias, ln.weight, ln.bias)
+    u = _conv_lowp(fmt, t, w1, 1, 1, hid, l1.bias, 1, 0, fmt.gelu_epilogue)
     if row_scale is None:
-        K.conv_s3(u3, w2, 1, 1, c, l2.bias, 1, 0, _lib.EPI_F32_RESID, scale=blk.layer_scale.view(-1), r=h, out=h)
+        _conv_lowp(fmt, u, w2, 1, 1, c, l2.bias, 1, 0, _lib.EPI_F32_RESID, scale=gamma, r=h, out=h)
     else:
-        K.linear_s3_rowscale(u3, w2, l2.bias, blk.layer_scale.view(-1), h, row_scale, hh * ww)
-    return h
-
-
-def _cnblock_bf16(blk: CNBlock, h: Tensor, cache: Dict, key: str, row_scale: Optional[Tensor] = None) -> Tensor:
-    """One CNBlock in place on NHWC fp32 ``h`` with plain bf16 GEMMs (precision "bf16"): dwconv+LN
-    rounds once to bf16, Linear1 (+GELU, fp32) rounds once to a bf16 hidden tensor, Linear2 adds
-    layer_scale * (.) into the fp32 residual stream -- one bf16 product per multiply, RNE-bf16
-    weights, fp32 accumulation.  Every stage runs this unfused pair (no fused bf16 MLP kernel).
-    ``row_scale`` as in _cnblock_hip: the branch times keep_b / (1 - p) in the Linear2 epilogue."""
-    dw, ln, l1, l2 = blk.block[0], blk.block[2], blk.block[3], blk.block[5]
-    b, hh, ww, c = h.shape
-    if dw.kernel_size != (7, 7) or dw.padding != (3, 3) or dw.groups != c or dw.stride != (1, 1):
-        raise RuntimeError(f"CNBlock {key}: unsupported depthwise conv {dw}")
-    hid = l1.out_features
-    wdw = packed(cache, key + ".dw", dw.weight, lambda w: w.reshape(c, 49).t())
-    w1 = packed(cache, key + ".fc1.bf16", l1.weight, lambda w: K.pack_conv_weight_bf16(w.view(hid, 1, 1, c)))
-    w2 = packed(cache, key + ".fc2.bf16", l2.weight, lambda w: K.pack_conv_weight_bf16(w.view(c, 1, 1, hid)))
-    t = K.dwconv7_ln_bf16(h, wdw, dw.bias, ln.weight, ln.bias)
-    u = K.conv_bf16_mix(t, w1, 1, 1, l1.bias, 1, 0, _lib.EPI_BIAS_GELU)
-    if row_scale is None:
-        K.conv_bf16_mix(u, w2, 1, 1, l2.bias, 1, 0, _lib.EPI_F32_RESID, scale=blk.layer_scale.view(-1), r=h, out=h)
-    else:
-        K.linear_bf16_mix_rowscale(u, w2, l2.bias, blk.layer_scale.view(-1), h, row_scale, hh * ww)
+        getattr(K, fmt.rowscale_fn)(u, w2, l2.bias, gamma, h, row_scale, hh * ww)
     return h
 
 
@@ -366,14 +346,13 @@ def convnext_features_hip_steps(features: nn.Sequential, x: Tensor, cache: Dict,
     downsample convs as split-bf16 GEMMs, include/pipnet_amd.h) or "bf16" (the same layers as plain
     bf16 GEMMs on bf16 activations: one product per multiply, fp32 accumulation and residual stream;
     error budget in DESIGN.md section 4).  Masks and a precision combine: a block with p > 0 then
-    scales its branch per sample in the low-precision Linear2's epilogue (K.linear_s3_rowscale /
-    K.linear_bf16_mix_rowscale), a block with p == 0 runs what it runs without masks.  These are
+    scales its branch per sample in the low-precision Linear2's epilogue (the format's rowscale entry,
+    K.LOWP_FORMATS), a block with p == 0 runs what it runs without masks.  These are
     forward-only layers (no saved activations): the frozen part of a training step
     (convnext_train.train_forward with set_hip_train_dtype), never its trainable suffix."""
     if precision not in PRECISIONS:
         raise ValueError(f"unknown HIP precision {precision!r} (expected one of {PRECISIONS})")
-    s3 = precision == "bf16x3"
-    bf = precision == "bf16"
+    fmt = K.LOWP_FORMATS.get(precision)
     K.require_device(x, "network input")
     x = x.contiguous()
     h = None
@@ -390,28 +369,18 @@ def convnext_features_hip_steps(features: nn.Sequential, x: Tensor, cache: Dict,
         elif len(mod) > 0 and isinstance(mod[0], CNBlock):
             for j, blk in enumerate(mod):
                 row_scale = None if scales is None else scales.get(bid)
-                if s3:
-                    h = _cnblock_s3(blk, h, cache, f"{name}.{j}", row_scale)
-                elif bf:
-                    h = _cnblock_bf16(blk, h, cache, f"{name}.{j}", row_scale)
-                else:
-                    h = _cnblock_hip(blk, h, cache, f"{name}.{j}", row_scale)
+                h = _cnblock(blk, h, cache, f"{name}.{j}", row_scale, precision)
                 bid += 1
                 yield
         elif len(mod) == 2 and isinstance(mod[0], LayerNorm2d) and isinstance(mod[1], nn.Conv2d):
             ln, conv = mod[0], mod[1]
             if conv.kernel_size != (2, 2) or conv.padding != (0, 0):
                 raise RuntimeError(f"unsupported ConvNeXt downsample {conv}")
-            if s3 and conv.in_channels % 32 == 0:
-                t3 = K.layernorm_s3(h, ln.weight, ln.bias)
-                wp = packed(cache, name + ".conv.s3", conv.weight,
-                            lambda w: K.split_planes_weight(w.permute(0, 2, 3, 1)))
-                h = K.conv_s3(t3, wp, 2, 2, conv.out_channels, conv.bias, conv.stride[0], 0, _lib.EPI_F32_BIAS)
-            elif bf and conv.in_channels % 32 == 0:
-                t = K.layernorm_bf16(h, ln.weight, ln.bias)
-                wp = packed(cache, name + ".conv.bf16", conv.weight,
-                            lambda w: K.pack_conv_weight_bf16(w.permute(0, 2, 3, 1)))
-                h = K.conv_bf16_mix(t, wp, 2, 2, conv.bias, conv.stride[0], 0, _lib.EPI_F32_BIAS)
+            if fmt is not None and conv.in_channels % 32 == 0:
+                t = getattr(K, fmt.layernorm_fn)(h, ln.weight, ln.bias)
+                wp = packed(cache, name + ".conv" + fmt.cache_suffix, conv.weight,
+                            lambda w: fmt.pack(w.permute(0, 2, 3, 1)))
+                h = _conv_lowp(fmt, t, wp, 2, 2, conv.out_channels, conv.bias, conv.stride[0], 0, _lib.EPI_F32_BIAS)
             else:
                 t = K.layernorm(h, ln.weight, ln.bias)
                 wp = packed(cache, name + ".conv", conv.weight, lambda w: w.permute(0, 2, 3, 1))

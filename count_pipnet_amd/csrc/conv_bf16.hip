@@ -357,53 +357,36 @@ int conv_dual_shape(ConvParams& p, int64_t M, int Cin, int N1, int N2) {
   return PIPNET_OK;
 }
 
-// The same for pipnet_conv2d_nhwc_s3 (Cin = the fp32 channels; ldc is the caller's: it depends on the output form).
-int conv_s3_shape(ConvParams& p, bool& dense, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
-                  int pad, int epilogue, int tile) {
+// The same for the two ConvNeXt operand formats.  s3 (pipnet_conv2d_nhwc_s3): x holds split planes [hi | lo] of Cin
+// fp32 channels, read as the virtual 3 Cin channels [hi | lo | hi] of each tap (seg_remap) against weights
+// [hi | hi | lo]; K is rounded to the 32-deep steps the split tiles (0, 4, 5, 7) all walk.  Plain
+// (pipnet_conv2d_nhwc_bf16_mix): bf16 A, weights packed as pipnet_pack_conv_weight_bf16 makes them (K padded to KPAD
+// with zeros).  Cin % 32 == 0 keeps every 32-deep K-tile inside one tap and the valid K a whole number of K-tiles
+// (the ping-pong tiles re-read the last valid K-tile against the zero weight padding).  ldc is Cout; the launch
+// doubles it for the split-plane output of PIPNET_EPI_S3_GELU.
+int conv_cnx_shape(ConvParams& p, bool& dense, bool s3, int B, int H, int W, int Cin, int Cout, int KH, int KW,
+                   int stride, int pad, int epilogue, int tile) {
   if (B < 0 || H <= 0 || W <= 0 || Cin <= 0 || (Cin % 32) || Cout <= 0 || (Cout & 7) || KH <= 0 || KW <= 0 ||
       stride <= 0 || pad < 0)
     return PIPNET_ERR_ARG;
-  if (!is_s3_epi(epilogue)) return PIPNET_ERR_ARG;
+  if (!(s3 ? is_s3_epi(epilogue) : is_mix_epi(epilogue))) return PIPNET_ERR_ARG;
   if (tile != -1 && tile != 0 && tile != 4 && tile != 5 && tile != 7) return PIPNET_ERR_ARG;
   const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
   if (OH <= 0 || OW <= 0) return PIPNET_ERR_ARG;
   if ((int64_t)B * OH * OW >= (int64_t)1 << 31) return PIPNET_ERR_ARG;
-  p.ldr = Cout;
-  p.M = B * OH * OW; p.N = Cout;
-  p.Kv = KH * KW * 3 * Cin;
-  p.K = (p.Kv + 31) / 32 * 32;                 // the split tiles (0, 4, 5) all walk K in 32-deep steps
-  p.H = H; p.Wd = W; p.Cin = 3 * Cin; p.OH = OH; p.OW = OW; p.stride = stride; p.KW = KW; p.pad = pad;
-  p.Cinp = 2 * Cin;
-  p.seg = Cin;
-  dense = KH == 1 && KW == 1 && stride == 1 && pad == 0;
-  if (dense) p.lda = 2 * Cin;
-  return PIPNET_OK;
-}
-
-// The same for pipnet_conv2d_nhwc_bf16_mix: plain bf16 A (no split planes), weights packed as
-// pipnet_pack_conv_weight_bf16 makes them (K padded to KPAD with zeros).  Cin % 32 == 0 keeps every
-// 32-deep K-tile inside one tap and the valid K a whole number of K-tiles (the ping-pong tiles re-read
-// the last valid K-tile against the zero weight padding).
-int conv_mix_shape(ConvParams& p, bool& dense, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
-                   int pad, int epilogue, int tile) {
-  if (B < 0 || H <= 0 || W <= 0 || Cin <= 0 || (Cin % 32) || Cout <= 0 || (Cout & 7) || KH <= 0 || KW <= 0 ||
-      stride <= 0 || pad < 0)
-    return PIPNET_ERR_ARG;
-  if (!is_mix_epi(epilogue)) return PIPNET_ERR_ARG;
-  if (tile != -1 && tile != 0 && tile != 4 && tile != 5 && tile != 7) return PIPNET_ERR_ARG;
-  const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
-  if (OH <= 0 || OW <= 0) return PIPNET_ERR_ARG;
-  if ((int64_t)B * OH * OW >= (int64_t)1 << 31 || (int64_t)KH * KW * Cin >= (int64_t)1 << 30) return PIPNET_ERR_ARG;
+  if (!s3 && (int64_t)KH * KW * Cin >= (int64_t)1 << 30) return PIPNET_ERR_ARG;
+  const int kpad = s3 ? 32 : KPAD;
   p.ldr = Cout;
   p.ldc = Cout;
   p.M = B * OH * OW; p.N = Cout;
-  p.Kv = KH * KW * Cin;
-  p.K = (p.Kv + KPAD - 1) / KPAD * KPAD;
-  p.H = H; p.Wd = W; p.Cin = Cin; p.OH = OH; p.OW = OW; p.stride = stride; p.KW = KW; p.pad = pad;
-  p.Cinp = Cin;
-  p.seg = 0;
+  p.Kv = KH * KW * (s3 ? 3 * Cin : Cin);
+  p.K = (p.Kv + kpad - 1) / kpad * kpad;
+  p.H = H; p.Wd = W; p.OH = OH; p.OW = OW; p.stride = stride; p.KW = KW; p.pad = pad;
+  p.Cin = s3 ? 3 * Cin : Cin;
+  p.Cinp = s3 ? 2 * Cin : Cin;
+  p.seg = s3 ? Cin : 0;
   dense = KH == 1 && KW == 1 && stride == 1 && pad == 0;
-  if (dense) p.lda = Cin;
+  if (dense) p.lda = p.Cinp;
   return PIPNET_OK;
 }
 
@@ -532,15 +515,16 @@ extern "C" int pipnet_maxpool2d_nhwc_bf16(const void* x, int B, int H, int W, in
   return PIPNET_OK;
 }
 
-// Split-bf16 ("bf16x3") conv / linear of the ConvNeXt backbone (include/pipnet_amd.h): x holds
-// split planes [hi | lo] (2 Cin channels per pixel), read as the virtual 3 Cin channels
-// [hi | lo | hi] of each tap (seg_remap), against weights [hi | hi | lo] per tap.
-extern "C" int pipnet_conv2d_nhwc_s3(const void* x, int B, int H, int W, int Cin, const void* w_packed,
-                                     const float* bias, const float* scale, const float* R, int Cout, int KH, int KW,
-                                     int stride, int pad, int epilogue, void* y, int tile, void* stream) {
+namespace {
+
+// The launch and the label of pipnet_conv2d_nhwc_s3 (s3) and pipnet_conv2d_nhwc_bf16_mix: fp32 output, or the next
+// GEMM's bf16 A operand (PIPNET_EPI_S3_GELU: split planes, 2 Cout wide; PIPNET_EPI_BIAS_GELU: Cout wide).
+int conv_cnx_launch(bool s3, const void* x, int B, int H, int W, int Cin, const void* w_packed, const float* bias,
+                    const float* scale, const float* R, int Cout, int KH, int KW, int stride, int pad, int epilogue,
+                    void* y, int tile, void* stream) {
   ConvParams p{};
   bool dense = false;
-  if (const int st = conv_s3_shape(p, dense, B, H, W, Cin, Cout, KH, KW, stride, pad, epilogue, tile)) return st;
+  if (const int st = conv_cnx_shape(p, dense, s3, B, H, W, Cin, Cout, KH, KW, stride, pad, epilogue, tile)) return st;
   if (epilogue == PIPNET_EPI_F32_RESID && (!R || !scale)) return PIPNET_ERR_ARG;
   if (!x || !w_packed || !y) return PIPNET_ERR_ARG;
   if (!aligned16(x) || !aligned16(w_packed) || !aligned16(y) || (R && !aligned16(R)) || (bias && !aligned16(bias)) ||
@@ -552,58 +536,48 @@ extern "C" int pipnet_conv2d_nhwc_s3(const void* x, int B, int H, int W, int Cin
   p.bias = bias;
   p.scale = scale;
   p.R32 = R;
-  if (epilogue == PIPNET_EPI_S3_GELU) {
-    p.C = reinterpret_cast<bf16*>(y);
-    p.ldc = 2 * (int64_t)Cout;
-  } else {
-    p.Cf = reinterpret_cast<float*>(y);
-    p.ldc = Cout;
-  }
+  if (epilogue == PIPNET_EPI_S3_GELU || epilogue == PIPNET_EPI_BIAS_GELU) p.C = reinterpret_cast<bf16*>(y);
+  else p.Cf = reinterpret_cast<float*>(y);
+  if (epilogue == PIPNET_EPI_S3_GELU) p.ldc = 2 * (int64_t)Cout;
   return dense ? launch_conv<ALOAD_DENSE>(p, epilogue, tile, (hipStream_t)stream)
                : launch_conv<ALOAD_CONV>(p, epilogue, tile, (hipStream_t)stream);
+}
+
+int conv_cnx_label(bool s3, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int epilogue,
+                   int tile, char* buf, int cap) {
+  ConvParams p{};
+  bool dense = false;
+  if (conv_cnx_shape(p, dense, s3, B, H, W, Cin, Cout, KH, KW, stride, pad, epilogue, tile)) return -PIPNET_ERR_ARG;
+  return pipnet::write_label(dense ? select_conv<ALOAD_DENSE>(p, epilogue, tile)
+                                   : select_conv<ALOAD_CONV>(p, epilogue, tile), buf, cap);
+}
+
+}  // namespace
+
+// Split-bf16 ("bf16x3") conv / linear of the ConvNeXt backbone (include/pipnet_amd.h), and the plain bf16 one: one
+// bf16 product per multiply on the split GEMM's tiles, with its fp32-output epilogues or the one-rounding bf16 GELU.
+extern "C" int pipnet_conv2d_nhwc_s3(const void* x, int B, int H, int W, int Cin, const void* w_packed,
+                                     const float* bias, const float* scale, const float* R, int Cout, int KH, int KW,
+                                     int stride, int pad, int epilogue, void* y, int tile, void* stream) {
+  return conv_cnx_launch(true, x, B, H, W, Cin, w_packed, bias, scale, R, Cout, KH, KW, stride, pad, epilogue, y, tile,
+                         stream);
+}
+
+extern "C" int pipnet_conv2d_nhwc_bf16_mix(const void* x, int B, int H, int W, int Cin, const void* w_packed,
+                                           const float* bias, const float* scale, const float* R, int Cout, int KH,
+                                           int KW, int stride, int pad, int epilogue, void* y, int tile, void* stream) {
+  return conv_cnx_launch(false, x, B, H, W, Cin, w_packed, bias, scale, R, Cout, KH, KW, stride, pad, epilogue, y,
+                         tile, stream);
 }
 
 extern "C" int pipnet_conv2d_nhwc_s3_label(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
                                            int epilogue, int tile, char* buf, int cap) {
-  ConvParams p{};
-  bool dense = false;
-  if (conv_s3_shape(p, dense, B, H, W, Cin, Cout, KH, KW, stride, pad, epilogue, tile)) return -PIPNET_ERR_ARG;
-  return pipnet::write_label(dense ? select_conv<ALOAD_DENSE>(p, epilogue, tile)
-                                   : select_conv<ALOAD_CONV>(p, epilogue, tile), buf, cap);
-}
-
-// Plain bf16 conv / linear of the ConvNeXt backbone (include/pipnet_amd.h): one bf16 product per
-// multiply on the split GEMM's tiles, with its fp32-output epilogues or the one-rounding bf16 GELU.
-extern "C" int pipnet_conv2d_nhwc_bf16_mix(const void* x, int B, int H, int W, int Cin, const void* w_packed,
-                                           const float* bias, const float* scale, const float* R, int Cout, int KH,
-                                           int KW, int stride, int pad, int epilogue, void* y, int tile, void* stream) {
-  ConvParams p{};
-  bool dense = false;
-  if (const int st = conv_mix_shape(p, dense, B, H, W, Cin, Cout, KH, KW, stride, pad, epilogue, tile)) return st;
-  if (epilogue == PIPNET_EPI_F32_RESID && (!R || !scale)) return PIPNET_ERR_ARG;
-  if (!x || !w_packed || !y) return PIPNET_ERR_ARG;
-  if (!aligned16(x) || !aligned16(w_packed) || !aligned16(y) || (R && !aligned16(R)) || (bias && !aligned16(bias)) ||
-      (scale && !aligned16(scale)))
-    return PIPNET_ERR_ALIGN;
-  if (B == 0) return PIPNET_OK;
-  p.A = reinterpret_cast<const bf16*>(x);
-  p.W = reinterpret_cast<const bf16*>(w_packed);
-  p.bias = bias;
-  p.scale = scale;
-  p.R32 = R;
-  if (epilogue == PIPNET_EPI_BIAS_GELU) p.C = reinterpret_cast<bf16*>(y);
-  else p.Cf = reinterpret_cast<float*>(y);
-  return dense ? launch_conv<ALOAD_DENSE>(p, epilogue, tile, (hipStream_t)stream)
-               : launch_conv<ALOAD_CONV>(p, epilogue, tile, (hipStream_t)stream);
+  return conv_cnx_label(true, B, H, W, Cin, Cout, KH, KW, stride, pad, epilogue, tile, buf, cap);
 }
 
 extern "C" int pipnet_conv2d_nhwc_bf16_mix_label(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
                                                  int pad, int epilogue, int tile, char* buf, int cap) {
-  ConvParams p{};
-  bool dense = false;
-  if (conv_mix_shape(p, dense, B, H, W, Cin, Cout, KH, KW, stride, pad, epilogue, tile)) return -PIPNET_ERR_ARG;
-  return pipnet::write_label(dense ? select_conv<ALOAD_DENSE>(p, epilogue, tile)
-                                   : select_conv<ALOAD_CONV>(p, epilogue, tile), buf, cap);
+  return conv_cnx_label(false, B, H, W, Cin, Cout, KH, KW, stride, pad, epilogue, tile, buf, cap);
 }
 
 namespace {
@@ -614,10 +588,8 @@ int linear_rowscale_shape(ConvParams& p, bool s3, int64_t M, int Cin, int Cout, 
   if (M < 0 || M >= (int64_t)1 << 31) return PIPNET_ERR_ARG;
   bool dense = false;
   const int h = M > 0 ? (int)M : 1;
-  const int st = s3 ? conv_s3_shape(p, dense, M > 0, h, 1, Cin, Cout, 1, 1, 1, 0, PIPNET_EPI_F32_RESID, tile)
-                    : conv_mix_shape(p, dense, M > 0, h, 1, Cin, Cout, 1, 1, 1, 0, PIPNET_EPI_F32_RESID, tile);
-  if (st) return st;
-  p.ldc = Cout;
+  if (const int st = conv_cnx_shape(p, dense, s3, M > 0, h, 1, Cin, Cout, 1, 1, 1, 0, PIPNET_EPI_F32_RESID, tile))
+    return st;
   return dense ? PIPNET_OK : PIPNET_ERR_ARG;
 }
 

@@ -211,34 +211,9 @@ extern "C" int pipnet_convnext_stem_f32(const float* x, int B, int H, int W, con
 // C5 stages 25 -> 17.5 (96 @ 32^2), 17 -> 12.4 us (192 @ 16^2); 768 @ 26^2 keeps TY = 1
 // (profiles/r04/dw_window_lab.txt).  Every tile sums the same 49 products in the same order:
 // bitwise equal outputs.  The choice depends on W only (per-pixel results stay batch-invariant).
-extern "C" int pipnet_dwconv7_ln_f32(const float* x, int B, int H, int W, int C, const float* w_packed,
-                                     const float* bias, const float* ln_w, const float* ln_b, float* y,
-                                     void* stream) {
-  if (B < 0 || H <= 0 || W <= 0) return PIPNET_ERR_ARG;
-  if (!x || !w_packed || !bias || !ln_w || !ln_b || !y) return PIPNET_ERR_ARG;
-  if (!aligned16(x) || !aligned16(w_packed) || !aligned16(bias) || !aligned16(ln_w) || !aligned16(ln_b) ||
-      !aligned16(y))
-    return PIPNET_ERR_ALIGN;
-  if (B == 0) return PIPNET_OK;
-  hipStream_t s = (hipStream_t)stream;
-  switch (C) {
-    case 96:
-      if (W > 16 && W <= 32) return pipnet_dw::launch_dw<96, 4, 4, 1, false, 8>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
-      if (W > 32) return pipnet_dw::launch_dw<96, 7, 2, 1, false, 8>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
-      return pipnet_dw::launch_dw<96, 7, 1, 1, false, 8>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
-    case 192:
-      if (W > 8 && W <= 16) return pipnet_dw::launch_dw<192, 4, 2, 1, false, 16>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
-      if (W > 16) return pipnet_dw::launch_dw<192, 7, 2, 1, false, 16>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
-      return pipnet_dw::launch_dw<192, 7, 1, 1, false, 16>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
-    case 384: return pipnet_dw::launch_dw<384, 7, 3, 1, false, 32>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
-    case 768: return pipnet_dw::launch_dw<768, 13, 1, 1>(x, B, H, W, w_packed, bias, ln_w, ln_b, y, s);
-    default: return PIPNET_ERR_ARG;
-  }
-}
-
 namespace {
 
-// pipnet_dwconv7_ln_f32's tiles with a bf16 output form (convnext_dw.hpp: OUT_S3 / OUT_BF16).
+// One body for the three output forms (convnext_dw.hpp: OUT_F32 / OUT_S3 / OUT_BF16).
 template <int OUT>
 int dwconv7_ln_planes(const float* x, int B, int H, int W, int C, const float* w_packed, const float* bias,
                       const float* ln_w, const float* ln_b, void* y, void* stream) {
@@ -264,7 +239,7 @@ int dwconv7_ln_planes(const float* x, int B, int H, int W, int C, const float* w
   }
 }
 
-// pipnet_layernorm_f32 with a bf16 output form.
+// Row LayerNorm in the same three output forms.
 template <int OUT>
 int layernorm_planes(const float* x, int64_t rows, int C, const float* w, const float* b, void* y, void* stream) {
   if (rows < 0 || C <= 0 || C > 2048 || !x || !w || !b || !y) return PIPNET_ERR_ARG;
@@ -282,6 +257,12 @@ int layernorm_planes(const float* x, int64_t rows, int C, const float* w, const 
 }
 
 }  // namespace
+
+extern "C" int pipnet_dwconv7_ln_f32(const float* x, int B, int H, int W, int C, const float* w_packed,
+                                     const float* bias, const float* ln_w, const float* ln_b, float* y,
+                                     void* stream) {
+  return dwconv7_ln_planes<pipnet_dw::OUT_F32>(x, B, H, W, C, w_packed, bias, ln_w, ln_b, y, stream);
+}
 
 extern "C" int pipnet_dwconv7_ln_s3(const float* x, int B, int H, int W, int C, const float* w_packed,
                                     const float* bias, const float* ln_w, const float* ln_b, void* y, void* stream) {
@@ -305,16 +286,5 @@ extern "C" int pipnet_layernorm_bf16(const float* x, int64_t rows, int C, const 
 
 extern "C" int pipnet_layernorm_f32(const float* x, int64_t rows, int C, const float* w, const float* b, float* y,
                                     void* stream) {
-  if (rows < 0 || C <= 0 || C > 2048 || !x || !w || !b || !y) return PIPNET_ERR_ARG;
-  if (rows == 0) return PIPNET_OK;
-  const dim3 grid((unsigned)((rows + 3) / 4));
-  hipStream_t s = (hipStream_t)stream;
-  const int nj = (C + 63) / 64;
-  if (nj <= 2) hipLaunchKernelGGL(layernorm_kernel<2>, grid, dim3(256), 0, s, x, rows, C, w, b, y);
-  else if (nj <= 3) hipLaunchKernelGGL(layernorm_kernel<3>, grid, dim3(256), 0, s, x, rows, C, w, b, y);
-  else if (nj <= 6) hipLaunchKernelGGL(layernorm_kernel<6>, grid, dim3(256), 0, s, x, rows, C, w, b, y);
-  else if (nj <= 12) hipLaunchKernelGGL(layernorm_kernel<12>, grid, dim3(256), 0, s, x, rows, C, w, b, y);
-  else hipLaunchKernelGGL(layernorm_kernel<32>, grid, dim3(256), 0, s, x, rows, C, w, b, y);
-  PIPNET_CHECK_LAUNCH();
-  return PIPNET_OK;
+  return layernorm_planes<pipnet_dw::OUT_F32>(x, rows, C, w, b, y, stream);
 }

@@ -10,10 +10,11 @@ from __future__ import annotations
 import contextlib
 import copy
 import ctypes
+import dataclasses
 import functools
 import threading
 
-from typing import Optional, Tuple
+from typing import Callable, Optional, Tuple
 
 import os
 
@@ -375,9 +376,10 @@ def bf16_conv_kernel_name(b: int, h: int, w: int, cin: int, cout: int, kh: int, 
     _s3_label / _bf16_mix_label); RuntimeError when the library has none, as the launch would answer."""
     if s3 and mix:
         raise ValueError("bf16_conv_kernel_name: s3 and mix name different entry points")
-    entry = "pipnet_conv2d_nhwc_s3_label" if s3 else \
-        "pipnet_conv2d_nhwc_bf16_mix_label" if mix else "pipnet_conv2d_nhwc_bf16_label"
-    return _lib.label(entry, b, h, w, cin, cout, kh, kw, stride, pad, epilogue, tile)
+    args = (b, h, w, cin, cout, kh, kw, stride, pad, epilogue, tile)
+    if s3 or mix:
+        return _lowp_label(LOWP_FORMATS["bf16x3" if s3 else "bf16"].conv_label, *args)
+    return _lib.label("pipnet_conv2d_nhwc_bf16_label", *args)
 
 
 def pack_conv_weight_bf16(w_ohwi: Tensor) -> Tensor:
@@ -568,26 +570,8 @@ def cnblock_mlp(t: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, gamma
     return x
 
 
-def _chk_dwconv7_ln(fn: str, x_nhwc: Tensor, w_packed: Tensor, bias: Tensor, ln_w: Tensor, ln_b: Tensor):
-    _chk_rows(fn, x_nhwc, "input", 4)
-    c = x_nhwc.shape[3]
-    _operand(fn, "w_packed", w_packed, shape=49 * c, device=x_nhwc.device)
-    for what, t in (("bias", bias), ("ln_w", ln_w), ("ln_b", ln_b)):
-        _operand(fn, what, t, shape=c, device=x_nhwc.device)
-    return x_nhwc.shape
-
-
-def dwconv7_ln(x_nhwc: Tensor, w_packed: Tensor, bias: Tensor, ln_w: Tensor, ln_b: Tensor,
-               out: Optional[Tensor] = None) -> Tensor:
-    b, h, w, c = _chk_dwconv7_ln("dwconv7_ln", x_nhwc, w_packed, bias, ln_w, ln_b)
-    _chk_same("dwconv7_ln", x_nhwc, out=out)
-    y = torch.empty_like(x_nhwc) if out is None else out
-    _lib.call("pipnet_dwconv7_ln_f32", x_nhwc.data_ptr(), b, h, w, c, w_packed.data_ptr(), bias.data_ptr(),
-              ln_w.data_ptr(), ln_b.data_ptr(), y.data_ptr(), _stream(x_nhwc))
-    return y
-
-
-# ---- split-bf16 ("bf16x3") ConvNeXt path (include/pipnet_amd.h, pipnet_conv2d_nhwc_s3) ----
+# ---- the low-precision ConvNeXt paths: split bf16 ("bf16x3", pipnet_conv2d_nhwc_s3) and plain bf16 ("bf16",
+# ---- pipnet_conv2d_nhwc_bf16_mix), include/pipnet_amd.h ----
 S3_KTILE = 32          # split weights: K padded to the 32-deep K tiles of the split kernels
 def split_planes_weight(w_ohwi: Tensor) -> Tensor:
     """fp32 weight [Cout, KH, KW, Cin] -> packed split-bf16 B operand [Cout, Kp] bf16: per tap
@@ -610,82 +594,103 @@ def split_planes(x: Tensor) -> Tensor:
     return torch.cat([hi, lo], dim=-1).contiguous()
 
 
-def conv_s3(x2: Tensor, w_packed: Tensor, kh: int, kw: int, cout: int, bias: Optional[Tensor], stride: int, pad: int,
-            epilogue: int, scale: Optional[Tensor] = None, r: Optional[Tensor] = None, out: Optional[Tensor] = None,
-            tile: int = -1) -> Tensor:
-    """Split-bf16 conv / linear: x2 [B,H,W,2Cin] split planes, w_packed from split_planes_weight.
-    EPI_S3_GELU -> split planes [B,OH,OW,2Cout] of gelu(conv + b); EPI_F32_BIAS -> fp32
-    [B,OH,OW,Cout]; EPI_F32_RESID -> fp32 r + scale * (conv + b) (``out`` may be ``r``)."""
-    _chk_bf(x2, "split-plane input")
-    b, h, w, cin2 = x2.shape
-    cin = cin2 // 2
-    k = kh * kw * 3 * cin
-    if cin2 % 2:
-        raise RuntimeError(f"conv_s3: split planes need an even channel count, got {cin2}")
-    _operand("conv_s3", "split-plane weight", w_packed, dtype=torch.bfloat16, device=x2.device,
-             shape=(cout, -(-k // S3_KTILE) * S3_KTILE))
-    _chk_vec("conv_s3", x2, cout, bias=bias, scale=scale)
+@dataclasses.dataclass(frozen=True)
+class OperandFormat:
+    """What differs between the low-precision operand formats of the ConvNeXt GEMMs, and nothing else: the one place
+    a new format is added."""
+    a_planes: int          # bf16 values per input channel in A: 2 = split planes [hi | lo], 1 = plain bf16
+    k_factor: int          # packed-K entries per input channel and tap
+    ktile: int             # the K tile the packed weight is padded to
+    pack: Callable[[Tensor], Tensor]    # fp32 [Cout, KH, KW, Cin] -> the packed B operand
+    gelu_epilogue: int     # writes gelu(conv + b) as the next GEMM's A operand, a_planes * Cout bf16 wide
+    flop_div: int          # products per multiply: the launch hook is told the algorithmic flops
+    conv: str              # library entries
+    conv_label: str
+    rowscale: str
+    rowscale_label: str
+    dwconv7_ln: str
+    layernorm: str
+    conv_fn: str           # the public wrappers of those entries in this module: their name opens every message, and
+    rowscale_fn: str       # the executor looks them up by it at call time, so a tool can swap one (tools/ab/)
+    dwconv7_ln_fn: str
+    layernorm_fn: str
+    conv_takes_cout: bool  # conv_s3 has a ``cout`` argument after kw, conv_bf16_mix reads it off the weight
+    cache_suffix: str      # of the packed weights' keys in a model's weight cache
+
+
+LOWP_FORMATS = {
+    "bf16x3": OperandFormat(
+        a_planes=2, k_factor=3, ktile=S3_KTILE, pack=split_planes_weight, gelu_epilogue=_lib.EPI_S3_GELU, flop_div=3,
+        conv="pipnet_conv2d_nhwc_s3", conv_label="pipnet_conv2d_nhwc_s3_label", rowscale="pipnet_linear_s3_rowscale",
+        rowscale_label="pipnet_linear_s3_rowscale_label", dwconv7_ln="pipnet_dwconv7_ln_s3",
+        layernorm="pipnet_layernorm_s3", conv_fn="conv_s3", rowscale_fn="linear_s3_rowscale",
+        dwconv7_ln_fn="dwconv7_ln_s3", layernorm_fn="layernorm_s3", conv_takes_cout=True, cache_suffix=".s3"),
+    "bf16": OperandFormat(
+        a_planes=1, k_factor=1, ktile=BF16_KTILE, pack=pack_conv_weight_bf16, gelu_epilogue=_lib.EPI_BIAS_GELU,
+        flop_div=1, conv="pipnet_conv2d_nhwc_bf16_mix", conv_label="pipnet_conv2d_nhwc_bf16_mix_label",
+        rowscale="pipnet_linear_bf16_mix_rowscale", rowscale_label="pipnet_linear_bf16_mix_rowscale_label",
+        dwconv7_ln="pipnet_dwconv7_ln_bf16", layernorm="pipnet_layernorm_bf16", conv_fn="conv_bf16_mix",
+        rowscale_fn="linear_bf16_mix_rowscale", dwconv7_ln_fn="dwconv7_ln_bf16", layernorm_fn="layernorm_bf16",
+        conv_takes_cout=False, cache_suffix=".bf16"),
+}
+_S3, _MIX = LOWP_FORMATS["bf16x3"], LOWP_FORMATS["bf16"]
+
+
+@functools.lru_cache(maxsize=4096)
+def _lowp_label(entry: str, *args: int) -> str:
+    """rocprof name of the instantiation a format's conv / rowscale entry launches (``entry``: its label entry)."""
+    return _lib.label(entry, *args)
+
+
+def _conv_lowp(fmt: OperandFormat, x: Tensor, w_packed: Tensor, kh: int, kw: int, bias: Optional[Tensor],
+               stride: int, pad: int, epilogue: int, scale: Optional[Tensor] = None, r: Optional[Tensor] = None,
+               out: Optional[Tensor] = None, tile: int = -1, cout: Optional[int] = None) -> Tensor:
+    """conv_s3 / conv_bf16_mix: ``x`` [B,H,W,a_planes * Cin] bf16 against a weight packed by ``fmt.pack``."""
+    fn = fmt.conv_fn
+    _operand(fn, "input", x, dtype=torch.bfloat16)
+    if x.dim() != 4 or x.shape[3] % fmt.a_planes:
+        raise RuntimeError(f"{fn}: input must be [B,H,W,{fmt.a_planes} x Cin] (got shape {tuple(x.shape)})")
+    b, h, w, width = x.shape
+    dev, cin = x.device, width // fmt.a_planes
+    k = kh * kw * fmt.k_factor * cin
+    _operand(fn, "weight", w_packed, dtype=torch.bfloat16, device=dev)
+    if w_packed.dim() != 2 or w_packed.shape[1] != -(-k // fmt.ktile) * fmt.ktile or \
+            cout not in (None, w_packed.shape[0]):
+        raise RuntimeError(f"{fn}: packed weight {tuple(w_packed.shape)} does not match {kh}x{kw}x{cin}"
+                           f"{'' if cout is None else f' -> {cout}'} (K padded to {fmt.ktile})")
+    cout = w_packed.shape[0]
+    if epilogue not in (fmt.gelu_epilogue, _lib.EPI_F32_BIAS, _lib.EPI_F32_RESID):
+        raise RuntimeError(f"{fn}: epilogue {epilogue} is not the format's GELU ({fmt.gelu_epilogue}), EPI_F32_BIAS or "
+                           "EPI_F32_RESID")
+    _chk_vec(fn, x, cout, bias=bias, scale=scale)
     oh, ow = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
-    if epilogue == _lib.EPI_S3_GELU:
-        shape, dt = (b, oh, ow, 2 * cout), torch.bfloat16
+    m = b * oh * ow
+    if epilogue == _lib.EPI_F32_RESID and scale is None:
+        raise RuntimeError(f"{fn}: EPI_F32_RESID needs r and scale")
+    _operand(fn, "residual", r, shape=m * cout, device=dev, optional=epilogue != _lib.EPI_F32_RESID)
+    if epilogue == fmt.gelu_epilogue:
+        shape, dt = (b, oh, ow, fmt.a_planes * cout), torch.bfloat16
     else:
         shape, dt = (b, oh, ow, cout), torch.float32
-    if epilogue == _lib.EPI_F32_RESID and scale is None:
-        raise RuntimeError("conv_s3: EPI_F32_RESID needs r and scale")
-    _operand("conv_s3", "residual", r, shape=b * oh * ow * cout, device=x2.device,
-             optional=epilogue != _lib.EPI_F32_RESID)
     if out is None:
-        out = torch.empty(shape, device=x2.device, dtype=dt)
+        out = torch.empty(shape, device=dev, dtype=dt)
     else:
-        _operand("conv_s3", "out", out, dtype=dt, shape=b * oh * ow * shape[-1], device=x2.device)
-    m = b * oh * ow
-    _launch(bf16_conv_kernel_name(b, h, w, cin, cout, kh, kw, stride, pad, epilogue, tile, s3=True),
-            2.0 * m * cout * k / 3.0,
-            lambda: _lib.call("pipnet_conv2d_nhwc_s3", x2.data_ptr(), b, h, w, cin, w_packed.data_ptr(), _ptr(bias),
-                              _ptr(scale), _ptr(r), cout, kh, kw, stride, pad, epilogue, out.data_ptr(), tile,
-                              _stream(x2)))
+        _operand(fn, "out", out, dtype=dt, shape=m * shape[-1], device=dev)
+    _launch(_lowp_label(fmt.conv_label, b, h, w, cin, cout, kh, kw, stride, pad, epilogue, tile),
+            2.0 * m * cout * k / fmt.flop_div,
+            lambda: _lib.call(fmt.conv, x.data_ptr(), b, h, w, cin, w_packed.data_ptr(), _ptr(bias), _ptr(scale),
+                              _ptr(r), cout, kh, kw, stride, pad, epilogue, out.data_ptr(), tile, _stream(x)))
     return out
 
 
-def dwconv7_ln_s3(x_nhwc: Tensor, w_packed: Tensor, bias: Tensor, ln_w: Tensor, ln_b: Tensor) -> Tensor:
-    """pipnet_dwconv7_ln_f32 writing split planes [B,H,W,2C] bf16."""
-    b, h, w, c = _chk_dwconv7_ln("dwconv7_ln_s3", x_nhwc, w_packed, bias, ln_w, ln_b)
-    y = torch.empty((b, h, w, 2 * c), device=x_nhwc.device, dtype=torch.bfloat16)
-    _lib.call("pipnet_dwconv7_ln_s3", x_nhwc.data_ptr(), b, h, w, c, w_packed.data_ptr(), bias.data_ptr(),
-              ln_w.data_ptr(), ln_b.data_ptr(), y.data_ptr(), _stream(x_nhwc))
-    return y
-
-
-def layernorm_s3(x: Tensor, w: Tensor, b: Tensor) -> Tensor:
-    """Row LayerNorm writing split planes [..., 2C] bf16."""
-    _operand("layernorm_s3", "input", x)
-    c = x.shape[-1]
-    _chk_vec("layernorm_s3", x, c, w=w, b=b)
-    y = torch.empty(tuple(x.shape[:-1]) + (2 * c,), device=x.device, dtype=torch.bfloat16)
-    _lib.call("pipnet_layernorm_s3", x.data_ptr(), x.numel() // c, c, w.data_ptr(), b.data_ptr(), y.data_ptr(),
-              _stream(x))
-    return y
-
-
-# ---- plain bf16 ConvNeXt path (include/pipnet_amd.h, pipnet_conv2d_nhwc_bf16_mix) ----
-def dwconv7_ln_bf16(x_nhwc: Tensor, w_packed: Tensor, bias: Tensor, ln_w: Tensor, ln_b: Tensor) -> Tensor:
-    """pipnet_dwconv7_ln_f32 rounded once (RNE) to bf16 [B,H,W,C]: the hi plane of dwconv7_ln_s3."""
-    b, h, w, c = _chk_dwconv7_ln("dwconv7_ln_bf16", x_nhwc, w_packed, bias, ln_w, ln_b)
-    y = torch.empty((b, h, w, c), device=x_nhwc.device, dtype=torch.bfloat16)
-    _lib.call("pipnet_dwconv7_ln_bf16", x_nhwc.data_ptr(), b, h, w, c, w_packed.data_ptr(), bias.data_ptr(),
-              ln_w.data_ptr(), ln_b.data_ptr(), y.data_ptr(), _stream(x_nhwc))
-    return y
-
-
-def layernorm_bf16(x: Tensor, w: Tensor, b: Tensor) -> Tensor:
-    """Row LayerNorm rounded once (RNE) to bf16 [..., C]: the hi plane of layernorm_s3."""
-    _operand("layernorm_bf16", "input", x)
-    c = x.shape[-1]
-    _chk_vec("layernorm_bf16", x, c, w=w, b=b)
-    y = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16)
-    _lib.call("pipnet_layernorm_bf16", x.data_ptr(), x.numel() // c, c, w.data_ptr(), b.data_ptr(), y.data_ptr(),
-              _stream(x))
-    return y
+def conv_s3(x2: Tensor, w_packed: Tensor, kh: int, kw: int, cout: int, bias: Optional[Tensor], stride: int, pad: int,
+            epilogue: int, scale: Optional[Tensor] = None, r: Optional[Tensor] = None, out: Optional[Tensor] = None,
+            tile: int = -1) -> Tensor:
+    """Split-bf16 conv / linear: x2 [B,H,W,2Cin] split planes, w_packed [cout, Kp] from split_planes_weight.
+    EPI_S3_GELU -> split planes [B,OH,OW,2Cout] of gelu(conv + b); EPI_F32_BIAS -> fp32
+    [B,OH,OW,Cout]; EPI_F32_RESID -> fp32 r + scale * (conv + b) (``out`` may be ``r``).
+    tile -1 = automatic, or 0 / 4 / 5 / 7."""
+    return _conv_lowp(_S3, x2, w_packed, kh, kw, bias, stride, pad, epilogue, scale, r, out, tile, cout)
 
 
 def conv_bf16_mix(x: Tensor, w_packed: Tensor, kh: int, kw: int, bias: Optional[Tensor], stride: int, pad: int,
@@ -695,36 +700,72 @@ def conv_bf16_mix(x: Tensor, w_packed: Tensor, kh: int, kw: int, bias: Optional[
     pack_conv_weight_bf16, fp32 accumulation.  EPI_BIAS_GELU -> bf16 [B,OH,OW,Cout] of gelu(conv + b);
     EPI_F32_BIAS -> fp32 conv + b; EPI_F32_RESID -> fp32 r + scale * (conv + b) (``out`` may be ``r``).
     tile -1 = automatic, or 0 / 4 / 5 / 7 (the split GEMM's tiles)."""
-    fn = "conv_bf16_mix"
-    _chk_bf(x, "conv_bf16_mix input")
-    if x.dim() != 4:
-        raise RuntimeError(f"{fn}: input must be [B,H,W,Cin] (got shape {tuple(x.shape)})")
-    b, h, w, cin = x.shape
-    dev, k = x.device, kh * kw * cin
-    _operand(fn, "weight", w_packed, dtype=torch.bfloat16, device=dev)
-    if w_packed.dim() != 2 or w_packed.shape[1] != -(-k // BF16_KTILE) * BF16_KTILE:
-        raise RuntimeError(f"{fn}: packed weight {tuple(w_packed.shape)} does not match {kh}x{kw}x{cin} "
-                           f"(K padded to {BF16_KTILE})")
-    cout = w_packed.shape[0]
-    if epilogue not in (_lib.EPI_BIAS_GELU, _lib.EPI_F32_BIAS, _lib.EPI_F32_RESID):
-        raise RuntimeError(f"{fn}: epilogue {epilogue} is not one of EPI_BIAS_GELU / EPI_F32_BIAS / EPI_F32_RESID")
-    _chk_vec(fn, x, cout, bias=bias, scale=scale)
-    oh, ow = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
-    if epilogue == _lib.EPI_F32_RESID and scale is None:
-        raise RuntimeError(f"{fn}: EPI_F32_RESID needs r and scale")
-    _operand(fn, "residual", r, shape=b * oh * ow * cout, device=dev, optional=epilogue != _lib.EPI_F32_RESID)
-    dt = torch.bfloat16 if epilogue == _lib.EPI_BIAS_GELU else torch.float32
-    if out is None:
-        out = torch.empty((b, oh, ow, cout), device=dev, dtype=dt)
-    else:
-        _operand(fn, "out", out, dtype=dt, shape=b * oh * ow * cout, device=dev)
-    m = b * oh * ow
-    _launch(bf16_conv_kernel_name(b, h, w, cin, cout, kh, kw, stride, pad, epilogue, tile, mix=True),
-            2.0 * m * cout * k,
-            lambda: _lib.call("pipnet_conv2d_nhwc_bf16_mix", x.data_ptr(), b, h, w, cin, w_packed.data_ptr(),
-                              _ptr(bias), _ptr(scale), _ptr(r), cout, kh, kw, stride, pad, epilogue, out.data_ptr(),
-                              tile, _stream(x)))
-    return out
+    return _conv_lowp(_MIX, x, w_packed, kh, kw, bias, stride, pad, epilogue, scale, r, out, tile)
+
+
+def _form_out(fmt: Optional[OperandFormat], x: Tensor) -> Tensor:
+    """The output of a producer kernel over fp32 ``x`` [..., C]: fp32 (``fmt`` None), or ``fmt``'s A operand."""
+    if fmt is None:
+        return torch.empty_like(x)
+    return torch.empty(tuple(x.shape[:-1]) + (fmt.a_planes * x.shape[-1],), device=x.device, dtype=torch.bfloat16)
+
+
+def _dwconv7_ln(fmt: Optional[OperandFormat], x_nhwc: Tensor, w_packed: Tensor, bias: Tensor, ln_w: Tensor,
+                ln_b: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    fn = "dwconv7_ln" if fmt is None else fmt.dwconv7_ln_fn
+    _chk_rows(fn, x_nhwc, "input", 4)
+    b, h, w, c = x_nhwc.shape
+    _operand(fn, "w_packed", w_packed, shape=49 * c, device=x_nhwc.device)
+    for what, t in (("bias", bias), ("ln_w", ln_w), ("ln_b", ln_b)):
+        _operand(fn, what, t, shape=c, device=x_nhwc.device)
+    _chk_same(fn, x_nhwc, out=out)
+    y = _form_out(fmt, x_nhwc) if out is None else out
+    _lib.call("pipnet_dwconv7_ln_f32" if fmt is None else fmt.dwconv7_ln, x_nhwc.data_ptr(), b, h, w, c,
+              w_packed.data_ptr(), bias.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), y.data_ptr(), _stream(x_nhwc))
+    return y
+
+
+def dwconv7_ln(x_nhwc: Tensor, w_packed: Tensor, bias: Tensor, ln_w: Tensor, ln_b: Tensor,
+               out: Optional[Tensor] = None) -> Tensor:
+    """Depthwise 7x7 conv (pad 3) + bias + LayerNorm over channels, NHWC fp32 (pipnet_dwconv7_ln_f32)."""
+    return _dwconv7_ln(None, x_nhwc, w_packed, bias, ln_w, ln_b, out)
+
+
+def dwconv7_ln_s3(x_nhwc: Tensor, w_packed: Tensor, bias: Tensor, ln_w: Tensor, ln_b: Tensor) -> Tensor:
+    """pipnet_dwconv7_ln_f32 writing split planes [B,H,W,2C] bf16."""
+    return _dwconv7_ln(_S3, x_nhwc, w_packed, bias, ln_w, ln_b)
+
+
+def dwconv7_ln_bf16(x_nhwc: Tensor, w_packed: Tensor, bias: Tensor, ln_w: Tensor, ln_b: Tensor) -> Tensor:
+    """pipnet_dwconv7_ln_f32 rounded once (RNE) to bf16 [B,H,W,C]: the hi plane of dwconv7_ln_s3."""
+    return _dwconv7_ln(_MIX, x_nhwc, w_packed, bias, ln_w, ln_b)
+
+
+def _layernorm(fmt: Optional[OperandFormat], x: Tensor, w: Tensor, b: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    fn = "layernorm" if fmt is None else fmt.layernorm_fn
+    _operand(fn, "input", x)
+    c = x.shape[-1]
+    _chk_vec(fn, x, c, w=w, b=b)
+    _chk_same(fn, x, out=out)
+    y = _form_out(fmt, x) if out is None else out
+    _lib.call("pipnet_layernorm_f32" if fmt is None else fmt.layernorm, x.data_ptr(), x.numel() // c, c, w.data_ptr(),
+              b.data_ptr(), y.data_ptr(), _stream(x))
+    return y
+
+
+def layernorm(x: Tensor, w: Tensor, b: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """Row LayerNorm over the last dimension, fp32 (pipnet_layernorm_f32)."""
+    return _layernorm(None, x, w, b, out)
+
+
+def layernorm_s3(x: Tensor, w: Tensor, b: Tensor) -> Tensor:
+    """Row LayerNorm writing split planes [..., 2C] bf16."""
+    return _layernorm(_S3, x, w, b)
+
+
+def layernorm_bf16(x: Tensor, w: Tensor, b: Tensor) -> Tensor:
+    """Row LayerNorm rounded once (RNE) to bf16 [..., C]: the hi plane of layernorm_s3."""
+    return _layernorm(_MIX, x, w, b)
 
 
 # ---- CNBlock Linear2 under train-mode stochastic depth on the low-precision operands ----
@@ -735,19 +776,20 @@ LOWP_ROWSCALE_TILES = (-1, 0, 4, 5, 7)      # what EPI_F32_RESID takes on either
 def linear_lowp_rowscale_kernel_name(m: int, cin: int, cout: int, tile: int = -1, s3: bool = False) -> str:
     """rocprof name of the instantiation linear_bf16_mix_rowscale (``s3``: linear_s3_rowscale, ``cin`` its fp32
     channels) launches (pipnet_linear_bf16_mix_rowscale_label / pipnet_linear_s3_rowscale_label)."""
-    entry = "pipnet_linear_s3_rowscale_label" if s3 else "pipnet_linear_bf16_mix_rowscale_label"
-    return _lib.label(entry, m, cin, cout, tile)
+    return _lowp_label(LOWP_FORMATS["bf16x3" if s3 else "bf16"].rowscale_label, m, cin, cout, tile)
 
 
-def _linear_lowp_rowscale(fn: str, s3: bool, a: Tensor, w_packed: Tensor, bias: Optional[Tensor], scale: Tensor,
-                          r: Tensor, row_scale: Tensor, rows_per_scale: int, out: Optional[Tensor], tile: int) -> Tensor:
+def _linear_lowp_rowscale(fmt: OperandFormat, a: Tensor, w_packed: Tensor, bias: Optional[Tensor], scale: Tensor,
+                          r: Tensor, row_scale: Tensor, rows_per_scale: int, out: Optional[Tensor] = None,
+                          tile: int = -1) -> Tensor:
+    fn = fmt.rowscale_fn
     _operand(fn, "input", a, dtype=torch.bfloat16)
-    if a.dim() < 2 or (s3 and a.shape[-1] % 2):
-        raise RuntimeError(f"{fn}: input must be rows of {'split planes [..., 2 Cin]' if s3 else '[..., Cin]'} "
-                           f"(got shape {tuple(a.shape)})")
+    if a.dim() < 2 or a.shape[-1] % fmt.a_planes:
+        raise RuntimeError(f"{fn}: input must be rows [..., {fmt.a_planes} x Cin] (got shape {tuple(a.shape)})")
     width = a.shape[-1]
-    cin, m = (width // 2 if s3 else width), a.numel() // width
-    kp = -(-3 * cin // S3_KTILE) * S3_KTILE if s3 else -(-cin // BF16_KTILE) * BF16_KTILE
+    cin, m = width // fmt.a_planes, a.numel() // width
+    k = fmt.k_factor * cin
+    kp = -(-k // fmt.ktile) * fmt.ktile
     _operand(fn, "weight", w_packed, dtype=torch.bfloat16, device=a.device)
     if w_packed.dim() != 2 or w_packed.shape[1] != kp:
         raise RuntimeError(f"{fn}: packed weight {tuple(w_packed.shape)} does not match {cin} input channels "
@@ -764,11 +806,10 @@ def _linear_lowp_rowscale(fn: str, s3: bool, a: Tensor, w_packed: Tensor, bias: 
         out = r
     else:
         _operand(fn, "out", out, shape=m * cout, device=a.device)
-    k = 3 * cin if s3 else cin
-    _launch(linear_lowp_rowscale_kernel_name(m, cin, cout, tile, s3), 2.0 * m * cout * k / (3.0 if s3 else 1.0),
-            lambda: _lib.call("pipnet_linear_s3_rowscale" if s3 else "pipnet_linear_bf16_mix_rowscale", a.data_ptr(), m,
-                              cin, w_packed.data_ptr(), _ptr(bias), scale.data_ptr(), r.data_ptr(), cout,
-                              row_scale.data_ptr(), rows_per_scale, out.data_ptr(), tile, _stream(a)))
+    _launch(_lowp_label(fmt.rowscale_label, m, cin, cout, tile), 2.0 * m * cout * k / fmt.flop_div,
+            lambda: _lib.call(fmt.rowscale, a.data_ptr(), m, cin, w_packed.data_ptr(), _ptr(bias), scale.data_ptr(),
+                              r.data_ptr(), cout, row_scale.data_ptr(), rows_per_scale, out.data_ptr(), tile,
+                              _stream(a)))
     return out
 
 
@@ -778,7 +819,7 @@ def linear_bf16_mix_rowscale(a: Tensor, w_packed: Tensor, bias: Optional[Tensor]
     """fp32 r + row_scale[m // rows_per_scale] * (scale * (a w^T + bias)) on plain bf16 rows ``a`` [..., Cin]
     and a pack_conv_weight_bf16 weight: conv_bf16_mix's EPI_F32_RESID with one stochastic-depth factor per
     sample (same tile, same K order).  In place on ``r`` unless ``out`` is given; tile -1 / 0 / 4 / 5 / 7."""
-    return _linear_lowp_rowscale("linear_bf16_mix_rowscale", False, a, w_packed, bias, scale, r, row_scale,
+    return _linear_lowp_rowscale(_MIX, a, w_packed, bias, scale, r, row_scale,
                                  rows_per_scale, out, tile)
 
 
@@ -786,19 +827,8 @@ def linear_s3_rowscale(a2: Tensor, w_packed: Tensor, bias: Optional[Tensor], sca
                        row_scale: Tensor, rows_per_scale: int, out: Optional[Tensor] = None, tile: int = -1) -> Tensor:
     """The same on split planes ``a2`` [..., 2 Cin] and a split_planes_weight weight: conv_s3's EPI_F32_RESID
     with one stochastic-depth factor per sample."""
-    return _linear_lowp_rowscale("linear_s3_rowscale", True, a2, w_packed, bias, scale, r, row_scale,
+    return _linear_lowp_rowscale(_S3, a2, w_packed, bias, scale, r, row_scale,
                                  rows_per_scale, out, tile)
-
-
-def layernorm(x: Tensor, w: Tensor, b: Tensor, out: Optional[Tensor] = None) -> Tensor:
-    _operand("layernorm", "input", x)
-    c = x.shape[-1]
-    _chk_vec("layernorm", x, c, w=w, b=b)
-    _chk_same("layernorm", x, out=out)
-    y = torch.empty_like(x) if out is None else out
-    _lib.call("pipnet_layernorm_f32", x.data_ptr(), x.numel() // c, c, w.data_ptr(), b.data_ptr(), y.data_ptr(),
-              _stream(x))
-    return y
 
 
 def softmax_pool(feat_nhwc: Tensor, pool_mode: int, out=None) -> Tuple[Tensor, Tensor]:

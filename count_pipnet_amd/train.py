@@ -9,7 +9,7 @@ NonNegLinear weight / bias -> ``optimizer_classifier.step()`` (AdamW, util/args.
 
   * forward: the same HIP backbone / head as inference, plus torchvision's row stochastic
     depth -- a dropped sample skips the block's branch outright
-    (``convnext_features._cnblock_hip``); pooled is not thresholded (inference=False);
+    (``convnext_features._cnblock``); pooled is not thresholded (inference=False);
   * ``kernels.train_loss`` (csrc/train_ops.hip): align / tanh / class terms, correct count
     and d loss / d out in two launches (the align term reads the proto map once);
   * ``kernels.nonneg_linear_backward`` and ``kernels.adamw_step_`` (AdamW fused with the
