@@ -242,8 +242,9 @@ int dwconv7_ln_planes(const float* x, int B, int H, int W, int C, const float* w
 // Row LayerNorm in the same three output forms.
 template <int OUT>
 int layernorm_planes(const float* x, int64_t rows, int C, const float* w, const float* b, void* y, void* stream) {
-  if (rows < 0 || C <= 0 || C > 2048 || !x || !w || !b || !y) return PIPNET_ERR_ARG;
-  if (rows == 0) return PIPNET_OK;
+  if (rows < 0 || C <= 0 || C > 2048 || !w || !b) return PIPNET_ERR_ARG;
+  if (rows == 0) return PIPNET_OK;               // nothing to read or write: an empty tensor's pointer is null
+  if (!x || !y) return PIPNET_ERR_ARG;
   const dim3 grid((unsigned)((rows + 3) / 4));
   hipStream_t s = (hipStream_t)stream;
   const int nj = (C + 63) / 64;
