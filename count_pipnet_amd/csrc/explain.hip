@@ -152,7 +152,8 @@ __global__ __launch_bounds__(HEAD_THREADS) void map_argmax_kernel(const float* _
 // Done here as an insertion from the end that stops at the first entry >= the score.  By
 // induction the list is always the k best by (score descending, dataset index ascending).
 // Blocks past the (group, prototype) range count the abstained images (amax(out) == 0,
-// vis_pipnet.py:217-219) into one device int64.
+// vis_pipnet.py:217-219) into one device int64; torch.amax propagates NaN, so a row holding a NaN
+// is not abstained, whatever else it holds.
 struct TopkArgs {
   const float* score;      // [B, P]
   const int32_t* loc;      // [B, P]
@@ -193,10 +194,15 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_update_kernel(TopkArgs a) {
     for (int r = 0; r < TOPK_ROWS; ++r) {
       const int b = b0 + r;
       float m = -INFINITY;
+      bool nan = false;                             // fmaxf drops a NaN, torch.amax keeps it: NaN == 0 is false
       if (b < a.B)
-        for (int j = tid; j < a.K; j += TOPK_THREADS) m = fmaxf(m, a.out[(int64_t)b * a.K + j]);
+        for (int j = tid; j < a.K; j += TOPK_THREADS) {
+          const float x = a.out[(int64_t)b * a.K + j];
+          nan |= x != x;
+          m = fmaxf(m, x);
+        }
       m = wave_max(m);
-      cnt += b < a.B && m == 0.f;
+      cnt += b < a.B && m == 0.f && !__any(nan);
     }
     if (tid == 0 && cnt) atomicAdd(a.abstained, (unsigned long long)cnt);
     return;
@@ -265,11 +271,11 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_update_kernel(TopkArgs a) {
 extern "C" int pipnet_softmax_pool_argmax_f32(const float* feat, int B, int H, int W, int P, float* proto,
                                               float* pooled, int32_t* loc, void* workspace, void* stream) {
   if (B < 0 || B > 65535 || H <= 0 || W <= 0 || P <= 0 || (int64_t)H * W > INT_MAX) return PIPNET_ERR_ARG;   // B: grid.y
-  if (!feat || !pooled || !loc || !workspace) return PIPNET_ERR_ARG;
   const int nj = nj_bucket(P);
   if (nj < 0) return PIPNET_ERR_ARG;
+  if (B == 0) return PIPNET_OK;                      // an empty batch: its tensors' data pointers are null
+  if (!feat || !pooled || !loc || !workspace) return PIPNET_ERR_ARG;
   if (reinterpret_cast<uintptr_t>(workspace) & 7u) return PIPNET_ERR_ALIGN;
-  if (B == 0) return PIPNET_OK;
   hipStream_t s = (hipStream_t)stream;
   const int64_t n = (int64_t)B * P;
   unsigned long long* key = reinterpret_cast<unsigned long long*>(workspace);
@@ -291,8 +297,8 @@ extern "C" int pipnet_softmax_pool_argmax_f32(const float* feat, int B, int H, i
 extern "C" int pipnet_map_argmax_f32(const float* map, int B, int H, int W, int P, float* val, int32_t* loc,
                                      void* stream) {
   if (B < 0 || B > 65535 || H <= 0 || W <= 0 || P <= 0 || (int64_t)H * W > INT_MAX) return PIPNET_ERR_ARG;   // B: grid.y
-  if (!map || !val || !loc) return PIPNET_ERR_ARG;
   if (B == 0) return PIPNET_OK;
+  if (!map || !val || !loc) return PIPNET_ERR_ARG;
   hipLaunchKernelGGL(map_argmax_kernel, dim3((P + 63) / 64, B), dim3(HEAD_THREADS), 0, (hipStream_t)stream, map, H, W,
                      P, val, loc);
   PIPNET_CHECK_LAUNCH();
@@ -304,9 +310,9 @@ extern "C" int pipnet_topk_update(const float* score, const int32_t* loc, int B,
                                   int k, float* st_score, int64_t* st_index, int32_t* st_loc, int32_t* st_fill,
                                   int64_t* abstained, void* stream) {
   if (B < 0 || P <= 0 || G <= 0 || k < 1 || k > TOPK_MAX_K || (int64_t)G * P > INT_MAX - TOPK_THREADS) return PIPNET_ERR_ARG;
-  if (!score || !loc || !st_score || !st_index || !st_loc || !st_fill) return PIPNET_ERR_ARG;
   if (out && (K <= 0 || !abstained)) return PIPNET_ERR_ARG;
-  if (B == 0) return PIPNET_OK;
+  if (B == 0) return PIPNET_OK;                      // an empty batch: score / loc may be null
+  if (!score || !loc || !st_score || !st_index || !st_loc || !st_fill) return PIPNET_ERR_ARG;
   TopkArgs a;
   a.score = score;
   a.loc = loc;

@@ -369,7 +369,10 @@ int pipnet_softmax_pool_f32(const float* feat, int B, int HW, int P, int pool_mo
  *   After any sequence of calls the state is the reference's one-image-at-a-time list
  *   (vis_pipnet.py:248-274): the k best by (score descending, dataset index ascending).
  *   1 <= k <= PIPNET_TOPK_MAX_K.  out [B,K] (NULL to skip): images with amax(out) == 0 are added to *abstained
- *   (device int64; vis_pipnet.py:217-219), whatever their group. */
+ *   (device int64; vis_pipnet.py:217-219), whatever their group.  The test is torch's: a maximum of +0.0 or
+ *   -0.0 abstains, a subnormal maximum does not (fp32 subnormals are kept, not flushed), and a NaN anywhere in
+ *   the row means not abstained (torch.amax propagates it and NaN == 0 is false).  A negative st_fill entry is
+ *   read as 0, one above k as k, and a stored st_loc below -1 as -1. */
 #define PIPNET_TOPK_MAX_K 32
 int pipnet_softmax_pool_argmax_f32(const float* feat, int B, int H, int W, int P, float* proto, float* pooled,
                                    int32_t* loc, void* workspace, void* stream);

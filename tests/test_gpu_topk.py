@@ -17,18 +17,12 @@ import torch
 from count_pipnet_amd import kernels as K
 from count_pipnet_amd.synthetic import synth_exponential, synth_images
 from count_pipnet_amd.topk import COUNT_MIN_SCORE, img_coordinates, patch_size, prototype_topk
+from explain_ref import reference_lists as _reference_lists, topk_expected as _topk_expected, two_step_loc
 from golden_util import golden_args, load_golden
 from model_util import build_model
 from oracle import ref_cpu
 
 pytestmark = pytest.mark.gpu
-
-
-def two_step_loc(proto_nchw):
-    """vis_pipnet.py:235-238 for every (image, prototype) of a CPU [B,P,H,W] map -> (h_idx, w_idx)."""
-    max_h, h_idx = torch.max(proto_nchw, dim=2)          # over H: [B,P,W]
-    _, w_idx = torch.max(max_h, dim=2)                   # over W: [B,P]
-    return h_idx.gather(2, w_idx.unsqueeze(-1)).squeeze(-1), w_idx
 
 
 # ---- kernel (a) -------------------------------------------------------------------------------
@@ -110,20 +104,6 @@ def test_map_argmax(gpu, shape, kind):
 
 
 # ---- kernel (c) -------------------------------------------------------------------------------
-def _topk_expected(score, loc, k, groups=None, g=0, min_score=None):
-    """The k best by (score descending, dataset index ascending) per prototype, -1 padded."""
-    n, p = score.shape
-    s_out = np.zeros((p, k), np.float32)
-    i_out = -np.ones((p, k), np.int64)
-    l_out = -np.ones((p, k), np.int32)
-    for pp in range(p):
-        cand = [(-float(score[i, pp]), i) for i in range(n)
-                if (groups is None or groups[i] == g) and (min_score is None or score[i, pp] >= min_score)]
-        for j, (ns, i) in enumerate(sorted(cand)[:k]):
-            s_out[pp, j], i_out[pp, j], l_out[pp, j] = -ns, i, loc[i, pp]
-    return s_out, i_out, l_out
-
-
 def _topk_inputs(n, p, seed):
     g = torch.Generator().manual_seed(seed)
     levels = torch.tensor([0.0, 0.1, 0.25, 0.5, 1.0])
@@ -181,32 +161,6 @@ def test_topk_update_groups_min_score_and_abstain(gpu):
 
 
 # ---- end to end, PIP-Net ------------------------------------------------------------------------
-def _reference_lists(outputs, k, protos, min_score=None, groups=None):
-    """The reference loop (vis_pipnet.py:227-274 / :698-754), one image at a time on CPU copies of a
-    forward's outputs: outputs[i] = (proto [1,P,H,W], pooled [1,P], out [1,K]); groups[i] selects the
-    list an image goes to.  Returns ({(p, group): [(score, index, h_idx, w_idx), ...]}, abstained)."""
-    lists, abstained = {}, 0
-    for i, (proto, pooled, out) in enumerate(outputs):
-        if torch.amax(out, dim=1)[0].item() == 0.0:
-            abstained += 1
-        for p in protos:
-            score = pooled.squeeze(0)[p].item()
-            if min_score is not None and score < min_score:
-                continue
-            fmap = proto.squeeze(0)[p]
-            max_h, h_idx = torch.max(fmap, dim=0)
-            _, w_idx = torch.max(max_h, dim=0)
-            item = (score, i, h_idx[w_idx].item(), w_idx.item())
-            lst = lists.setdefault((p, None if groups is None else groups[i]), [])
-            if len(lst) < k:
-                lst.append(item)
-                lst.sort(key=lambda t: t[0], reverse=True)
-            elif score > lst[-1][0]:
-                lst[-1] = item
-                lst.sort(key=lambda t: t[0], reverse=True)
-    return lists, abstained
-
-
 def _assert_lists(res, lists, k, image_size):
     """Every slot of a (host) PrototypeTopK equals the reference lists, coordinates included."""
     pn, ng = res.scores.shape[:2]
