@@ -14,12 +14,20 @@ bit-identically to Pillow:
                        ``pipnet_patch_compose_rgb8`` launch per chunk lays the windows into the grids
   explanation_images   per stored entry the patch (same kernel) and the frame with the rectangle
                        outlined (``pipnet_draw_rects_rgb8``)
+  explanation_heatmaps / similarity_heatmaps
+                       per entry ``heatmap_p{p}.png`` (visualize_prediction.py:92-100): the prototype's
+                       similarity map as bytes, Pillow's bicubic resize to the frame, the colour table and
+                       the float32 blend ``0.2 * colour + 0.6 * image`` that ``plt.imsave`` turns into bytes,
+                       bit for bit and in one ``pipnet_heatmap_rgb8`` launch per ``batch_size`` entries; the
+                       map is read from the forward's own NHWC tensor
 
 No model forward runs here.  The reference opens the files without ``.convert("RGB")``; for RGB and 8-bit
 grey files the pixels it crops are those of the loader's ``convert("RGB")`` (a grey file gives a grey grid in
 three equal bands instead of one), and that is the contract: palette and alpha files follow the loader's
 ``convert("RGB")``, where the reference would resize palette indices or keep the alpha band.  The label strip,
-its text, ``grid_topk_all.png``, heatmaps, file names and PNG encoding stay with the caller.
+its text, ``grid_topk_all.png``, file names and PNG encoding stay with the caller; so do, for the heatmaps, the
+colour table itself (OpenCV's JET is an argument, not shipped), the alpha band of 255 that ``plt.imsave`` adds,
+and the matplotlib figure of vis_pipnet.py:454-486 (a scipy spline ``zoom`` under a viridis overlay).
 
 ``make_grid``'s rule is restated from torchvision's published source (the package is not a dependency).
 """
@@ -33,6 +41,7 @@ import torch
 from torch import Tensor
 
 from . import kernels as K
+from .convnext_features import as_nhwc
 from .data import DeviceEvalTransform, pack_images
 from .explain_forward import PATCH_SIZE, HostCopy, unwrap
 from .local import LocalExplanation
@@ -68,6 +77,15 @@ class ExplanationImages(HostCopy):
     patches: Tensor        # [N, 32, 32, 3] uint8 (device): the window coords[b, r, j] at the top left, 0 beyond patch_hw
     patch_hw: Tensor       # [N, 2] int64 (rows, columns) of the window
     rects: Tensor          # [N, S, S, 3] uint8 (device): the frame of image b with rect[b, r, j] outlined
+
+
+@dataclass
+class ExplanationHeatmaps(HostCopy):
+    """Result of ``explanation_heatmaps``: one row per stored entry of a ``LocalExplanation``, in (b, r, j) order,
+    the rows of ``ExplanationImages``.  ``plt.imsave`` adds an alpha band of 255 to these pixels."""
+    entry: Tensor          # [N, 3] int64 (image b, class rank r, slot j)
+    prototype: Tensor      # [N] int64 the entry's prototype p: the file is heatmap_p{p}.png
+    heatmaps: Tensor       # [N, S, S, 3] uint8 (device): the similarity map of p over the frame of image b
 
 
 # ---- selection (host) -------------------------------------------------------------------------------
@@ -257,12 +275,13 @@ def explanation_images(dataset_or_frames, res: LocalExplanation, *, image_size: 
     size; ``rects[n]`` is the frame with ``rect[b, r, j]`` outlined in yellow, ``rect_width`` wide, as
     ``ImageDraw.rectangle`` draws it (one rectangle per image, as the reference reopens the file per entry),
     produced ``batch_size`` entries at a time.  A rectangle narrower than ``2 * rect_width + 1`` raises
-    ValueError.  Pixels: see the module docstring.  File names and heatmaps stay with the caller."""
+    ValueError.  Pixels: see the module docstring.  File names stay with the caller; the third picture of an
+    entry, its heatmap, comes from ``explanation_heatmaps``."""
     if batch_size < 1:
         raise ValueError(f"explanation_images: batch_size must be at least 1, got {batch_size}")
     dev_res = res.classes.device
     res = res.cpu()
-    b, c, m = res.prototype.shape
+    b = res.prototype.shape[0]
     if torch.is_tensor(dataset_or_frames):
         frames = dataset_or_frames
         if indices is not None:
@@ -282,8 +301,7 @@ def explanation_images(dataset_or_frames, res: LocalExplanation, *, image_size: 
         frames = torch.cat(chunks) if chunks else torch.empty((0, image_size, image_size, 3), dtype=torch.uint8,
                                                               device=dev)
     dev = frames.device
-    stored = torch.clamp(res.count, max=m).tolist()
-    entry = [(bi, r, j) for bi in range(b) for r in range(c) for j in range(stored[bi][r])]
+    entry = _stored_entries(res)
     n = len(entry)
     coords, rect = res.coords.tolist(), res.rect.tolist()
     windows = [_window(coords[bi][r][j], image_size) for bi, r, j in entry]
@@ -298,3 +316,83 @@ def explanation_images(dataset_or_frames, res: LocalExplanation, *, image_size: 
     return ExplanationImages(entry=torch.tensor(entry, dtype=torch.int64).reshape(-1, 3), patches=patches,
                              patch_hw=torch.tensor([(w[1] - w[0], w[3] - w[2]) for w in windows],
                                                    dtype=torch.int64).reshape(-1, 2), rects=rects)
+
+
+def _stored_entries(res: LocalExplanation) -> List[Tuple[int, int, int]]:
+    """The stored entries (b, r, j) of ``res`` (on the host), j < min(count, max_entries), in (b, r, j) order."""
+    b, c, m = res.prototype.shape
+    stored = torch.clamp(res.count, max=m).tolist()
+    return [(bi, r, j) for bi in range(b) for r in range(c) for j in range(stored[bi][r])]
+
+
+def similarity_heatmaps(proto_features: Tensor, frames: Tensor, pairs, lut: Tensor, *, batch_size: int = 64,
+                        weights=K.HEATMAP_WEIGHTS) -> Tensor:
+    """[N, S, S, 3] uint8 on the device: per pair the RGB pixels of the reference's ``heatmap_p{p}.png``
+    (visualize_prediction.py:92-100), see the module docstring.
+
+    ``proto_features``: the [B, P, h, w] float32 similarity maps a forward returned (``net(xs, inference=True)[0]``);
+    our forward's output is NHWC-backed and is read in place, any other layout is copied once.  ``frames``
+    [F, S, S, 3] uint8: the resized images (``DeviceEvalTransform(S)(packed, device, want_u8=True)[1]``), h, w <= S.
+    ``pairs``: a list (or integer array) of (b, p), the frame being ``frames[b]``, or of (b, p, frame).  ``lut``
+    [256, 3] uint8 RGB on the device: the colour table; the reference's is
+    ``cv2.applyColorMap(np.arange(256, dtype=np.uint8), cv2.COLORMAP_JET)[:, 0, ::-1]``.  ``weights``: the factors
+    of the colour and of the image (>= 0, sum <= 1).  ``batch_size`` pairs are rendered per launch.  A wrong shape,
+    dtype, pair or ``batch_size`` raises ValueError, an operand off the ROCm device RuntimeError, before anything is
+    launched.  Nothing in the call waits for the device."""
+    if batch_size < 1:
+        raise ValueError(f"similarity_heatmaps: batch_size must be at least 1, got {batch_size}")
+    if not torch.is_tensor(proto_features) or proto_features.dim() != 4:
+        raise ValueError("similarity_heatmaps: proto_features must be the [B, P, h, w] tensor of a forward")
+    K.heatmap_shapes(proto_features.permute(0, 2, 3, 1), frames, lut)
+    K.heatmap_weights(weights)
+    b, p = proto_features.shape[:2]
+    f, s = frames.shape[:2]
+    items = np.asarray(pairs if len(pairs) else np.zeros((0, 2)), dtype=np.float64)
+    if items.ndim != 2 or items.shape[1] not in (2, 3) or (items != np.floor(items)).any():
+        raise ValueError("similarity_heatmaps: pairs must be rows of integers (b, p) or (b, p, frame)")
+    items = items.astype(np.int64)
+    if items.shape[1] == 2:
+        items = np.concatenate([items, items[:, :1]], axis=1)
+    bad = (items < 0).any(axis=1) | (items[:, 0] >= b) | (items[:, 1] >= p) | (items[:, 2] >= f)
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError(f"similarity_heatmaps: pair {i} {tuple(int(v) for v in items[i])} lies outside the {b} "
+                         f"images, {p} prototypes or {f} frames")
+    if not (proto_features.is_cuda and frames.is_cuda and lut.is_cuda):
+        raise RuntimeError("similarity_heatmaps: proto_features, frames and lut must be on a ROCm device; there is "
+                           "no CPU fallback")
+    proto = as_nhwc(proto_features)
+    n = items.shape[0]
+    out = torch.empty((n, s, s, 3), dtype=torch.uint8, device=frames.device)
+    table = torch.from_numpy(items.astype(np.int32)).to(frames.device, non_blocking=True)      # checked above, sent once
+    for i in range(0, n, batch_size):
+        K.heatmap_rgb8(proto, frames, table[i:i + batch_size], lut, weights=weights, out=out[i:i + batch_size])
+    return out
+
+
+def explanation_heatmaps(proto_features: Tensor, frames: Tensor, res: LocalExplanation, lut: Tensor, *,
+                         batch_size: int = 64) -> ExplanationHeatmaps:
+    """The ``heatmap_p{p}.png`` pixels of ``vis_pred`` (visualize_prediction.py:92-100) for every stored entry of an
+    ``explain_predictions`` result, in the (b, r, j) order of ``explanation_images``: ``heatmaps[n]`` belongs to
+    that call's ``patches[n]`` and ``rects[n]``.
+
+    ``proto_features`` [B, P, h, w] and ``frames`` [B, S, S, 3] are those of the batch ``res`` explains: the maps of
+    ``net(xs, inference=True)`` and the uint8 frames of the transform that made ``xs``.  A prototype kept under
+    several classes of an image is rendered once per occurrence, as the reference does.  ``lut``, the arithmetic
+    and the errors: ``similarity_heatmaps`` (the reference's weights 0.2 / 0.6).  But for the copy of ``res`` to the
+    host, nothing in the call waits for the device."""
+    if batch_size < 1:
+        raise ValueError(f"explanation_heatmaps: batch_size must be at least 1, got {batch_size}")
+    res = res.cpu()
+    b = res.prototype.shape[0]
+    if not torch.is_tensor(proto_features) or proto_features.dim() != 4 or proto_features.shape[0] != b or \
+            not torch.is_tensor(frames) or frames.dim() != 4 or frames.shape[0] != b:
+        raise ValueError(f"explanation_heatmaps: proto_features [B, P, h, w] and frames [B, S, S, 3] must hold the "
+                         f"{b} images of the result")
+    entry = _stored_entries(res)
+    proto = res.prototype.tolist()
+    ids = [proto[bi][r][j] for bi, r, j in entry]
+    heatmaps = similarity_heatmaps(proto_features, frames, [(e[0], p) for e, p in zip(entry, ids)], lut,
+                                   batch_size=batch_size)
+    return ExplanationHeatmaps(entry=torch.tensor(entry, dtype=torch.int64).reshape(-1, 3),
+                               prototype=torch.tensor(ids, dtype=torch.int64), heatmaps=heatmaps)

@@ -1764,6 +1764,152 @@ def draw_rects_rgb8(frames: Tensor, src, rects, width: int = 2, colour=YELLOW) -
     return out
 
 
+# ---- prototype similarity heatmaps (csrc/heatmap_ops.hip) ---------------------------------------
+BICUBIC_TAPS = 5                # coefficients per row of an upscale: 2 * support + 1
+HEATMAP_WEIGHTS = (0.2, 0.6)    # visualize_prediction.py:99
+
+
+def _bicubic(x: float) -> float:
+    """Pillow's bicubic filter (a = -0.5, support 2), in doubles."""
+    a = -0.5
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+@functools.lru_cache(maxsize=256)
+def _bicubic_rows(in_size: int, out_size: int) -> Tuple[Tuple[int, ...], ...]:
+    scale = in_size / out_size
+    filterscale = max(scale, 1.0)
+    support = 2.0 * filterscale
+    ss = 1.0 / filterscale
+    rows = []
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        n = min(int(center + support + 0.5), in_size) - xmin
+        k = [_bicubic((x + xmin - center + 0.5) * ss) for x in range(n)]
+        ww = 0.0
+        for v in k:                         # a sequential sum, as the C loop's
+            ww += v
+        if ww != 0.0:
+            k = [v / ww for v in k]
+        q = [int(-0.5 + v * (1 << 22)) if v < 0 else int(0.5 + v * (1 << 22)) for v in k]
+        assert n <= BICUBIC_TAPS, (in_size, out_size, xx, n)
+        rows.append((xmin, n) + tuple(q) + (0,) * (BICUBIC_TAPS - n))
+    return tuple(rows)
+
+
+def bicubic_rows(in_size: int, out_size: int) -> Tensor:
+    """int32 [out_size, 2 + 5] on the host: per output coordinate the row (xmin, n, k[0..5)) of Pillow's
+    ``ImagingResample`` with ``BICUBIC`` for an 8-bit axis resized ``in_size`` -> ``out_size``: ``precompute_coeffs``
+    in Python doubles (sequential sums, weights normalised by their sum), then 22-bit fixed point rounded half away
+    from zero (``normalize_coeffs_8bpc``).  Upscale only (``1 <= in_size <= out_size``): a row then has at most 5
+    coefficients.  ``pipnet_heatmap_rgb8`` reads these tables; tests/test_heatmap_cpu.py holds them against Pillow."""
+    in_size, out_size = int(in_size), int(out_size)
+    if not 1 <= in_size <= out_size:
+        raise ValueError(f"bicubic_rows: only 1 <= in_size <= out_size is supported, got {in_size} -> {out_size}")
+    return torch.tensor(_bicubic_rows(in_size, out_size), dtype=torch.int32).reshape(out_size, 2 + BICUBIC_TAPS)
+
+
+_BICUBIC_DEV = {}
+
+
+def _bicubic_rows_on(in_size: int, out_size: int, dev: torch.device) -> Tensor:
+    """``bicubic_rows`` on ``dev``, uploaded once per (sizes, device)."""
+    key = (int(in_size), int(out_size), dev)
+    t = _BICUBIC_DEV.get(key)
+    if t is None:
+        t = _BICUBIC_DEV[key] = bicubic_rows(in_size, out_size).to(dev)
+    return t
+
+
+def heatmap_weights(weights) -> Tuple[float, float]:
+    """(w_heat, w_img) as floats; ValueError unless both are >= 0 and their float32 sum is at most 1, the range in
+    which ``plt.imsave`` accepts the blended image."""
+    import numpy as np
+    try:
+        wh, wi = (float(v) for v in weights)
+    except (TypeError, ValueError):
+        raise ValueError(f"heatmap_rgb8: weights must be two numbers (w_heat, w_img), got {weights!r}") from None
+    if not (wh >= 0 and wi >= 0 and np.float32(wh) + np.float32(wi) <= np.float32(1)):
+        raise ValueError(f"heatmap_rgb8: weights must be >= 0 and sum to at most 1, got {weights!r}")
+    return wh, wi
+
+
+def heatmap_shapes(proto_nhwc: Tensor, frames: Tensor, lut: Tensor) -> Tuple[int, int, int, int, int, int]:
+    """(B, h, w, P, F, S) of the operands of ``heatmap_rgb8``; ValueError where a dtype or a shape is not the
+    documented one.  Attribute comparisons only, on any device."""
+    fn = "heatmap_rgb8"
+    for what, t in (("proto_nhwc", proto_nhwc), ("frames", frames), ("lut", lut)):
+        if not torch.is_tensor(t):
+            raise ValueError(f"{fn}: {what} must be a tensor, got {type(t).__name__}")
+    if proto_nhwc.dtype != torch.float32 or proto_nhwc.dim() != 4 or min(proto_nhwc.shape[1:]) < 1:
+        raise ValueError(f"{fn}: proto_nhwc must be float32 [B,h,w,P] with h, w, P >= 1, got {proto_nhwc.dtype} "
+                         f"{tuple(proto_nhwc.shape)}")
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[1] != frames.shape[2] \
+            or frames.shape[1] < 1:
+        raise ValueError(f"{fn}: frames must be uint8 [F,S,S,3], got {frames.dtype} {tuple(frames.shape)}")
+    if lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3):
+        raise ValueError(f"{fn}: lut must be uint8 [256,3] (RGB), got {lut.dtype} {tuple(lut.shape)}")
+    b, h, w, p = proto_nhwc.shape
+    f, s = frames.shape[:2]
+    if h > s or w > s:
+        raise ValueError(f"{fn}: the {h} x {w} map is larger than the {s} x {s} frame; only the upscale is supported")
+    return b, h, w, p, f, s
+
+
+def heatmap_rgb8(proto_nhwc: Tensor, frames: Tensor, items, lut: Tensor, *, weights=HEATMAP_WEIGHTS,
+                 out: Optional[Tensor] = None, resized: Optional[Tensor] = None) -> Tensor:
+    """[N,S,S,3] uint8: per row (b, p, frame) of the host integer table ``items`` [N,3] the ``heatmap_p{p}.png``
+    pixels of visualize_prediction.py:92-100 -- the map ``proto_nhwc[b, :, :, p]`` quantised to bytes, resized to
+    S x S as Pillow's ``BICUBIC`` does, looked up in ``lut`` [256,3] uint8 (RGB) and blended in float32 as
+    ``weights[0] * colour / 255 + weights[1] * frames[frame] / 255``, then ``(v * 255).astype(uint8)``
+    (pipnet_heatmap_rgb8; bit for bit).  ``proto_nhwc`` [B,h,w,P] float32 with ``h, w <= S``, ``frames`` [F,S,S,3]
+    uint8, all dense and on one ROCm device.  ``out`` [N,S,S,3] uint8 and ``resized`` [N,S,S] uint8 (the bytes
+    after the resize) are written when given.  A wrong dtype, shape or weight raises ValueError, a wrong device
+    or layout or a row of ``items`` out of range RuntimeError; nothing is launched then.  ``items`` may also be
+    an int32 [N,3] tensor already on the device (one upload for many launches): its rows cannot be read here, the
+    caller has checked them, and the kernel writes nothing for a row out of range.  One launch (none for N == 0),
+    on the current stream."""
+    fn = "heatmap_rgb8"
+    b, h, w, p, f, s = heatmap_shapes(proto_nhwc, frames, lut)
+    wh, wi = heatmap_weights(weights)
+    _operand(fn, "proto_nhwc", proto_nhwc)
+    dev = proto_nhwc.device
+    _frames(fn, "frames", frames, dev)
+    _operand(fn, "lut", lut, dtype=torch.uint8, shape=torch.Size((256, 3)), device=dev)
+    if torch.is_tensor(items) and items.is_cuda:       # a table already on the device: the caller has checked it
+        if items.dim() != 2:
+            raise RuntimeError(f"{fn}: a device table of items must be int32 [N,3], got shape {tuple(items.shape)}")
+        _operand(fn, "items", items, dtype=torch.int32, shape=torch.Size((items.shape[0], 3)), device=dev)
+        it_dev, n = items, items.shape[0]
+    else:
+        it = _host_i32(fn, "items", items, 3)
+        n = it.shape[0]
+        bad = (it < 0).any(axis=1) | (it[:, 0] >= b) | (it[:, 1] >= p) | (it[:, 2] >= f)
+        if bad.any():
+            i = int(bad.argmax())
+            raise RuntimeError(f"{fn}: item {i} {tuple(int(v) for v in it[i])} lies outside the {b} images, {p} "
+                               f"prototypes or {f} frames")
+        it_dev = torch.from_numpy(it).to(dev, non_blocking=True) if n else None
+    if out is None:
+        out = torch.empty((n, s, s, 3), device=dev, dtype=torch.uint8)
+    else:
+        _operand(fn, "out", out, dtype=torch.uint8, shape=torch.Size((n, s, s, 3)), device=dev)
+    _operand(fn, "resized", resized, dtype=torch.uint8, shape=torch.Size((n, s, s)), device=dev, optional=True)
+    if n == 0:
+        return out
+    rows_h, rows_v = _bicubic_rows_on(w, s, dev), _bicubic_rows_on(h, s, dev)
+    _lib.call("pipnet_heatmap_rgb8", proto_nhwc.data_ptr(), b, h, w, p, frames.data_ptr(), f, s, it_dev.data_ptr(), n,
+              lut.data_ptr(), rows_h.data_ptr(), rows_v.data_ptr(), wh, wi, out.data_ptr(), _ptr(resized),
+              torch.cuda.current_stream(dev).cuda_stream)
+    return out
+
+
 # ---- two-view training augmentation (csrc/augment_ops.hip) ----------------------------------
 AUG_GEOM_PARAMS, AUG_VIEW_PARAMS = _lib.CONSTANTS["AUG_GEOM_PARAMS"], _lib.CONSTANTS["AUG_VIEW_PARAMS"]
 AUG_OP_SHARPNESS, AUG_OP_LAST = 4, 8

@@ -64,7 +64,8 @@ extern "C" {
  * pipnet_draw_rects_rgb8) and the attribution-image entry points (pipnet_saliency_*), and the row-scaled
  * low-precision Linear2 (pipnet_linear_bf16_mix_rowscale, pipnet_linear_s3_rowscale + _label), and the state
  * merges of the sharded dataset passes (pipnet_topk_merge, pipnet_proto_stats_merge, pipnet_colsum_merge_f64,
- * pipnet_part_purity_merge); no signature changed. */
+ * pipnet_part_purity_merge), and the similarity-heatmap entry point (pipnet_heatmap_rgb8); no signature
+ * changed. */
 #define PIPNET_AMD_ABI_VERSION 4
 int pipnet_amd_abi_version(void);
 const char* pipnet_amd_status_string(int status);
@@ -925,6 +926,36 @@ int pipnet_patch_compose_rgb8(const uint8_t* frames, int F, int fh, int fw, cons
                               uint8_t* canvases, int C, int ch, int cw, void* stream);
 int pipnet_draw_rects_rgb8(const uint8_t* frames, int F, int fh, int fw, const int32_t* src, const int32_t* rects,
                            int N, int width, int r, int g, int b, uint8_t* out, void* stream);
+
+/* ---- prototype similarity heatmaps (util/visualize_prediction.py:92-100, heatmap_p{p}.png;
+ * csrc/heatmap_ops.hip) ------------------------------------------------------------------------------------
+ * pipnet_heatmap_rgb8: per row (b, p, frame) of items [N,3] int32 (device) the S x S RGB picture the reference
+ *   writes for prototype p of image b, bit for bit:
+ *     q   = uint8(trunc(m * 255f)) of the map m = proto[b, :, :, p], saturated to 0..255 (domain 0 <= m <= 1 +
+ *           2^-22; NaN is outside the contract and reads as 0);
+ *     r   = Pillow's Image.resize((S, S), BICUBIC) of the 8-bit band q: horizontal pass, uint8 intermediate,
+ *           vertical pass, each clip8(((1 << 21) + sum(u8 * k)) >> 22); a pass whose axis keeps its size is
+ *           skipped;
+ *     v   = fl(fl(w_heat * fl(lut[r][c] / 255f)) + fl(w_img * fl(frames[frame][y][x][c] / 255f))), float32, no
+ *           fused multiply-add, correctly rounded divisions;
+ *     out = uint8(trunc(fl(v * 255f))), saturated to 0..255 (plt.imsave(vmin=0, vmax=1) without its alpha band).
+ *   proto [B,h,w,P] float32 (the NHWC storage of a forward's proto_features), frames [F,S,S,3] uint8, lut [256,3]
+ *   uint8 (RGB; the caller's colour table, cv2.COLORMAP_JET reversed to RGB in the reference), out [N,S,S,3]
+ *   uint8, resized [N,S,S] uint8 or NULL: the bytes r.  rows_h / rows_v [S,7] int32 (device): the coefficient
+ *   row (xmin, n, k[0..5)) of every output column (w -> S) and output row (h -> S): Pillow's precompute_coeffs
+ *   for the bicubic filter (a = -0.5, support 2) in doubles, normalised, in 22-bit fixed point rounded half away
+ *   from zero (normalize_coeffs_8bpc); n <= 5.  Both pointers must be non-NULL; a table is read only where its
+ *   pass runs.  The kernel
+ *   clamps every index it reads from them, so a wrong table gives wrong pixels and no access outside an operand.
+ *   Upscale only: 1 <= h, w <= S.  A row of items with b, p or frame out of range writes nothing.  Four pixels
+ *   per lane (12-byte accesses) when S % 4 == 0 and frames, out and resized are 4-byte aligned, one byte per lane
+ *   otherwise; the same bytes.  S * S below 2^29, N * ceil(S / 16) workgroups of 256 threads below 2^24 (a grid holds fewer than 2^32
+ *   threads), and 4096 + 22 * (ceil16(S) +
+ *   ceil16(w)) bytes of LDS within 64 KiB (S + w up to about 2,700); byte offsets are 64-bit.  N == 0 launches
+ *   nothing.  A violation or a NULL pointer (but resized) returns PIPNET_ERR_ARG before any HIP call. */
+int pipnet_heatmap_rgb8(const float* proto, int B, int h, int w, int P, const uint8_t* frames, int F, int S,
+                        const int32_t* items, int N, const uint8_t* lut, const int32_t* rows_h, const int32_t* rows_v,
+                        float w_heat, float w_img, uint8_t* out, uint8_t* resized, void* stream);
 
 /* ---- attribution images (util/interpret_idg.py:413-427 fold / normalise / blend, :183-204
  * normalize_attribution_map, :442-446 un-normalised image, :626-641 logit mode; csrc/saliency_ops.hip) ----

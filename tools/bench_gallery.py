@@ -10,7 +10,20 @@ for a pass.  Timed, each with a host clock ending in a device synchronise where 
   reference  vis_pipnet.py's procedure restated with Pillow: per shown entry Image.open -> Resize -> crop
              (ToTensor / make_grid / ToPILImage are copies of the same bytes and are left out)
 
+``--heatmaps`` times the similarity heatmaps instead (gallery.explanation_heatmaps, pipnet_heatmap_rgb8) at C2
+dimensions: 64 images, a 26 x 26 x 768 map, 224^2 frames, a LocalExplanation of 3 classes with ``--entries`` kept
+prototypes each.  Random maps and frames stand in for a forward (the kernel's work does not depend on the values):
+
+  heatmaps   explanation_heatmaps, whole call, device events around it
+  launches   the pipnet_heatmap_rgb8 launches alone into a preallocated result (events), and the bytes the
+             algorithm moves per second: per entry one h x w float32 channel and one frame in, one picture out;
+             both at ``--batch-size`` entries per launch and with every entry in one launch
+  reference  the reference's heatmap chain (visualize_prediction.py:92-99) per entry on the host CPU with torch,
+             Pillow and numpy, the copy of the [B, P, h, w] maps to the host included (a table lookup stands in for
+             cv2.applyColorMap)
+
 Usage: python tools/bench_gallery.py [--prototypes 768] [--k 10] [--size 224] [--images 1024] [--out FILE]
+       python tools/bench_gallery.py --heatmaps [--entries 8] [--size 224] [--batch-size 64] [--out FILE]
 """
 import argparse
 import os
@@ -20,13 +33,15 @@ import time
 
 import numpy as np
 import torch
+from PIL import Image
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from count_pipnet_amd import kernels as K                                               # noqa: E402
 from count_pipnet_amd.data import DecodedImageFolder, DeviceEvalTransform, pack_images  # noqa: E402
 from count_pipnet_amd.explain_forward import img_coordinates, patch_skip                # noqa: E402
-from count_pipnet_amd.gallery import prototype_gallery                                  # noqa: E402
+from count_pipnet_amd.gallery import explanation_heatmaps, prototype_gallery            # noqa: E402
+from count_pipnet_amd.local import LocalExplanation                                     # noqa: E402
 from count_pipnet_amd.topk import PrototypeTopK                                         # noqa: E402
 
 
@@ -67,8 +82,127 @@ def reference_procedure(ds, res: PrototypeTopK, size: int) -> int:
     return done
 
 
+HBM_ACHIEVABLE = 6.3e12         # bytes / s a streaming kernel reaches on an MI355X (8 TB/s peak)
+
+
+def jet_like_lut() -> np.ndarray:
+    """[256, 3] uint8 RGB ramps shaped like JET; the arithmetic does not depend on the table's values."""
+    x = np.arange(256) / 255.0
+    rgb = [np.clip(1.5 - np.abs(4 * x - c), 0, 1) for c in (3, 2, 1)]
+    return np.round(np.stack(rgb, axis=1) * 255).astype(np.uint8)
+
+
+def synthetic_explanation(b: int, classes: int, entries: int, pn: int) -> LocalExplanation:
+    g = torch.Generator().manual_seed(3)
+    z = lambda *s: torch.zeros(*s, dtype=torch.int64)      # noqa: E731
+    zf = lambda *s: torch.zeros(*s)                        # noqa: E731
+    return LocalExplanation(classes=z(b, classes), logits=zf(b, classes),
+                            count=torch.full((b, classes), entries, dtype=torch.int64),
+                            prototype=torch.randint(0, pn, (b, classes, entries), generator=g),
+                            similarity=zf(b, classes, entries), weight=zf(b, classes, entries),
+                            simweight=zf(b, classes, entries), h_idx=z(b, classes, entries), w_idx=z(b, classes, entries),
+                            coords=z(b, classes, entries, 4), rect=z(b, classes, entries, 4), proto_shape=(1, pn, 26, 26))
+
+
+def host_heatmaps(feats: torch.Tensor, frames: torch.Tensor, res: LocalExplanation, lut: np.ndarray, size: int) -> int:
+    """The baseline: what the reference's vis_pred does per stored entry for its heatmap, with the same libraries, on
+    the host -- both device-to-host copies, then per entry the map as an 8-bit image (torch), Pillow's bicubic resize,
+    back to float32 in 0..1, the table lookup on ``uint8(255 * .)`` and the float32 blend 0.2 * colour + 0.6 * image.
+    Writing the PNG is left out on both sides."""
+    maps_host, frames_host = feats.cpu(), frames.cpu()
+    made = 0
+    for bi in range(res.prototype.shape[0]):
+        picture = frames_host[bi].float().div(255).numpy()                 # one float image per frame
+        for p in res.prototype[bi].flatten().tolist():
+            small = Image.fromarray(maps_host[bi, p].mul(255).byte().numpy(), "L")
+            unit = torch.from_numpy(np.array(small.resize((size, size), Image.BICUBIC))).float().div(255).numpy()
+            colour = lut[(255 * unit).astype(np.uint8)].astype(np.float32) / 255
+            blended = 0.2 * colour + 0.6 * picture
+            made += int(blended.shape == (size, size, 3) and blended.dtype == np.float32)
+    return made
+
+
+def time_heatmaps(say, nhwc, feats, frames, res, lut, batch_size: int) -> float:
+    """Times ``explanation_heatmaps`` and its launches alone at ``batch_size``; the whole call's best time in ms."""
+    n, s = res.prototype.numel(), frames.shape[1]
+    per_entry = nhwc.shape[1] * nhwc.shape[2] * 4 + 2 * s * s * 3
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    whole = []
+    for i in range(6):                                                     # the first call is the warm-up
+        torch.cuda.synchronize()
+        start.record()
+        out = explanation_heatmaps(feats, frames, res, lut, batch_size=batch_size)
+        end.record()
+        torch.cuda.synchronize()
+        whole.append(start.elapsed_time(end))
+    assert tuple(out.heatmaps.shape) == (n, s, s, 3)
+    say(f"batch_size {batch_size}:")
+    say(f"heatmaps   explanation_heatmaps, whole call (events)   {min(whole[1:]):9.3f} ms   (5 runs: "
+        + ", ".join(f"{t:.3f}" for t in whole[1:]) + ")")
+    items = [(int(e[0]), int(q), int(e[0])) for e, q in zip(out.entry.tolist(), out.prototype.tolist())]
+    table = torch.tensor(items, dtype=torch.int32, device=frames.device)   # sent once, as the call above does
+    chunks = [table[i:i + batch_size] for i in range(0, n, batch_size)]
+    dst = torch.empty_like(out.heatmaps)
+    reps, alone = 20, []
+    for i in range(4):
+        torch.cuda.synchronize()
+        start.record()
+        for _ in range(reps):
+            for c, it in enumerate(chunks):
+                K.heatmap_rgb8(nhwc, frames, it, lut, out=dst[c * batch_size:c * batch_size + len(it)])
+        end.record()
+        torch.cuda.synchronize()
+        alone.append(start.elapsed_time(end) / reps)
+    assert torch.equal(dst, out.heatmaps)
+    rate = n * per_entry / (min(alone[1:]) * 1e-3)
+    say(f"launches   {len(chunks)} pipnet_heatmap_rgb8 launch(es) (events)      {min(alone[1:]):9.3f} ms   (3 x {reps} runs: "
+        + ", ".join(f"{t:.3f}" for t in alone[1:]) + f"), {min(alone[1:]) / len(chunks) * 1e3:.1f} us per launch")
+    say(f"           {rate / 1e12:.3f} TB/s of algorithmic bytes = {100 * rate / HBM_ACHIEVABLE:.1f} % of the "
+        f"{HBM_ACHIEVABLE / 1e12:.1f} TB/s a streaming kernel reaches from HBM (8 TB/s peak)")
+    return min(whole[1:])
+
+
+def heatmaps_main(a, dev, say) -> None:
+    b, pn, hw, classes, s = 64, 768, 26, 3, a.size
+    g = torch.Generator().manual_seed(4)
+    nhwc = torch.rand((b, hw, hw, pn), generator=g).to(dev)
+    feats = nhwc.permute(0, 3, 1, 2)                                       # [B, P, h, w], NHWC-backed as a forward's
+    frames = torch.randint(0, 256, (b, s, s, 3), generator=g, dtype=torch.uint8).to(dev)
+    lut_np = jet_like_lut()
+    lut = torch.from_numpy(lut_np).to(dev)
+    res = synthetic_explanation(b, classes, a.entries, pn)
+    n = b * classes * a.entries
+    per_entry = hw * hw * 4 + 2 * s * s * 3
+    say("python tools/bench_gallery.py " + " ".join(sys.argv[1:]))
+    say(f"{b} images x {classes} classes x {a.entries} prototypes = {n} heatmaps at {s}^2 from a {hw} x {hw} x {pn} map; "
+        f"{per_entry} bytes per entry (one channel and one frame in, one picture out), {n * per_entry / 1e6:.1f} MB in "
+        f"all, the {b * s * s * 3 / 1e6:.1f} MB of frames re-read from cache; the maps are {nhwc.numel() * 4 / 1e6:.0f} MB")
+    best = time_heatmaps(say, nhwc, feats, frames, res, lut, a.batch_size)
+    if n != a.batch_size:
+        time_heatmaps(say, nhwc, feats, frames, res, lut, n)               # every entry in one launch
+    t0 = time.perf_counter()
+    done = host_heatmaps(feats, frames, res, lut_np, s)
+    t_ref = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    feats.cpu()
+    t_copy = time.perf_counter() - t0
+    say(f"reference  the reference's chain per entry on the host {t_ref * 1e3:9.1f} ms   ({done} entries, "
+        f"{t_ref / done * 1e3:.2f} ms per entry; {t_copy * 1e3:.1f} ms of it the copy of the maps to the host, "
+        f"torch {torch.get_num_threads()} threads)")
+    say(f"reference / heatmaps at batch_size {a.batch_size} = {t_ref * 1e3 / best:.0f}")
+
+
+def write_out(path, lines) -> None:
+    if path:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--heatmaps", action="store_true", help="time the similarity heatmaps instead of the gallery")
+    ap.add_argument("--entries", type=int, default=8, help="--heatmaps: kept prototypes per (image, class)")
     ap.add_argument("--prototypes", type=int, default=768)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--size", type=int, default=224)
@@ -85,6 +219,10 @@ def main() -> None:
         print(s, flush=True)
         lines.append(s)
 
+    if a.heatmaps:
+        heatmaps_main(a, dev, say)
+        write_out(a.out, lines)
+        return
     with tempfile.TemporaryDirectory() as root:
         t0 = time.perf_counter()
         write_folder(root, a.images)
@@ -133,10 +271,7 @@ def main() -> None:
         say(f"reference  Pillow open -> resize -> crop per entry    {t_ref * 1e3:9.1f} ms   ({done} entries, "
             f"{t_ref / done * 1e3:.2f} ms per entry)")
         say(f"reference / gallery = {t_ref / min(times):.1f}")
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    write_out(a.out, lines)
 
 
 if __name__ == "__main__":
