@@ -90,18 +90,30 @@ Located = namedtuple("Located", "scores loc out hw raw")
 def located_forward(net, xs: Tensor, small: Optional[bool], with_raw: bool = False) -> Located:
     """(scores [B,P], loc [B,P] int32, logits [B,K], (H, W), raw) of one batch: the inference forward with the flat
     location h * W + w of every prototype's maximum.  Every image gets the bits of its own batch-1 forward, whatever
-    the batch; ``small``: ``small_map`` of the latent map.
+    the batch; ``small``: ``small_map`` of the latent map.  ``located_forward_maps`` also returns the map.
 
     PIP-Net: PIPNet._forward_hip with the arg-location head in place of softmax_pool, the proto map not stored
     (fp32 logits); scores are the clamped pooled values, ``raw`` the unclamped ones (the non-inference forward's)
     with ``with_raw``; ``small`` False is the plain forward's path, concurrent sub-batches included.
     CountPIPNet: its own forward (scores: the clamped counts), then the arg-location on its 0/1 map; no ``raw``."""
+    return _located(net, xs, small, with_raw, False)[0]
+
+
+def located_forward_maps(net, xs: Tensor, small: Optional[bool]) -> Tuple[Located, Tensor]:
+    """``located_forward`` and the fp32 prototype map [B,P,H,W] (NHWC memory) its scores and locations were read
+    from.  PIP-Net: the head writes the map (``softmax_pool_argmax(write_proto=True)``; pooled values, locations
+    and logits keep their bits) and the batch runs on one stream, every image still on the plan of its own batch-1
+    forward.  CountPIPNet: the map its forward returns."""
+    return _located(net, xs, small, False, True)
+
+
+def _located(net, xs: Tensor, small: Optional[bool], with_raw: bool, with_proto: bool):
     b = xs.shape[0]
     if is_count(net):
         with K.per_image_gemm_plan(b if small is not False else 1):
             proto, clamped, out = net(xs, inference=True)
         _, loc = K.map_argmax(as_nhwc(proto))
-        return Located(clamped, loc, out, tuple(proto.shape[2:]), None)
+        return Located(clamped, loc, out, tuple(proto.shape[2:]), None), proto
     cls = net._classification
     dev = xs.device
     pn, kc = cls.weight.shape[1], cls.weight.shape[0]
@@ -110,19 +122,24 @@ def located_forward(net, xs: Tensor, small: Optional[bool], with_raw: bool = Fal
     clamped = torch.empty((b, pn), device=dev, dtype=torch.float32)
     out = torch.empty((b, kc), device=dev, dtype=torch.float32)
 
+    maps = []
+
     def head(logits, i0, i1):
         if logits.dtype == torch.bfloat16:      # bf16 build: its own head, then the location on the fp32 map
             proto, _ = K.softmax_pool_bf16(logits, 0)
             K.map_argmax(proto, out=(pooled[i0:i1], loc[i0:i1]))
         else:
-            K.softmax_pool_argmax(logits, out=(pooled[i0:i1], loc[i0:i1]))
+            proto = K.softmax_pool_argmax(logits, write_proto=with_proto, out=(pooled[i0:i1], loc[i0:i1]))[0]
+        if with_proto:
+            maps.append(proto)
         K.nonneg_linear(pooled[i0:i1], cls.weight, cls.bias, PRESENCE_THRESHOLD, out=(clamped[i0:i1], out[i0:i1]))
 
-    n = stream_split(net, xs) if small is False else 1
+    n = stream_split(net, xs) if small is False and not with_proto else 1      # the map: one part, one stream
     with K.per_image_gemm_plan(b if n == 1 else 1):    # n > 1: the plain forward's concurrent sub-batches
         streams, logits = sub_batch_logits(net, xs, n)
     run_heads(streams, logits, head)
-    return Located(clamped, loc, out, tuple(logits[0].shape[1:3]), pooled if with_raw else None)
+    return (Located(clamped, loc, out, tuple(logits[0].shape[1:3]), pooled if with_raw else None),
+            maps[0].permute(0, 3, 1, 2) if with_proto else None)
 
 
 def patch_size(args) -> Tuple[int, int]:

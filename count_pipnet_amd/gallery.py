@@ -20,14 +20,25 @@ bit-identically to Pillow:
                        the float32 blend ``0.2 * colour + 0.6 * image`` that ``plt.imsave`` turns into bytes,
                        bit for bit and in one ``pipnet_heatmap_rgb8`` launch per ``batch_size`` entries; the
                        map is read from the forward's own NHWC tensor
+  prototype_map_overlays / feature_map_overlays
+                       per entry the arrays behind ``feature_maps/prototype_{p}/*_overlay.png``
+                       (vis_pipnet.py:454-475, :1000-1021): the prototype's similarity map, its
+                       ``scipy.ndimage.zoom`` to the image (a cubic B-spline in float64), ``mask = resized > 0.1``
+                       and the RGBA overlay ``(*cmap(resized[y, x])[:3], 0.7)`` the reference fills in a Python
+                       loop over the pixels, bit for bit and in one ``pipnet_map_overlay`` launch per
+                       ``batch_size`` entries; ``select_map_entries`` is the rule that picks up to three stored
+                       images per prototype (:362-391, :897-922)
 
-No model forward runs here.  The reference opens the files without ``.convert("RGB")``; for RGB and 8-bit
+Only ``prototype_map_overlays`` runs a model forward (the pass keeps no maps, so the selected images go through
+the located forward once more).  The reference opens the files without ``.convert("RGB")``; for RGB and 8-bit
 grey files the pixels it crops are those of the loader's ``convert("RGB")`` (a grey file gives a grey grid in
 three equal bands instead of one), and that is the contract: palette and alpha files follow the loader's
 ``convert("RGB")``, where the reference would resize palette indices or keep the alpha band.  The label strip,
 its text, ``grid_topk_all.png``, file names and PNG encoding stay with the caller; so do, for the heatmaps, the
-colour table itself (OpenCV's JET is an argument, not shipped), the alpha band of 255 that ``plt.imsave`` adds,
-and the matplotlib figure of vis_pipnet.py:454-486 (a scipy spline ``zoom`` under a viridis overlay).
+colour table itself (OpenCV's JET is an argument, not shipped) and the alpha band of 255 that ``plt.imsave`` adds,
+and for the overlays the viridis table (an argument: ``matplotlib.colormaps['viridis'](np.arange(256))[:, :3]``)
+and the matplotlib figures themselves: titles, the rectangle, the colour bar, ``*_original.png`` and
+``*_feature_map.png``.
 
 ``make_grid``'s rule is restated from torchvision's published source (the package is not a dependency).
 """
@@ -43,7 +54,7 @@ from torch import Tensor
 from . import kernels as K
 from .convnext_features import as_nhwc
 from .data import DeviceEvalTransform, pack_images
-from .explain_forward import PATCH_SIZE, HostCopy, unwrap
+from .explain_forward import PATCH_SIZE, HostCopy, located_forward_maps, map_is_small, note_map, unwrap
 from .local import LocalExplanation
 from .topk import PrototypeTopK
 
@@ -86,6 +97,30 @@ class ExplanationHeatmaps(HostCopy):
     entry: Tensor          # [N, 3] int64 (image b, class rank r, slot j)
     prototype: Tensor      # [N] int64 the entry's prototype p: the file is heatmap_p{p}.png
     heatmaps: Tensor       # [N, S, S, 3] uint8 (device): the similarity map of p over the frame of image b
+
+
+@dataclass
+class PrototypeMapOverlays(HostCopy):
+    """Result of ``prototype_map_overlays``: one row per shown entry, prototypes ascending and within a prototype
+    in file order.  PIP-Net names the files ``proto_{p}_rank_{rank}_of_{of}_score_{score:.3f}``, CountPIPNet
+    ``proto_{p}_count_{groups[g]}_model_count_{score:.1f}_class_{label}``.  The pixel tensors stay on the device
+    until ``.cpu()`` is asked for; the small tables are built on the host and stay there."""
+    entry: Tensor          # [N, 3] int64 (prototype p, group position g, slot j): res.scores[p, g, j]
+    rank: Tensor           # [N] int64 i + 1 of the entry among its prototype's
+    of: Tensor             # [N] int64 how many entries its prototype has
+    index: Tensor          # [N] int64 dataset index of the image
+    score: Tensor          # [N] float32
+    coords: Tensor         # [N, 4] int64 (h_min, h_max, w_min, w_max): the rectangle
+    h_idx: Tensor          # [N] int64 latent row of the maximum: the red cross of *_feature_map.png
+    w_idx: Tensor          # [N] int64 latent column
+    maps: Tensor           # [N, h, w] float32 (device): feature_map_np
+    map_sum: Tensor        # [N] float64: the map summed in float64, row-major from the first element on
+    resized: Tensor        # [N, S, S] float32 (device): zoom(feature_map_np, (S / h, S / w))
+    mask: Tensor           # [N, S, S] uint8 (device): resized > 0.1
+    colour: Tensor         # [N, S, S] uint8 (device): the row of the colour table, 0 off the mask
+    overlay: Optional[Tensor]     # [N, S, S, 4] float64 (device): what plt.imshow(overlay, alpha=0.7) is given; None unless wanted
+    frame_index: Tensor    # [F] int64 the distinct dataset indices of the entries, ascending
+    frames: Optional[Tensor]      # [F, S, S, 3] uint8 (device) resized images of frame_index; None unless keep_frames
 
 
 # ---- selection (host) -------------------------------------------------------------------------------
@@ -144,6 +179,48 @@ def select_entries(res: PrototypeTopK) -> List[List[Tuple[int, int]]]:
     if res.groups == [None]:
         return [_pipnet_selection(index, selected, unused, p) for p in range(len(index))]
     return [_count_selection(scores, index, res.groups, selected, p, k) for p in range(len(index))]
+
+
+def _pipnet_map_selection(scores, index, selected, unused, p: int, most: int) -> List[Tuple[int, int]]:
+    """vis_pipnet.py:362-391: the highest, the middle and the lowest stored image that still exceeds 0.1."""
+    if not selected[p] or unused[p]:
+        return []
+    slots = [j for j, i in enumerate(index[p][0]) if i >= 0]
+    n = len(slots)
+    if n == 0:
+        return []
+    picked = [0]
+    if n > 2:
+        picked.append(n // 2)
+    if n > 1:
+        lowest = n - 1
+        while lowest > 0 and scores[p][0][slots[lowest]] < 0.1:
+            lowest -= 1
+        if lowest not in picked:
+            picked.append(lowest)
+    return [(0, slots[i]) for i in picked[:most]]
+
+
+def _count_map_selection(index, groups, selected, p: int, most: int) -> List[Tuple[int, int]]:
+    """vis_pipnet.py:897-922: per non-empty count group, counts ascending, the image with the largest model count.
+    A group's list is sorted by it and ``sorted`` is stable, so that is the group's first stored slot."""
+    if not selected[p]:
+        return []
+    order = sorted(range(len(groups)), key=lambda g: groups[g])
+    first = [(g, next((j for j, i in enumerate(index[p][g]) if i >= 0), None)) for g in order]
+    return [(g, j) for g, j in first if j is not None][:most]
+
+
+def select_map_entries(res: PrototypeTopK, max_per_prototype: int = 3) -> List[List[Tuple[int, int]]]:
+    """Per prototype the (group position, slot) entries whose feature maps the reference draws
+    (``max_feature_maps_per_prototype``), in file order; an empty list where it draws none.  ``res`` on the host."""
+    if isinstance(max_per_prototype, bool) or not isinstance(max_per_prototype, int) or max_per_prototype < 1:
+        raise ValueError(f"select_map_entries: max_per_prototype must be an integer >= 1, got {max_per_prototype!r}")
+    scores, index = res.scores.tolist(), res.index.tolist()
+    selected, unused = res.selected.tolist(), res.unused.tolist()
+    if res.groups == [None]:
+        return [_pipnet_map_selection(scores, index, selected, unused, p, max_per_prototype) for p in range(len(index))]
+    return [_count_map_selection(index, res.groups, selected, p, max_per_prototype) for p in range(len(index))]
 
 
 # ---- geometry -----------------------------------------------------------------------------------------
@@ -396,3 +473,145 @@ def explanation_heatmaps(proto_features: Tensor, frames: Tensor, res: LocalExpla
                                    batch_size=batch_size)
     return ExplanationHeatmaps(entry=torch.tensor(entry, dtype=torch.int64).reshape(-1, 3),
                                prototype=torch.tensor(ids, dtype=torch.int64), heatmaps=heatmaps)
+
+
+def _pairs(fn: str, pairs, cols, limits, names: str) -> np.ndarray:
+    """``pairs`` as an int64 [N, cols] table with every column inside its limit, or ValueError."""
+    items = np.asarray(pairs if len(pairs) else np.zeros((0, cols)), dtype=np.float64)
+    if items.ndim != 2 or items.shape[1] != cols or (items != np.floor(items)).any():
+        raise ValueError(f"{fn}: pairs must be rows of {cols} integers")
+    items = items.astype(np.int64)
+    bad = (items < 0).any(axis=1) | (items >= np.asarray(limits, dtype=np.int64)[None, :]).any(axis=1)
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError(f"{fn}: pair {i} {tuple(int(v) for v in items[i])} lies outside the {names}")
+    return items
+
+
+def feature_map_overlays(proto_features: Tensor, pairs, lut: Tensor, *, size: int, alpha: float = K.OVERLAY_ALPHA,
+                         batch_size: int = 64, want_overlay: bool = True) -> K.MapOverlay:
+    """Per pair (b, p) the arrays behind the reference's ``*_overlay.png`` (vis_pipnet.py:454-475), see the module
+    docstring: ``MapOverlay(maps [N, h, w] float32, resized [N, S, S] float32, mask [N, S, S] uint8, colour [N, S, S]
+    uint8, overlay [N, S, S, 4] float64 or None)`` on the device, S = ``size``.
+
+    ``proto_features``: the [B, P, h, w] float32 similarity maps a forward returned (``net(xs, inference=True)[0]``),
+    h, w >= 3; our forward's output is NHWC-backed and is read in place, any other layout is copied once.  ``pairs``:
+    a list (or integer array) of (b, p); a pair may repeat.  ``lut`` [256, 3] float64 on the device: the colour table,
+    the reference's is ``matplotlib.colormaps['viridis'](np.arange(256))[:, :3]``.  ``alpha``: the fourth band on the
+    mask.  ``batch_size`` pairs are rendered per launch; without ``want_overlay`` the 32 bytes per pixel of the
+    overlay are neither computed nor allocated.  A wrong shape, dtype, pair, ``size`` or ``batch_size`` raises
+    ValueError, an operand off the ROCm device RuntimeError, before anything is launched.  Nothing in the call waits
+    for the device."""
+    fn = "feature_map_overlays"
+    if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
+        raise ValueError(f"{fn}: batch_size must be an integer >= 1, got {batch_size!r}")
+    if not torch.is_tensor(proto_features) or proto_features.dim() != 4:
+        raise ValueError(f"{fn}: proto_features must be the [B, P, h, w] tensor of a forward")
+    b, h, w, p, s = K.overlay_shapes(proto_features.permute(0, 2, 3, 1), lut, size, alpha)
+    items = _pairs(fn, pairs, 2, (b, p), f"{b} images or {p} prototypes")
+    if not (proto_features.is_cuda and lut.is_cuda):
+        raise RuntimeError(f"{fn}: proto_features and lut must be on a ROCm device; there is no CPU fallback")
+    dev = proto_features.device
+    proto = as_nhwc(proto_features)
+    n = items.shape[0]
+    out = K.MapOverlay(maps=torch.empty((n, h, w), dtype=torch.float32, device=dev),
+                       resized=torch.empty((n, s, s), dtype=torch.float32, device=dev),
+                       mask=torch.empty((n, s, s), dtype=torch.uint8, device=dev),
+                       colour=torch.empty((n, s, s), dtype=torch.uint8, device=dev),
+                       overlay=torch.empty((n, s, s, 4), dtype=torch.float64, device=dev) if want_overlay else None)
+    table = torch.from_numpy(items.astype(np.int32)).to(dev, non_blocking=True)                # checked above, sent once
+    for i in range(0, n, batch_size):
+        K.map_overlay(proto, table[i:i + batch_size], lut, s, alpha=alpha,
+                      out=K.MapOverlay(*(None if t is None else t[i:i + batch_size] for t in out)))
+    return out
+
+
+def _load_inputs(dataset, indices: Sequence[int], image_size: int, dev) -> Tuple[Tensor, Tensor]:
+    """(normalised float32 inputs [n, 3, S, S], resized uint8 frames [n, S, S, 3]) of ``dataset[i]`` on ``dev``."""
+    for i in indices:
+        if not 0 <= i < len(dataset):
+            raise ValueError(f"dataset index {i} lies outside the dataset of {len(dataset)} images")
+    packed = pack_images([dataset[i][0] for i in indices])
+    return DeviceEvalTransform(image_size)(packed, dev, want_u8=True)
+
+
+def prototype_map_overlays(net, dataset, res: PrototypeTopK, lut: Tensor, *, image_size: int, batch_size: int = 64,
+                           max_per_prototype: int = 3, want_overlay: bool = True,
+                           keep_frames: bool = False) -> PrototypeMapOverlays:
+    """The feature maps and overlays ``vizualize_network`` draws with ``visualize_prototype_maps`` (vis_pipnet.py
+    :354-486 PIP-Net, :889-1032 CountPIPNet) from a ``prototype_topk`` result: per shown entry the map, its sum, the
+    spline-resized map, the mask, the colour index and the RGBA overlay, see the module docstring.
+
+    ``net``: the PIPNet / CountPIPNet the pass ran (bare, under ``.module`` or in a world-size-1 ShardedInference);
+    it is put in eval mode, as the reference has it.  ``dataset``: the ``DecodedImageFolder`` the pass ran over.
+    ``lut`` [256, 3] float64 on the net's device: the colour table (``feature_map_overlays``).
+
+    The entries are ``select_map_entries(res, max_per_prototype)``.  The pass keeps no maps, so their distinct images
+    are decoded once each, ``batch_size`` at a time, and run through the located forward with the map written
+    (``explain_forward.located_forward_maps``: the bits of the pass, so ``maps[n].max()`` is the pooled value the
+    pass scored and its first maximum lies at ``(h_idx, w_idx)``); then one ``pipnet_map_overlay`` launch renders
+    ``batch_size`` entries.  A Gumbel CountPIPNet draws fresh noise in that forward: its maps are a new draw, not
+    the pass's -- a caller who kept the maps of its own forward renders them with ``feature_map_overlays``.
+    ``map_sum`` is computed on the host from a copy of the maps, which waits for the device once, after the last
+    launch.  The frames are dropped after their chunk unless ``keep_frames``.  Errors: ``feature_map_overlays``."""
+    fn = "prototype_map_overlays"
+    if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
+        raise ValueError(f"{fn}: batch_size must be an integer >= 1, got {batch_size!r}")
+    res = res.cpu()
+    selection = select_map_entries(res, max_per_prototype)
+    pn = res.scores.shape[0]
+    _, _, h, w = res.proto_shape
+    fake = torch.empty((0, h, w, pn), dtype=torch.float32, device="meta")
+    s = K.overlay_shapes(fake, lut, image_size)[4]
+    net = unwrap(net, fn)
+    if getattr(net, "_num_prototypes", pn) != pn:
+        raise ValueError(f"{fn}: the result holds {pn} prototypes, the net {net._num_prototypes}")
+    dev = _device(net, None)
+    if not lut.is_cuda:
+        raise RuntimeError(f"{fn}: lut must be on a ROCm device; there is no CPU fallback")
+    entry = [(p, g, j) for p, entries in enumerate(selection) for g, j in entries]
+    n = len(entry)
+    rank = [i + 1 for entries in selection for i in range(len(entries))]
+    of = [len(entries) for entries in selection for _ in entries]
+    pick = tuple(torch.tensor(col, dtype=torch.int64) for col in zip(*entry)) if n else None
+
+    def column(t: Tensor) -> Tensor:
+        return t[pick].clone() if n else t.new_empty((0,) + tuple(t.shape[3:]))
+
+    index = column(res.index)
+    by_image = {}                 # dataset index -> [(row n, prototype)]
+    for row, (i, (p, _, _)) in enumerate(zip(index.tolist(), entry)):
+        by_image.setdefault(i, []).append((row, p))
+    distinct = sorted(by_image)
+    maps = torch.empty((n, h, w), dtype=torch.float32, device=dev)
+    kept = []
+    net.eval()
+    with torch.no_grad():
+        for c0 in range(0, len(distinct), batch_size):
+            chunk = distinct[c0:c0 + batch_size]
+            xs, frames = _load_inputs(dataset, chunk, s, dev)
+            fwd, proto = located_forward_maps(net, xs, map_is_small(net, xs))
+            note_map(net, xs, fwd.hw)
+            if tuple(fwd.hw) != (h, w):
+                raise ValueError(f"{fn}: the net gives a {fwd.hw[0]} x {fwd.hw[1]} map at image_size {s}, the result "
+                                 f"was made with {h} x {w}")
+            rows = [row for i in chunk for row, _ in by_image[i]]
+            got = K.map_overlay(as_nhwc(proto), [(f, p) for f, i in enumerate(chunk) for _, p in by_image[i]], lut, s,
+                                out=K.MapOverlay(torch.empty((len(rows), h, w), dtype=torch.float32, device=dev),
+                                                 None, None, None, None)).maps          # a gather: nothing is resized
+            maps.index_copy_(0, torch.tensor(rows, dtype=torch.int64).to(dev, non_blocking=True), got)
+            if keep_frames:
+                kept.append(frames)
+    pictures = feature_map_overlays(maps.view(n, 1, h, w), [(i, 0) for i in range(n)], lut, size=s,
+                                    batch_size=batch_size, want_overlay=want_overlay)
+    frames = None
+    if keep_frames:
+        frames = torch.cat(kept) if kept else torch.empty((0, s, s, 3), dtype=torch.uint8, device=dev)
+    host = maps.cpu().numpy().astype(np.float64).reshape(n, h * w)
+    map_sum = torch.from_numpy(np.cumsum(host, axis=1)[:, -1].copy())        # a sequential sum in the stored order
+    return PrototypeMapOverlays(
+        entry=torch.tensor(entry, dtype=torch.int64).reshape(-1, 3), rank=torch.tensor(rank, dtype=torch.int64),
+        of=torch.tensor(of, dtype=torch.int64), index=index, score=column(res.scores), coords=column(res.coords),
+        h_idx=column(res.h_idx), w_idx=column(res.w_idx), maps=maps, map_sum=map_sum, resized=pictures.resized,
+        mask=pictures.mask, colour=pictures.colour, overlay=pictures.overlay,
+        frame_index=torch.tensor(distinct, dtype=torch.int64), frames=frames)

@@ -12,7 +12,9 @@ import copy
 import ctypes
 import dataclasses
 import functools
+import numbers
 import threading
+from collections import namedtuple
 
 from typing import Callable, Optional, Tuple
 
@@ -1907,6 +1909,85 @@ def heatmap_rgb8(proto_nhwc: Tensor, frames: Tensor, items, lut: Tensor, *, weig
     _lib.call("pipnet_heatmap_rgb8", proto_nhwc.data_ptr(), b, h, w, p, frames.data_ptr(), f, s, it_dev.data_ptr(), n,
               lut.data_ptr(), rows_h.data_ptr(), rows_v.data_ptr(), wh, wi, out.data_ptr(), _ptr(resized),
               torch.cuda.current_stream(dev).cuda_stream)
+    return out
+
+
+# ---- prototype feature-map overlays (csrc/overlay_ops.hip) ---------------------------------------
+OVERLAY_ALPHA = 0.7             # vis_pipnet.py:475
+MapOverlay = namedtuple("MapOverlay", "maps resized mask colour overlay")
+
+
+def overlay_shapes(proto_nhwc: Tensor, lut: Tensor, size, alpha=OVERLAY_ALPHA) -> Tuple[int, int, int, int, int]:
+    """(B, h, w, P, S) of the operands of ``map_overlay``; ValueError where a dtype, a shape, the size or alpha is not
+    the documented one.  Attribute comparisons only, on any device."""
+    fn = "map_overlay"
+    for what, t in (("proto_nhwc", proto_nhwc), ("lut", lut)):
+        if not torch.is_tensor(t):
+            raise ValueError(f"{fn}: {what} must be a tensor, got {type(t).__name__}")
+    if proto_nhwc.dtype != torch.float32 or proto_nhwc.dim() != 4 or min(proto_nhwc.shape[1:3]) < 3 or \
+            proto_nhwc.shape[3] < 1:
+        raise ValueError(f"{fn}: proto_nhwc must be float32 [B,h,w,P] with h, w >= 3 (a cubic spline needs three "
+                         f"samples) and P >= 1, got {proto_nhwc.dtype} {tuple(proto_nhwc.shape)}")
+    if lut.dtype != torch.float64 or tuple(lut.shape) != (256, 3):
+        raise ValueError(f"{fn}: lut must be float64 [256,3] (RGB), got {lut.dtype} {tuple(lut.shape)}")
+    if isinstance(size, bool) or not isinstance(size, numbers.Integral) or not 2 <= size < 1 << 14:
+        raise ValueError(f"{fn}: size must be an integer in 2 .. 16383, got {size!r}")
+    if isinstance(alpha, bool) or not isinstance(alpha, numbers.Real) or not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"{fn}: alpha must be a number in 0 .. 1, got {alpha!r}")
+    b, h, w, p = proto_nhwc.shape
+    # the library's own size rule: it holds the dimensions against its LDS budget before it looks at N == 0
+    if _lib.load().pipnet_map_overlay(None, 0, h, w, p, None, 0, None, int(size), float(alpha), None, None, None, None,
+                                      None, None) != 0:
+        raise ValueError(f"{fn}: the {h} x {w} map does not fit the 64 KiB of LDS beside a row of {size} pixels")
+    return b, h, w, p, int(size)
+
+
+def map_overlay(proto_nhwc: Tensor, items, lut: Tensor, size: int, *, alpha: float = OVERLAY_ALPHA,
+                out: Optional[MapOverlay] = None) -> MapOverlay:
+    """Per row (b, p) of the host integer table ``items`` [N,2] the arrays behind the ``*_overlay.png`` of
+    vis_pipnet.py:454-475: ``MapOverlay(maps [N,h,w] float32, resized [N,S,S] float32, mask [N,S,S] uint8, colour
+    [N,S,S] uint8, overlay [N,S,S,4] float64)`` with S = ``size`` -- the map ``proto_nhwc[b, :, :, p]``, its
+    ``scipy.ndimage.zoom`` to S x S, ``resized > 0.1``, the row of the 256-entry colour table ``cmap(resized)`` reads
+    (0 off the mask) and ``(*lut[colour], alpha)`` on the mask, zeros elsewhere (pipnet_map_overlay; the arithmetic
+    contract is in include/pipnet_amd.h, bit for bit tests/overlay_ref.py).  ``proto_nhwc`` [B,h,w,P] float32 with
+    h, w >= 3 and ``lut`` [256,3] float64, dense and on one ROCm device.  ``out``: a ``MapOverlay`` of tensors to
+    write into, None for a member that is not wanted (returned as given); without it all five are allocated.  A wrong
+    dtype, shape, size or alpha raises ValueError, a wrong device or layout or a row of ``items`` out of range
+    RuntimeError; nothing is launched then.  ``items`` may also be an int32 [N,2] tensor already on the device (one
+    upload for many launches): its rows cannot be read here, the caller has checked them, and the kernel writes
+    nothing for a row out of range.  One launch (none for N == 0), on the current stream."""
+    fn = "map_overlay"
+    b, h, w, p, s = overlay_shapes(proto_nhwc, lut, size, alpha)
+    _operand(fn, "proto_nhwc", proto_nhwc)
+    dev = proto_nhwc.device
+    _operand(fn, "lut", lut, dtype=torch.float64, shape=torch.Size((256, 3)), device=dev)
+    if torch.is_tensor(items) and items.is_cuda:       # a table already on the device: the caller has checked it
+        if items.dim() != 2:
+            raise RuntimeError(f"{fn}: a device table of items must be int32 [N,2], got shape {tuple(items.shape)}")
+        _operand(fn, "items", items, dtype=torch.int32, shape=torch.Size((items.shape[0], 2)), device=dev)
+        it_dev, n = items, items.shape[0]
+    else:
+        it = _host_i32(fn, "items", items, 2)
+        n = it.shape[0]
+        bad = (it < 0).any(axis=1) | (it[:, 0] >= b) | (it[:, 1] >= p)
+        if bad.any():
+            i = int(bad.argmax())
+            raise RuntimeError(f"{fn}: item {i} {tuple(int(v) for v in it[i])} lies outside the {b} images or {p} "
+                               f"prototypes")
+        it_dev = torch.from_numpy(it).to(dev, non_blocking=True) if n else None
+    spec = (("maps", torch.float32, (n, h, w)), ("resized", torch.float32, (n, s, s)), ("mask", torch.uint8, (n, s, s)),
+            ("colour", torch.uint8, (n, s, s)), ("overlay", torch.float64, (n, s, s, 4)))
+    if out is None:
+        out = MapOverlay(*(torch.empty(shape, device=dev, dtype=dtype) for _, dtype, shape in spec))
+    else:
+        if not isinstance(out, MapOverlay):
+            raise ValueError(f"{fn}: out must be a MapOverlay of tensors (None: not wanted), got {type(out).__name__}")
+        for (what, dtype, shape), t in zip(spec, out):
+            _operand(fn, what, t, dtype=dtype, shape=torch.Size(shape), device=dev, optional=True)
+    if n == 0:
+        return out
+    _lib.call("pipnet_map_overlay", proto_nhwc.data_ptr(), b, h, w, p, it_dev.data_ptr(), n, lut.data_ptr(), s,
+              float(alpha), *(_ptr(t) for t in out), torch.cuda.current_stream(dev).cuda_stream)
     return out
 
 

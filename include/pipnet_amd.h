@@ -64,8 +64,8 @@ extern "C" {
  * pipnet_draw_rects_rgb8) and the attribution-image entry points (pipnet_saliency_*), and the row-scaled
  * low-precision Linear2 (pipnet_linear_bf16_mix_rowscale, pipnet_linear_s3_rowscale + _label), and the state
  * merges of the sharded dataset passes (pipnet_topk_merge, pipnet_proto_stats_merge, pipnet_colsum_merge_f64,
- * pipnet_part_purity_merge), and the similarity-heatmap entry point (pipnet_heatmap_rgb8); no signature
- * changed. */
+ * pipnet_part_purity_merge), and the similarity-heatmap entry point (pipnet_heatmap_rgb8), and the feature-map
+ * overlay entry point (pipnet_map_overlay); no signature changed. */
 #define PIPNET_AMD_ABI_VERSION 4
 int pipnet_amd_abi_version(void);
 const char* pipnet_amd_status_string(int status);
@@ -956,6 +956,53 @@ int pipnet_draw_rects_rgb8(const uint8_t* frames, int F, int fh, int fw, const i
 int pipnet_heatmap_rgb8(const float* proto, int B, int h, int w, int P, const uint8_t* frames, int F, int S,
                         const int32_t* items, int N, const uint8_t* lut, const int32_t* rows_h, const int32_t* rows_v,
                         float w_heat, float w_img, uint8_t* out, uint8_t* resized, void* stream);
+
+/* ---- prototype feature-map overlays (util/vis_pipnet.py:454-475 and :1000-1021, *_overlay.png;
+ * csrc/overlay_ops.hip) ------------------------------------------------------------------------------------
+ * pipnet_map_overlay: per row (b, p) of items [N,2] int32 (device) the arrays behind the reference's overlay of
+ *   prototype p on image b: scipy.ndimage.zoom(m, (S / h, S / w)) of the map m = proto[b, :, :, p] (order 3, mode
+ *   'constant', grid_mode False), mask = resized > 0.1 and overlay[y, x] = (*cmap(resized[y, x])[:3], alpha).
+ *   The arithmetic contract.  h, w >= 3 and S >= 2.  Up to the final rounding everything is float64, every
+ *   operation below is one IEEE operation (correctly rounded divisions), nothing is contracted into a fused
+ *   multiply-add, and the order is the one written:
+ *   prefilter (spline_filter, order 3; mode 'constant' takes the mirror boundary and pads nothing), along axis 0
+ *     (every column) first, then along axis 1 (every row), with z = sqrt(3) - 2 and gain = (1 - z) * (1 - 1 / z);
+ *     on a line c[0..n):
+ *       1. c[i] *= gain for every i;
+ *       2. zn = pow(z, n - 1), computed on the host with libm inside this entry point, once for h and once for w;
+ *       3. c[0] = c[0] + zn * c[n-1];
+ *       4. for i = 1 .. n-2: c[0] += zi * (c[i] + zn * c[n-1-i]); zi *= z, starting from zi = z;
+ *       5. c[0] /= 1 - zn * zn;
+ *       6. causal pass, i = 1 .. n-1: c[i] += z * c[i-1];
+ *       7. c[n-1] = (z * c[n-2] + c[n-1]) * z / (z * z - 1);
+ *       8. anticausal pass, i = n-2 .. 0: c[i] = z * (c[i+1] - c[i]);
+ *   zoom: per axis zoom = (n - 1) / (S - 1), a double computed on the host; output index i has the coordinate
+ *     x = i * zoom, f = floor(x), y = x - f, t = 1 - y; its taps run from f - 1 to f + 2 with the weights
+ *       w0 = t * t * t / 6, w1 = (y * y * (y - 2) * 3 + 4) / 6, w2 = (t * t * (t - 2) * 3 + 4) / 6,
+ *       w3 = 1 - w0 - w1 - w2;
+ *     a tap index is mirrored once: idx < 0 -> -idx, idx >= n -> 2 * (n - 1) - idx;
+ *     s = 0; for a = 0 .. 3 over the rows, then b = 0 .. 3 over the columns: v = c[ya][xb]; v *= wy[a]; v *= wx[b];
+ *     s += v; resized = (float) s (zoom's output takes the input's dtype);
+ *   threshold and colour, in float32: mask = resized > 0.1f; colour = min(trunc(resized * 256f), 255), clamped
+ *     before the conversion so that huge values read 255, and 0 where the mask is false; NaN is outside the
+ *     contract, its mask is false;
+ *   overlay [S,S,4] float64: (lut[colour][0..2], alpha) where the mask is true, zeros elsewhere.
+ *   proto [B,h,w,P] float32 (the NHWC storage of a forward's proto_features); lut [256,3] float64, 16-byte aligned
+ *   (the caller's colour table: matplotlib.colormaps['viridis'](np.arange(256))[:, :3] in the reference; read only
+ *   when overlay is asked for, but never NULL); alpha: the reference's 0.7.  Outputs, each NULL or written: maps
+ *   [N,h,w] float32 (the map itself, dense), resized [N,S,S] float32, mask [N,S,S] uint8 (0 / 1), colour [N,S,S]
+ *   uint8, overlay [N,S,S,4] float64 (16-byte aligned); with maps alone the call is a gather of the maps and
+ *   resizes nothing.  A row of items with b or p out of range writes nothing.
+ *   One workgroup of 256 threads per (row, band of up to 32 output rows); the prefiltered map is staged in LDS as
+ *   doubles beside the colour table, the row taps and the band's float32 tile: ceil2(h * (w | 1)) * 8 + 6144 +
+ *   band * (48 + 4 * S) bytes must fit 64 KiB for some band in 32, 16, .., 1 (the largest that fits is taken; band 32
+ *   at 26 x 26 -> 224, and a square map of up to 85 x 85 at S = 224, 83 x 83 at S = 1024), N * ceil(S / band) below 2^24, S * S below 2^29; byte offsets are
+ *   64-bit.  16-byte stores throughout when S % 4 == 0 and resized is 16-byte, mask and colour 4-byte aligned; one
+ *   element per lane for those three otherwise; the same values.  N == 0 launches nothing.  A violation or a NULL
+ *   proto, items or lut returns PIPNET_ERR_ARG before any HIP call. */
+int pipnet_map_overlay(const float* proto, int B, int h, int w, int P, const int32_t* items, int N, const double* lut,
+                       int S, double alpha, float* maps, float* resized, uint8_t* mask, uint8_t* colour,
+                       double* overlay, void* stream);
 
 /* ---- attribution images (util/interpret_idg.py:413-427 fold / normalise / blend, :183-204
  * normalize_attribution_map, :442-446 un-normalised image, :626-641 logit mode; csrc/saliency_ops.hip) ----

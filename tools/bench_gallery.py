@@ -22,8 +22,22 @@ prototypes each.  Random maps and frames stand in for a forward (the kernel's wo
              Pillow and numpy, the copy of the [B, P, h, w] maps to the host included (a table lookup stands in for
              cv2.applyColorMap)
 
+``--overlays`` times the prototype feature-map overlays (gallery.feature_map_overlays, pipnet_map_overlay) at C2
+dimensions: ``--count`` (1,536) pairs drawn from a 26 x 26 x 768 map of 64 images, rendered to 224^2.  Random maps
+stand in for a forward and three ramps for viridis (the kernel's work does not depend on the values: a pixel off the
+mask is stored as zeros):
+
+  overlays   feature_map_overlays, whole call, device events around it (the results are allocated inside)
+  launches   the pipnet_map_overlay launches alone into preallocated results (events), and the bytes the algorithm
+             moves per second: per entry the h x w float32 map in and out, and 38 bytes out per pixel (resized 4,
+             mask 1, colour 1, overlay 32); both at ``--batch-size`` entries per launch and with every entry in one
+  reference  the reference's chain (vis_pipnet.py:459-475) on the host CPU for ``--host-entries`` overlays: scipy's
+             ``zoom``, the mask and the Python loop calling matplotlib's ``cmap`` once per pixel; skipped where
+             scipy or matplotlib cannot be imported
+
 Usage: python tools/bench_gallery.py [--prototypes 768] [--k 10] [--size 224] [--images 1024] [--out FILE]
        python tools/bench_gallery.py --heatmaps [--entries 8] [--size 224] [--batch-size 64] [--out FILE]
+       python tools/bench_gallery.py --overlays [--count 1536] [--host-entries 3] [--size 224] [--batch-size 64] [--out FILE]
 """
 import argparse
 import os
@@ -40,7 +54,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from count_pipnet_amd import kernels as K                                               # noqa: E402
 from count_pipnet_amd.data import DecodedImageFolder, DeviceEvalTransform, pack_images  # noqa: E402
 from count_pipnet_amd.explain_forward import img_coordinates, patch_skip                # noqa: E402
-from count_pipnet_amd.gallery import explanation_heatmaps, prototype_gallery            # noqa: E402
+from count_pipnet_amd.gallery import explanation_heatmaps, feature_map_overlays, prototype_gallery    # noqa: E402
 from count_pipnet_amd.local import LocalExplanation                                     # noqa: E402
 from count_pipnet_amd.topk import PrototypeTopK                                         # noqa: E402
 
@@ -192,6 +206,96 @@ def heatmaps_main(a, dev, say) -> None:
     say(f"reference / heatmaps at batch_size {a.batch_size} = {t_ref * 1e3 / best:.0f}")
 
 
+def time_overlays(say, nhwc, feats, pairs, lut, s: int, batch_size: int) -> float:
+    """Times ``feature_map_overlays`` and its launches alone at ``batch_size``; the whole call's best time in ms."""
+    n, hw = len(pairs), nhwc.shape[1] * nhwc.shape[2]
+    per_entry = 2 * hw * 4 + s * s * 38
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    whole = []
+    for i in range(6):                                                     # the first call is the warm-up
+        out = None                                                         # the allocator hands the blocks back
+        torch.cuda.synchronize()
+        start.record()
+        out = feature_map_overlays(feats, pairs, lut, size=s, batch_size=batch_size)
+        end.record()
+        torch.cuda.synchronize()
+        whole.append(start.elapsed_time(end))
+    assert tuple(out.overlay.shape) == (n, s, s, 4)
+    say(f"batch_size {batch_size}:")
+    say(f"overlays   feature_map_overlays, whole call (events)   {min(whole[1:]):9.3f} ms   (5 runs: "
+        + ", ".join(f"{t:.3f}" for t in whole[1:]) + ")")
+    table = torch.tensor(pairs, dtype=torch.int32, device=nhwc.device)     # sent once, as the call above does
+    dst = K.MapOverlay(*(torch.empty_like(t) for t in out))
+    chunks = [(table[i:i + batch_size], K.MapOverlay(*(t[i:i + batch_size] for t in dst))) for i in range(0, n, batch_size)]
+    reps, alone = 10, []
+    for i in range(4):
+        torch.cuda.synchronize()
+        start.record()
+        for _ in range(reps):
+            for it, part in chunks:
+                K.map_overlay(nhwc, it, lut, s, out=part)
+        end.record()
+        torch.cuda.synchronize()
+        alone.append(start.elapsed_time(end) / reps)
+    assert all(torch.equal(a, b) for a, b in zip(dst, out))
+    rate = n * per_entry / (min(alone[1:]) * 1e-3)
+    say(f"launches   {len(chunks)} pipnet_map_overlay launch(es) (events)       {min(alone[1:]):9.3f} ms   (3 x {reps} runs: "
+        + ", ".join(f"{t:.3f}" for t in alone[1:]) + f"), {min(alone[1:]) / len(chunks) * 1e3:.1f} us per launch")
+    say(f"           {rate / 1e12:.3f} TB/s of algorithmic bytes = {100 * rate / HBM_ACHIEVABLE:.1f} % of the "
+        f"{HBM_ACHIEVABLE / 1e12:.1f} TB/s a streaming kernel reaches from HBM (8 TB/s peak)")
+    return min(whole[1:])
+
+
+def host_overlays(maps: np.ndarray, s: int) -> int:
+    """The baseline: vis_pipnet.py:459-475 per overlay with the reference's libraries, or -1 without them."""
+    try:
+        import matplotlib
+        from scipy.ndimage import zoom
+    except ImportError:
+        return -1
+    cmap = matplotlib.colormaps["viridis"]
+    made = 0
+    for feature_map_np in maps:
+        resized_feature_map = zoom(feature_map_np, (s / feature_map_np.shape[0], s / feature_map_np.shape[1]))
+        mask = resized_feature_map > 0.1
+        overlay = np.zeros((*resized_feature_map.shape, 4))
+        for y in range(resized_feature_map.shape[0]):
+            for x in range(resized_feature_map.shape[1]):
+                if mask[y, x]:
+                    color = cmap(resized_feature_map[y, x])
+                    overlay[y, x] = (*color[:3], 0.7)
+        made += int(overlay.shape == (s, s, 4))
+    return made
+
+
+def overlays_main(a, dev, say) -> None:
+    b, pn, hw, s, n = 64, 768, 26, a.size, a.count
+    g = torch.Generator().manual_seed(6)
+    nhwc = (torch.rand((b, hw, hw, pn), generator=g) ** 3).to(dev)         # x^3 > 0.1 for about half of the pixels
+    feats = nhwc.permute(0, 3, 1, 2)                                       # [B, P, h, w], NHWC-backed as a forward's
+    x = np.arange(256) / 255.0
+    lut = torch.from_numpy(np.stack([x, 1 - x, 0.5 + 0.5 * x], axis=1)).to(dev)
+    pairs = torch.stack([torch.randint(0, b, (n,), generator=g), torch.randint(0, pn, (n,), generator=g)], dim=1).tolist()
+    per_entry = 2 * hw * hw * 4 + s * s * 38
+    say("python tools/bench_gallery.py " + " ".join(sys.argv[1:]))
+    say(f"{n} overlays at {s}^2 from a {hw} x {hw} x {pn} map of {b} images; {per_entry} bytes per entry (the map in "
+        f"and out, 38 bytes per pixel out: resized 4, mask 1, colour 1, overlay 32), {n * per_entry / 1e6:.1f} MB in all; "
+        f"the maps are {nhwc.numel() * 4 / 1e6:.0f} MB")
+    best = time_overlays(say, nhwc, feats, pairs, lut, s, a.batch_size)
+    if n != a.batch_size:
+        time_overlays(say, nhwc, feats, pairs, lut, s, n)                  # every entry in one launch
+    maps = np.stack([feats[bi, p].cpu().numpy() for bi, p in pairs[:a.host_entries]])
+    t0 = time.perf_counter()
+    done = host_overlays(maps, s)
+    t_ref = time.perf_counter() - t0
+    if done < 0:
+        say("reference  scipy or matplotlib cannot be imported here: the host chain was not timed")
+        return
+    say(f"reference  zoom + mask + cmap per pixel on the host    {t_ref * 1e3:9.1f} ms   ({done} entries, "
+        f"{t_ref / done * 1e3:.1f} ms per entry, {t_ref / done * n:.0f} s for {n})")
+    say(f"reference per entry / overlays per entry at batch_size {a.batch_size} = {t_ref / done * 1e3 / (best / n):.0f}")
+
+
 def write_out(path, lines) -> None:
     if path:
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -203,6 +307,9 @@ def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--heatmaps", action="store_true", help="time the similarity heatmaps instead of the gallery")
     ap.add_argument("--entries", type=int, default=8, help="--heatmaps: kept prototypes per (image, class)")
+    ap.add_argument("--overlays", action="store_true", help="time the feature-map overlays instead of the gallery")
+    ap.add_argument("--count", type=int, default=1536, help="--overlays: how many (image, prototype) pairs")
+    ap.add_argument("--host-entries", type=int, default=3, help="--overlays: overlays the host chain is timed on")
     ap.add_argument("--prototypes", type=int, default=768)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--size", type=int, default=224)
@@ -219,8 +326,8 @@ def main() -> None:
         print(s, flush=True)
         lines.append(s)
 
-    if a.heatmaps:
-        heatmaps_main(a, dev, say)
+    if a.heatmaps or a.overlays:
+        (heatmaps_main if a.heatmaps else overlays_main)(a, dev, say)
         write_out(a.out, lines)
         return
     with tempfile.TemporaryDirectory() as root:
